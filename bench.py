@@ -36,13 +36,6 @@ for _p in (os.path.join(REPO, "stylegan-for-facerec_amd"), REPO):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
-# The weight gradients run on a second HIP stream.  HIP multiplexes streams onto GPU_MAX_HW_QUEUES (default 4) hardware
-# queues round-robin; once RCCL has created its own streams the side stream can land on the SAME queue as the main
-# stream and the two serialise (measured: 19.7 instead of 17.8 ms per step with one rank).  Must be set before the HIP
-# runtime initialises.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
-
 
 def parse():
     ap = argparse.ArgumentParser()
@@ -68,7 +61,13 @@ def parse():
                     help="skip the short timings of the other BASELINE.json configs after the headline")
     ap.add_argument("--kernel-table", default="", help="write the per-launch timing table of the instrumented step")
     ap.add_argument("--clock-log", default="", help="write every shader-clock / power sample of the timed loop (rank 0)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed loop, write what its last step computed as DIR/<name>.npy (float32, rank 0): "
+                         "the loss, top-1 / top-5 precision and a fixed seeded sample of the parameters it updated")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def spawn_ranks(args):
@@ -532,8 +531,9 @@ def timed_loop(step, xs, ys, warmup, steps, world, device, sampler=None, sync_ti
         sync_timer.on = True
     t0 = time.perf_counter()
     for i in range(steps):
-        loss, _prec = step(xs[(warmup + i) % nb], ys[(warmup + i) % nb])
+        loss, prec = step(xs[(warmup + i) % nb], ys[(warmup + i) % nb])
     torch.cuda.synchronize()
+    timed_loop.last = (loss, prec)  # what the last timed step returned to its caller
     timed_loop.dt_local = time.perf_counter() - t0  # this rank's own time, before it waits for the slowest one
     if world > 1:
         dist.barrier()
@@ -546,6 +546,23 @@ def timed_loop(step, xs, ys, warmup, steps, world, device, sampler=None, sync_ti
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
     return dt, float(loss.detach()), clocks
+
+
+DUMP_PARAM_SAMPLE = 1 << 22  # parameter elements drawn into params.npy: at most 16 MB of float32
+
+
+def dump_outputs(out_dir, loss, prec, model, head):
+    """What the last timed step computed, as float32 DIR/<name>.npy: the loss and top-1 / top-5 precision it returned, and
+    the parameters it updated in place (backbone then head, ``named_parameters`` order, flattened) at a fixed seeded sample
+    of indices.  The inputs and weights are seeded, so two builds run with the same arguments compare element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    params = [p for m in (model, head) for _n, p in m.named_parameters()]
+    flat = torch.cat([p.detach().reshape(-1).float() for p in params])
+    idx = np.unique(np.random.default_rng(0).integers(0, flat.numel(), DUMP_PARAM_SAMPLE))
+    arrays = {"loss": loss, "top1": prec[0], "top5": prec[1], "params": flat[torch.from_numpy(idx).to(flat.device)]}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 # The other BASELINE.json configs, timed briefly behind the headline (same step function, same data parallelism when
@@ -626,6 +643,8 @@ def main():
 
     sampler = ClockSampler(local) if rank == 0 else None
     dt, loss_val, clocks = timed_loop(step, xs, ys, args.warmup, args.steps, world, device, sampler, sync_timer)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *timed_loop.last, model, head)
     dp_rec = dp_record(rank, world, device, dp, sync_timer, timed_loop.dt_local, args.steps) if dp is not None else None
     assert loss_val == loss_val, "loss is NaN"
     if sampler is not None and args.clock_log:

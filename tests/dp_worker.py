@@ -5,7 +5,6 @@ parameters must stay identical across ranks after optimizer steps."""
 import os
 import sys
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(os.path.dirname(HERE), "stylegan-for-facerec_amd"))
 

@@ -21,7 +21,6 @@ import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "stylegan-for-facerec_amd"))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 os.environ["FRHIP_FORCE_DP"] = "1"
 
 import torch  # noqa: E402

@@ -5,7 +5,6 @@ weight on the same GPU, and the oracle (CPU) on the same numbers."""
 import os
 import sys
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 sys.path.insert(0, REPO)

@@ -1308,6 +1308,34 @@ def test_bench_spawns_its_own_ranks(tmp_path):
     assert bad.returncode != 0 and "WORLD_SIZE=1" in bad.stderr
 
 
+def test_bench_dumps_what_the_last_timed_step_computed(tmp_path):
+    """``bench.py --dump-outputs DIR``: the loss, top-1 / top-5 and a seeded sample of the updated parameters of the last
+    timed step as float32 .npy, 64 MB at most.  The same arguments give the same inputs, so two runs agree; one timed
+    step less leaves different parameters (``--steps`` sets the number of steps that ran)."""
+    _need_gpu()
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    dumps = {}
+    for tag, steps in (("a", 2), ("b", 2), ("c", 1)):
+        cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--batch", "16",
+               "--classes", "1000", "--no-cpu-baseline", "--no-roofline", "--dump-outputs", str(tmp_path / tag)]
+        out = subprocess.run(cmd, cwd=repo, env=env, capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
+        assert json.loads(out.stdout.strip().splitlines()[-1])["steps"] == steps
+        files = sorted(os.listdir(tmp_path / tag))
+        assert files == ["loss.npy", "params.npy", "top1.npy", "top5.npy"], files
+        dumps[tag] = {f[:-4]: np.load(tmp_path / tag / f) for f in files}
+        assert all(v.dtype == np.float32 for v in dumps[tag].values())
+        assert sum(os.path.getsize(tmp_path / tag / f) for f in files) <= 64 << 20
+    a, b, c = dumps["a"], dumps["b"], dumps["c"]
+    assert np.isfinite(a["loss"]) and a["loss"].shape == () and a["params"].size > 1 << 21
+    for k in a:
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-3, atol=1e-4, err_msg=k)
+    assert a["params"].shape == c["params"].shape and np.abs(a["params"] - c["params"]).max() > 1e-3
+
+
 def _write_stage2_checkpoint(path, seed=19):
     """A Stage-2 (ReStyle) checkpoint in the G9 layout: {'state_dict': encoder.input_layer.* / encoder.body.* + decoder and
     style-head keys that Stage 3 ignores, 'latent_avg', 'opts'} (reference restyle_psp.py:419-437)."""

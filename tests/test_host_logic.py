@@ -387,6 +387,17 @@ def test_bench_gpus_flag_starts_that_many_ranks():
     assert not [l for l in out.stdout.splitlines() if l.startswith("{")]
 
 
+def test_bench_refuses_fewer_than_one_timed_step():
+    """``--steps`` is the number of timed steps: zero would time nothing and leave no last step to report."""
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = subprocess.run([sys.executable, "bench.py", "--steps", "0"], cwd=repo, env=env, capture_output=True, text=True,
+                         timeout=600)
+    assert out.returncode == 2 and "--steps must be at least 1" in out.stderr, out.stderr[-2000:]
+
+
 def test_readiness_marks_follow_the_arena_order():
     """engine.BackbonePlan._order_ready_marks (round 3): a deferring weight-gradient launch completes its predecessor's
     gradient one launch late, possibly in the NEXT unit's mark.  Announcements must still walk the gradient arena front to

@@ -24,7 +24,7 @@ import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
-import bench  # noqa: E402  (sets GPU_MAX_HW_QUEUES before torch starts the HIP runtime)
+import bench  # noqa: E402
 import torch  # noqa: E402
 
 

@@ -13,7 +13,6 @@ import time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "stylegan-for-facerec_amd"))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import argparse  # noqa: E402
 
 import torch  # noqa: E402
