@@ -205,8 +205,7 @@ int fr_conv_wgrad(const FrWgradArgs* args, int dtype, void* stream);
  * GW in {56, 28, 14, 7}, channels multiples of 64): the input tile holds the four parity planes of the strip. */
 int fr_conv_wgrad_strip(const FrWgradArgs* args, void* stream);
 int fr_conv_wgrad_strip_supported(int Cout, int Cin, int W);
-/* 1 when fr_conv_wgrad_strip serves these arguments (every served shape honours defer / prev_*; 0 also when the
- * deferral is switched off with FRHIP_WGRAD_DEFER=0).  fr_reduce_slabs: out[i] = sum over the slabs g = 0 .. groups-1
+/* 1 when fr_conv_wgrad_strip serves these arguments (every served shape honours defer / prev_*).  fr_reduce_slabs: out[i] = sum over the slabs g = 0 .. groups-1
  * of slab[g*n + i] in the library's fixed order (chunks of 16 slabs, csrc/slab_sum.h; n % 4 == 0, groups <= 256): the
  * sum a deferring launch left to its caller. */
 int fr_conv_wgrad_strip_defers(const FrWgradArgs* args);

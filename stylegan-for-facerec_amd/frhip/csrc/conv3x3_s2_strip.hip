@@ -327,18 +327,17 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_s2_kernel(const FrConvArgs
   // and its vector pipe through every tap list.  The halves touch disjoint columns of the output tile and of the reduction
   // scratch, so each gets barriers of its own (an LDS counter, 4 waves) and waves 4-7 start their first tap list when waves
   // 0-3 have finished theirs: from then on one wave of a SIMD issues MFMAs while the other runs its epilogue.  Same
-  // arithmetic, same order: bit-identical.  (xcd bit 1: FRHIP_S2_STAGGER, default on.)
+  // arithmetic, same order: bit-identical.
   constexpr bool STG = KIND == 1 && NW == 8 && WN == 8;
-  const bool stg = STG && (xcd & 2);
-  const int half = stg ? wave >> 2 : 0;
-  const int htid = stg ? (tid & 255) : tid;
-  const int hnth = stg ? 256 : NTH;
-  const int hoch = stg ? OCH / 2 : OCH;       // 16-byte chunks of a tile row this half moves
+  const int half = STG ? wave >> 2 : 0;
+  const int htid = STG ? (tid & 255) : tid;
+  const int hnth = STG ? 256 : NTH;
+  const int hoch = STG ? OCH / 2 : OCH;       // 16-byte chunks of a tile row this half moves
   const int hc0 = half * hoch;
   volatile unsigned* hctr = reinterpret_cast<volatile unsigned*>(smem + C::SYNC_OFF) + half;  // [0], [1]: barrier counters; [2]: start flag
   unsigned hgen = 0;
   auto hsync = [&]() {
-    if (!stg) {
+    if constexpr (!STG) {
       __syncthreads();
       return;
     }
@@ -491,7 +490,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_s2_kernel(const FrConvArgs
     }
     if (stats) {
       const size_t prow = (size_t)(cls < 0 ? 0 : cls) * nstrips + sblk;  // gradient: rows ordered [class][strip]
-      const int hcout = stg ? COUT / 2 : COUT;
+      const int hcout = STG ? COUT / 2 : COUT;
       for (int c = htid; c < 2 * hcout; c += hnth) {
         const int k = c / hcout, n = half * hcout + c - k * hcout;
         float t = 0.f;
@@ -570,7 +569,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_s2_kernel(const FrConvArgs
     S2_STAMP(2);
     zero_acc();
     issue_aux(0);
-    if (stg) {
+    if constexpr (STG) {
       volatile unsigned* start = reinterpret_cast<volatile unsigned*>(smem + C::SYNC_OFF) + 2;
       if (half == 1) {  // half a class behind: wait for waves 0-3 to finish their first tap list
         while (*start < 4u) __builtin_amdgcn_s_sleep(2);
@@ -605,10 +604,9 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_s2_kernel(const FrConvArgs
   }
 }
 
-static int s2_xcd_order() {  // bit 0: FRHIP_XCD_ORDER=0: strips in dispatch order; bit 1: FRHIP_S2_STAGGER=0: halves in lock-step
+static int s2_xcd_order() {  // bit 0: FRHIP_XCD_ORDER=0: strips in dispatch order
   static const int* v = fr_option_slot("FRHIP_XCD_ORDER", 1);
-  static const int* g = fr_option_slot("FRHIP_S2_STAGGER", 1);
-  return (*v != 0 ? 1 : 0) | (*g != 0 ? 2 : 0);
+  return *v != 0 ? 1 : 0;
 }
 
 template <int CIN, int COUT, int WL, int ROWS, int WN, int NW, int KIND, int PRO, int NSPL, int NIMG>

@@ -428,11 +428,10 @@ extern "C" int fr_conv_wgrad_strip_supported(int Cout, int Cin, int W) {
   return W == 112 || W == 56 || W == 28 || W == 14 || W == 7;
 }
 
-// every shape fr_conv_wgrad_strip serves honours defer / prev_* (FRHIP_WGRAD_DEFER=0 turns the answer off: A/B switch)
+// every shape fr_conv_wgrad_strip serves honours defer / prev_*
 extern "C" int fr_conv_wgrad_strip_defers(const FrWgradArgs* args) {
-  static const int* on = fr_option_slot("FRHIP_WGRAD_DEFER", 1);
   const FrWgradArgs& a = *args;
-  if (!*on || a.ldg % 8 || a.lda % 8 || !a.slab || a.nsplit < 1 || a.nsplit > 256 || a.KH != 3 || a.KW != 3 || a.pad != 1 ||
+  if (a.ldg % 8 || a.lda % 8 || !a.slab || a.nsplit < 1 || a.nsplit > 256 || a.KH != 3 || a.KW != 3 || a.pad != 1 ||
       a.Cout % CT || a.SC % CT)
     return 0;
   if (a.stride == 2) return a.GH == a.GW && a.SH == 2 * a.GH && a.SW == 2 * a.GW && (a.GW == 56 || a.GW == 28 || a.GW == 14 || a.GW == 7);

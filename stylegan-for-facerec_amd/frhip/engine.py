@@ -203,6 +203,22 @@ class _EvWait(object):
         self.stream.wait_event(self.ev)
 
 
+# Workgroups of a weight-gradient launch (dW tiles x image groups): 128, HALF the chip.  A weight-gradient workgroup
+# holds 87 KB of LDS and a strip workgroup of the main stream 142 KB: the two never share a CU, so a launch that covers
+# (nearly) every CU does not run BESIDE the data gradients, it alternates with them (the timeline of the 224-workgroup
+# default of rounds 3-4: every strip launch of the backward pass started on the 32 free CUs and waited for the rest).
+# With 128 the side stream owns half of the CUs and the main stream the other half, and the image groups divide the
+# batch exactly (256 images / 8 groups; 14 groups left 19 images to some workgroups and 18 to others).  Round 5, same-box
+# alternations (profiles/r05_ab_wgrad_wgs.txt): IR-50 bs 256 14.26-14.33 against 14.43-14.50 ms per step (224), 96:
+# 15.18, 160 / 192 / 208 / 256: 14.72-14.77 / 14.53; IR-SE-101 bs 128 16.94-16.99 against 18.14-18.22; pSp bs 256
+# 16.31 against 16.72.  Per-width / per-role overrides (temporary switches, removed) found nothing better than one
+# value for all.
+_WGRAD_WGS = 128  # the slab sum takes <= 256 groups
+# (Round 6, measured again with the lighter tail of the main stream: 256 / 192 workgroups for the two HBM-bound weight
+# gradients of the first unit, 112x112 -- 14.055-14.078 / 14.085-14.094 against 14.021-14.064 ms per step: nothing.)
+_BN_NEXT_MB = 20  # smallest unit-input gradient (MB) whose BN1 backward also takes the BN2-backward sums in front of it
+
+
 _SIDE_STREAMS = {}
 
 
@@ -246,21 +262,7 @@ class BackbonePlan(object):
         # the side stream is low priority: weight gradients fill the CUs the main chain (dgrads, BN/PReLU backward)
         # leaves idle instead of splitting the machine with it (HIP: 1 low .. -1 high; either way measured the same)
         self.stream2_t = _side_stream(device, 1) if self.dual else self.stream1_t
-        # Workgroups of a weight-gradient launch (dW tiles x image groups): 128, HALF the chip.  A weight-gradient workgroup
-        # holds 87 KB of LDS and a strip workgroup of the main stream 142 KB: the two never share a CU, so a launch that covers
-        # (nearly) every CU does not run BESIDE the data gradients, it alternates with them (the timeline of the 224-workgroup
-        # default of rounds 3-4: every strip launch of the backward pass started on the 32 free CUs and waited for the rest).
-        # With 128 the side stream owns half of the CUs and the main stream the other half, and the image groups divide the
-        # batch exactly (256 images / 8 groups; 14 groups left 19 images to some workgroups and 18 to others).  Round 5, same-box
-        # alternations (profiles/r05_ab_wgrad_wgs.txt): IR-50 bs 256 14.26-14.33 against 14.43-14.50 ms per step (224), 96:
-        # 15.18, 160 / 192 / 208 / 256: 14.72-14.77 / 14.53; IR-SE-101 bs 128 16.94-16.99 against 18.14-18.22; pSp bs 256
-        # 16.31 against 16.72.  Per-width / per-role overrides (temporary switches, removed) found nothing better than one
-        # value for all.
-        self.wgrad_wgs = min(256, max(64, _switch("FRHIP_WGRAD_WGS", 128)))  # the slab sum takes <= 256 groups
-        # (Round 6, measured again with the lighter tail of the main stream: 256 / 192 workgroups for the two HBM-bound weight
-        # gradients of the first unit, 112x112 -- 14.055-14.078 / 14.085-14.094 against 14.021-14.064 ms per step: nothing.)
         self.stream2 = ctypes.c_void_p(self.stream2_t.cuda_stream)
-        self.edge_signal = bool(_switch("FRHIP_EDGE_SIGNAL", 1))  # dependency edges as completion signals (_side_after_main)
         self.S = int(module.input_size if isinstance(module.input_size, int) else module.input_size[0])
         self.generation = 0
         # (FRHIP_GRAPH, rounds 2-3: the two launch lists captured into HIP graphs.  Replay was SLOWER than eager launches at
@@ -290,7 +292,6 @@ class BackbonePlan(object):
         self.slab, self._slab_users = None, []
         # deferred slab sums (FrWgradArgs.defer / prev_*): a weight-gradient launch that supports it leaves the sum of its
         # slabs to the NEXT such launch of the side stream (two slab buffers alternate); fr_reduce_slabs flushes the last
-        self.defer_slabs = True  # (FRHIP_WGRAD_DEFER=0 turns the library's answer off)
         self.slab2, self._slab2_users, self._slab_flip = None, [], 0
         self.slab3, self._slab3_users = None, []  # slabs of the launches that sum their own (the deferring chain skips them)
         self._pending = None  # (launch that wrote the slabs, groups, n, dw tensor, parameter)
@@ -300,7 +301,7 @@ class BackbonePlan(object):
         self._alloc()
         self._bind_params()
         # weight layouts (round 6): the packed 3x3 copies the LDS-strip kernels read are kept in MFMA-fragment order
-        self.w_frag = self.fr == FR_BF16 and bool(_switch("FRHIP_W_FRAG", 1))
+        self.w_frag = self.fr == FR_BF16
         self._weight_layout = {}
         self._pack_targets = set(id(d[k]) for d in self.ubuf for k in ("wp1", "wp2", "wt1", "wt2") if k in d)
         self._build_forward()
@@ -518,7 +519,9 @@ class BackbonePlan(object):
         3x3 layers whose shape is in the strip table run with the input strip resident in LDS."""
         return self._check_part(self._conv_launch(L, **kw), kw)
 
-    def _conv_launch(self, L, **kw):
+    def _conv_route(self, kw):
+        """Which kernel family runs a convolution, without side effects: (family, partial rows, fragment-order weights).
+        family: "strip" (fr_conv3x3_strip), "s2" (fr_conv3x3_s2_strip) or "igemm" (fr_conv_igemm)."""
         if (self.fr == FR_BF16 and self.use_strip and kw["KH"] == 3 and kw["stride"] == 1 and kw["RH"] == kw["SH"]):
             n = ops.strip_parts(kw["B"], kw["SC"], kw["N"], kw["SW"], kw.get("epi", 0))
             # (Round 5, measured and removed -- VERDICT r4 item 8, profiles/r05_hog_matrix.txt: the 256 -> 256 @14x14 launches as
@@ -528,31 +531,29 @@ class BackbonePlan(object):
             # the collectives back until the backward pass has left these layers, comm_gate below.)
             if n:
                 # Round 6: weights of the LDS-strip instances in MFMA-fragment order (FrConvArgs.w_frag): a weight load reads
-                # 1024 contiguous bytes instead of half of each of 16 lines (-5 ... -9 % per launch; FRHIP_W_FRAG=0: A/B)
-                if self._note_weight(kw["w"], self.w_frag and kw["SC"] % 64 == 0 and kw["N"] % 64 == 0 and bool(
-                        _lib.lib.fr_conv3x3_strip_takes_frag(kw["B"], kw["SC"], kw["N"], kw["SW"]))):
-                    kw = dict(kw, w_frag=1)
-                L.append(ops.conv_strip(self.stream, **kw))
-                self._last_conv_strips = n  # partial rows = strips, image-major
-                return n
+                # 1024 contiguous bytes instead of half of each of 16 lines (-5 ... -9 % per launch)
+                return "strip", n, self.w_frag and kw["SC"] % 64 == 0 and kw["N"] % 64 == 0 and bool(
+                    _lib.lib.fr_conv3x3_strip_takes_frag(kw["B"], kw["SC"], kw["N"], kw["SW"]))
+        mode = kw.get("mode", 0)
         if (self.fr == FR_BF16 and self.use_strip and self.use_s2 and kw["KH"] == 3 and kw["stride"] == 2 and
-                kw.get("mode", 0) in (0, 2)):
-            mode = kw.get("mode", 0)
-            n = ops.s2_strip_parts(kw["B"], kw["SC"], kw["N"], kw["RW"] if mode == 0 else kw["SW"], mode)
+                mode in (0, 2)):
+            wl = kw["RW"] if mode == 0 else kw["SW"]
+            n = ops.s2_strip_parts(kw["B"], kw["SC"], kw["N"], wl, mode)
             if n:
-                wl = kw["RW"] if mode == 0 else kw["SW"]
-                if self._note_weight(kw["w"], self.w_frag and bool(
-                        _lib.lib.fr_conv3x3_s2_strip_takes_frag(kw["B"], kw["SC"], wl, mode))):
-                    kw = dict(kw, w_frag=1)
-                L.append(ops.conv_s2_strip(self.stream, **kw))
-                self._last_conv_strips = n if mode == 0 else 0
-                return n
-        self._last_conv_strips = 0
-        self._note_weight(kw["w"], False)
-        L.append(ops.conv(self.stream, self.fr, **kw))
-        if kw.get("mode", 0) == 2:  # all four parity classes in one launch: [class][M tile] partial rows
-            return 4 * ((kw["B"] * (kw["RH"] // 2) * (kw["RW"] // 2) + 127) // 128)
-        return (kw["B"] * kw["RH"] * kw["RW"] + 127) // 128
+                return "s2", n, self.w_frag and bool(_lib.lib.fr_conv3x3_s2_strip_takes_frag(kw["B"], kw["SC"], wl, mode))
+        if mode == 2:  # all four parity classes in one launch: [class][M tile] partial rows
+            return "igemm", 4 * ((kw["B"] * (kw["RH"] // 2) * (kw["RW"] // 2) + 127) // 128), False
+        return "igemm", (kw["B"] * kw["RH"] * kw["RW"] + 127) // 128, False
+
+    def _conv_launch(self, L, **kw):
+        family, n, frag = self._conv_route(kw)
+        if self._note_weight(kw["w"], frag):
+            kw = dict(kw, w_frag=1)
+        make = {"strip": ops.conv_strip, "s2": ops.conv_s2_strip}.get(family)
+        L.append(make(self.stream, **kw) if make else ops.conv(self.stream, self.fr, **kw))
+        # partial rows that are strips, image-major (forward launches of the strip families), else 0
+        self._last_conv_strips = n if family == "strip" or (family == "s2" and kw.get("mode", 0) == 0) else 0
+        return n
 
     def _note_weight(self, w, frag):
         """Book-keeping of the weight layouts: a packed weight tensor has ONE layout, so every launch that reads it must agree.
@@ -568,11 +569,11 @@ class BackbonePlan(object):
         """Order the side stream behind everything enqueued on the main stream so far.  Round 6: the edge is the completion
         signal of the launch in front of it (ops.Launch.arm) where that is a launch of the main stream -- an event recorded
         behind it costs the main stream a marker packet its next kernel waits for: +5.1 us per edge against +1.6 (three edges
-        per residual unit; tools/edge_probe.hip, profiles/r06_edge_probe.txt).  FRHIP_EDGE_SIGNAL=0: A/B switch."""
+        per residual unit; tools/edge_probe.hip, profiles/r06_edge_probe.txt)."""
         if self.dual:
             ev = torch.cuda.Event()
             last = L[-1] if L else None
-            if (self.edge_signal and isinstance(last, ops.Launch) and last.tstream is None and last.stop_event is None):
+            if isinstance(last, ops.Launch) and last.tstream is None and last.stop_event is None:
                 ev.record(self.stream1_t)  # creates the hipEvent_t (torch allocates it at the first record)
                 last.arm(ev, self.stream)
             else:
@@ -587,7 +588,7 @@ class BackbonePlan(object):
             tiles = (kw["Cout"] // 64) * (kw["SC"] // 64)
             rows = {112: 2, 56: 4, 28: 7, 14: 14, 7: 7}[kw["SW"]]
             fills = kw["B"] * (kw["SW"] // rows) // (4 if kw["SW"] == 7 else 1)
-            groups = int(max(1, min(fills, self.wgrad_wgs // tiles if tiles <= self.wgrad_wgs else 1)))
+            groups = int(max(1, min(fills, _WGRAD_WGS // tiles if tiles <= _WGRAD_WGS else 1)))
             return self._slab_launch(L, dict(kw, nsplit=groups), groups * kw["Cout"] * 9 * kw["SC"], param=param)
         if (self.fr == FR_BF16 and self.use_strip and self.use_s2 and kw["KH"] == 3 and kw["stride"] == 2 and
                 kw["GW"] in (56, 28, 14, 7) and kw["SW"] == 2 * kw["GW"] and kw["Cout"] % 64 == 0 and kw["SC"] % 64 == 0):
@@ -595,7 +596,7 @@ class BackbonePlan(object):
             tiles = (kw["Cout"] // 64) * (kw["SC"] // 64)
             rows, nimg = {56: (2, 1), 28: (4, 1), 14: (7, 1), 7: (7, 2)}[kw["GW"]]
             fills = (kw["B"] * (kw["GW"] // rows) + nimg - 1) // nimg
-            groups = int(max(1, min(fills, self.wgrad_wgs // tiles if tiles <= self.wgrad_wgs else 1)))
+            groups = int(max(1, min(fills, _WGRAD_WGS // tiles if tiles <= _WGRAD_WGS else 1)))
             return self._slab_launch(L, dict(kw, nsplit=groups), groups * kw["Cout"] * 9 * kw["SC"], param=param)
         if kw.get("nsplit", 1) > 1:  # pixel slices go to slabs and are added in a fixed order (no float atomics)
             return self._slab_launch(L, kw, kw["nsplit"] * kw["Cout"] * kw["KH"] * kw["KW"] * kw["SC"], strip=False,
@@ -606,7 +607,7 @@ class BackbonePlan(object):
         return [param]
 
     def _slab_buffer(self, which, need):
-        """One of the two slab buffers, grown on demand (earlier launches are re-pointed at the new allocation)."""
+        """One of the three slab buffers, grown on demand (earlier launches are re-pointed at the new allocation)."""
         name, users = (("slab", self._slab_users), ("slab2", self._slab2_users), ("slab3", self._slab3_users))[which]
         buf = getattr(self, name)
         if buf is None or buf.numel() < need:
@@ -617,8 +618,8 @@ class BackbonePlan(object):
         return buf, users
 
     def _flush_pending(self, L):
-        """Sum the slabs a deferring launch left behind with a launch of its own (end of the list, or in front of a
-        launch that cannot fold them).  Returns the parameter whose gradient became final, or None."""
+        """Sum the slabs the last deferring launch left behind with a launch of its own (end of the list).  Returns the
+        parameter whose gradient became final, or None."""
         if self._pending is None:
             return None
         l0, groups, n, dw, param, which = self._pending
@@ -635,7 +636,7 @@ class BackbonePlan(object):
         [param] for a launch that sums its own slabs, the previous deferring launch's parameter for one that folds it,
         [] for the first deferring launch."""
         done = []
-        if strip and self.defer_slabs:
+        if strip:
             probe = ops._fill(_lib.FrWgradArgs(), **dict(kw, slab=self.part))
             if _lib.lib.fr_conv_wgrad_strip_defers(ctypes.byref(probe)):
                 which = self._slab_flip
@@ -658,14 +659,8 @@ class BackbonePlan(object):
         # A launch that sums its own slabs (1x1 shortcut weight gradients, shapes off the strip tables).  Rounds 3-5 first
         # flushed the slabs a deferring launch had left behind (fr_reduce_slabs: 34-53 us on the weight-gradient stream, three
         # times per IR-50 step) so that both could share buffer 0; with a buffer of its own the launch goes out at once and
-        # the deferred sum stays with the next deferring launch (FRHIP_WGRAD_SKIP_FLUSH=0: the old order).
-        if _switch("FRHIP_WGRAD_SKIP_FLUSH", 1) and self.defer_slabs:
-            buf, users = self._slab_buffer(2, need)
-        else:
-            flushed = self._flush_pending(L)  # keep the side stream's sums in order
-            if flushed is not None:
-                done.append(flushed)
-            buf, users = self._slab_buffer(0, need)
+        # the deferred sum stays with the next deferring launch.
+        buf, users = self._slab_buffer(2, need)
         kw = dict(kw, slab=buf)
         l = ops.wgrad_strip(self.stream2, **kw) if strip else ops.wgrad(self.stream2, self.fr, **kw)
         l.tstream = self.stream2_t
@@ -795,9 +790,8 @@ class BackbonePlan(object):
         x = self.z0
         # Round 6: the packing of the 3x3 weights (350 MB of traffic, 60 us) runs on the weight-gradient stream, idle in the
         # forward pass, beside the stem (im2col rows + two GEMM passes, HBM-bound but below the HBM rate on their own); the main
-        # stream waits for it in front of the first residual unit.  Training plans with two streams; FRHIP_PACK_SIDE=0: A/B
-        self.pack_side = (self.dual and not fold and not self.infer and not self.body_only and
-                          bool(_switch("FRHIP_PACK_SIDE", 1)))
+        # stream waits for it in front of the first residual unit.  Training plans with two streams
+        self.pack_side = self.dual and not fold and not self.infer and not self.body_only
         if self.pack_side:
             self._pack_ev0, self._pack_ev1 = torch.cuda.Event(), torch.cuda.Event()
             L.append(_EvWait(self.stream1_t, self._pack_ev1))
@@ -1092,14 +1086,14 @@ class BackbonePlan(object):
             if glw is not None:  # straight into the master's layout (one workgroup per element: the add is onto the zeroed arena)
                 # Round 6: on the weight-gradient stream, which has nothing to do until the last unit's data gradients exist
                 # (70 us of a 51-MB write that feeds nothing downstream, off a main stream that is a chain of 5-us launches
-                # here; FRHIP_LINEAR_WGRAD_SIDE=0: A/B switch)
-                side = self.dual and bool(_switch("FRHIP_LINEAR_WGRAD_SIDE", 1))
-                if side:
+                # here)
+                if self.dual:
                     self._side_after_main(L)
-                lw = ops.wgrad(self.stream2 if side else st, fr, g=gfT, src=self.a, dw=glw, B=B, GH=1, GW=1, Cout=512, SH=1,
-                               SW=1, SC=self.feat_in, KH=1, KW=1, stride=1, pad=0, ldg=512, lda=self.feat_in, pro=0, nsplit=1)
+                lw = ops.wgrad(self.stream2 if self.dual else st, fr, g=gfT, src=self.a, dw=glw, B=B, GH=1, GW=1, Cout=512,
+                               SH=1, SW=1, SC=self.feat_in, KH=1, KW=1, stride=1, pad=0, ldg=512, lda=self.feat_in, pro=0,
+                               nsplit=1)
                 L.append(lw)
-                if side:
+                if self.dual:
                     lw.tstream = self.stream2_t
                     head_done = torch.cuda.Event()
                     L.append(_EvRecord(head_done, self.stream2_t))
@@ -1136,216 +1130,31 @@ class BackbonePlan(object):
         self._build_backward_units(L, g_out, cur)
 
     def _build_backward_units(self, L, g_out, cur):
-        B, st, fr = self.B, self.stream, self.fr
         # ---- residual units in reverse
         unit_done = {}  # unit index -> event recorded on the side stream after its weight gradients
         sums_left = 0  # rows of BN2-backward sums the previous launch left in self.part (0: none)
+        self._unit0_apply = None
         for i in range(len(self.units) - 1, -1, -1):
             u, d = self.units[i], self.ubuf[i]
             x = self.ubuf[i - 1]["out"] if i > 0 else self.z0
-            rin, rout = B * u.H * u.H, B * u.Ho * u.Ho
-            HWo = u.Ho * u.Ho
-            bn1, bn2 = d["bn1"], d["bn2"]
             par = i % self.nset if self.dual else 0
-            g_y2 = self.g_y2s[par][:rout * u.depth]
-            if self.dual:
-                # unit i + nset's weight gradients read this buffer set
-                if i + self.nset in unit_done:
-                    L.append(_EvWait(self.stream1_t, unit_done[i + self.nset]))
+            if self.dual and i + self.nset in unit_done:  # unit i + nset's weight gradients read this buffer set
+                L.append(_EvWait(self.stream1_t, unit_done[i + self.nset]))
             # (Round 4, schedule experiments measured and removed again -- profiles/r04_ab_edges.txt, r04_ab_edge2_wgrad_order.txt:
             # ONE main -> side edge per unit with both weight gradients behind it: +0.26 ms (the first weight gradient then
             # starts a data gradient later); the main stream waiting for the side stream every second unit with four buffer
             # sets: +0.05; no second edge in front of conv1's weight gradient: nothing; conv1's weight gradient before
             # conv2's: +0.39 ms.  Round 5, 128-workgroup weight gradients: conv2's weight gradient launched BEFORE its data
             # gradient -- it needs g_y2 and y1 only --: +0.3 ms at bs 256, +0.9 ms IR-SE-101 bs 128, bit-identical.)
-            S = S2 = L
-
-            def edge():
-                self._side_after_main(L)
-            nb = ops.grid_blocks(rout, u.depth, fr)
             ready = [u.bn2.weight, u.bn2.bias]
-            se_kw = {}
-            if u.se is not None:
-                R = u.se.fc1.out_channels
-                g1, g2 = self.grad_of(u.se.fc1.weight), self.grad_of(u.se.fc2.weight)
-                if g1 is None:
-                    g1 = self.se_scratch[0, :R * u.depth]
-                if g2 is None:
-                    g2 = self.se_scratch[1, :R * u.depth]
-                # gradient wrt the excite scale (a pass over g and y2) + the MLP backward of the same image in one launch.
-                # Round 5: with fewer images than CUs the squeeze runs over row slices of an image in 256-thread workgroups
-                # (IR-SE-101 + CosFace(28000), bs 128: 17.57 against 17.66-17.81 ms per step; at bs 256 -- pSp -- the one
-                # 1024-thread workgroup per image is the faster one: 16.05 against 16.17; profiles/r05_ab_se_slices.txt).
-                # (Round 4, measured and removed: the same pass also leaving the per-image sums BN2's backward needs, so that
-                # fr_bn_bwd_reduce disappears from the IR-SE units -- IR-SE-101 + CosFace(28000), bs 128: 19.50-19.52 against
-                # 19.22-19.30 ms per step; pSp bs 256: 17.31 against 17.22; profiles/r04_ab_se_sums.txt: the pass it deleted ran
-                # beside the weight gradients of the side stream, the extra work sat in a 128-workgroup launch.)
-                # Round 6: the weight gradients of the two 1x1 convolutions of the MLP (one launch, 6-13 us, 4 workgroups) feed
-                # nothing downstream: with two streams they run on the weight-gradient stream behind conv2's data gradient
-                # (IR-SE-101 bs 128: 49 launches off a main stream whose channel-wise chain is longer than its convolutions)
-                se_side = self.dual and bool(_switch("FRHIP_SE_WGRAD_SIDE", 1))
-                # Round 6: the squeeze pass also takes the per-image sums from which BN2's backward sums follow (the gate and
-                # its gradient are constant over an image): fr_bn_bwd_reduce -- a third pass over (g, y2) behind the MLP,
-                # 14-19 us per unit on the main stream's chain -- is gone (bf16 path; FRHIP_SE_BN_SUMS=0: A/B switch)
-                se_sums = (fr == FR_BF16 and bool(_switch("FRHIP_SE_BN_SUMS", 1)) and u.depth % 8 == 0 and
-                           (u.depth // 8) <= 256 and 256 % (u.depth // 8) == 0)
-                if se_sums:
-                    L.append(ops.call("fr_se_gscale_mlp_bwd_sums", g_out, d["y2"], bn2.scale, bn2.shift, bn2.mean, bn2.invstd,
-                                      d["s"], d["hidden"], u.se.fc1.weight, u.se.fc2.weight, d["gpooled"], d["gz"], d["gh"],
-                                      self.se_gs_part, self.part, B, u.depth, R, HWo, fr, st))
-                    if not se_side:
-                        L.append(ops.call("fr_se_mlp_wgrad", d["gz"], d["gh"], d["hidden"], d["pooled"], g1, g2, B, u.depth,
-                                          R, st))
-                else:
-                    L.append(ops.call("fr_se_gscale_mlp_bwd", g_out, d["y2"], bn2.scale, bn2.shift, d["s"], d["hidden"],
-                                      d["pooled"], u.se.fc1.weight, u.se.fc2.weight, d["gpooled"], None if se_side else g1,
-                                      None if se_side else g2, d["gz"], d["gh"], self.se_gs_part if B <= 160 else None, B,
-                                      u.depth, R, HWo, fr, st))
-                se_wgrad = None
-                if se_side:
-                    se_wgrad = ops.call("fr_se_mlp_wgrad", d["gz"], d["gh"], d["hidden"], d["pooled"], g1, g2, B, u.depth, R,
-                                        self.stream2)
-                    se_wgrad.tstream = self.stream2_t
-                se_kw = dict(se=d["s"], gse=d["gpooled"])
-                ready += [u.se.fc1.weight, u.se.fc2.weight]
-            db, dg = self._bn_grads(bn2)
-            common = dict(g=g_out, x=d["y2"], mean=bn2.mean, invstd=bn2.invstd, rows=rout, C=u.depth,
-                          rows_per_image=HWo, nblocks=nb, **se_kw)
-            if u.se is not None and se_sums:
-                self._reduce(L, B, 2, u.depth, db, dg)  # one row pair per image, left by fr_se_gscale_mlp_bwd_sums
-            elif sums_left:
-                self._reduce(L, sums_left, 2, u.depth, db, dg)  # left by the launch that formed g_out (nx below)
-            else:
-                L.append(ops.bn_bwd_reduce(st, fr, part=self.part, **common))
-                self._reduce(L, nb, 3, u.depth, db, dg)
-            s0, s1 = self._s01(bn2, db, dg)
-            L.append(ops.bn_bwd_apply(st, fr, gx=g_y2, gamma=u.bn2.weight, s0=s0, s1=s1, inv_count=1.0 / rout, **common))
-            g_xS = None
-            if u.sc_conv is not None:
-                bnS = d["bnS"]
-                g_yS = self.g_ySs[par][:rout * u.depth]
-                db, dg = self._bn_grads(bnS)
-                common = dict(g=g_out, x=d["yS"], mean=bnS.mean, invstd=bnS.invstd, rows=rout, C=u.depth,
-                              rows_per_image=HWo, nblocks=nb)
-                L.append(ops.bn_bwd_reduce(st, fr, part=self.part, **common))
-                self._reduce(L, nb, 3, u.depth, db, dg)
-                s0, s1 = self._s01(bnS, db, dg)
-                L.append(ops.bn_bwd_apply(st, fr, gx=g_yS, gamma=u.sc_bn.weight, s0=s0, s1=s1,
-                                          inv_count=1.0 / rout, **common))
-                # 1x1 stride-s data gradient = dense GEMM on the Ho x Ho grid; it lands on the pixels (s*i, s*j) of
-                # the unit input, which the final bn_bwd_apply adds as a strided scatter (add_kind 2)
-                g_xS = self.g_xS[:rout * u.cin]
-                kws = dict(src=g_yS, w=d["wtS"], out=g_xS, B=B, RH=u.Ho, RW=u.Ho, SH=u.Ho, SW=u.Ho, SC=u.depth, N=u.cin, KH=1,
-                           KW=1, stride=1, pad=0, mode=0, lda=u.depth, ldc=u.cin, pro=0, epi=ops.EPI_STORE)
-                if self._c1_parts(B, u.Ho, u.depth, u.cin, 1, u.Ho):
-                    L.append(ops.conv1x1_stream(st, **kws))
-                else:
-                    L.append(ops.conv(st, fr, **kws))
-                gws = self.grad_of(u.sc_conv.weight)
-                if gws is not None:
-                    tiles = ((u.depth + 127) // 128) * ((u.cin + 127) // 128)
-                    edge()
-                    ready += self._wgrad(S, param=u.sc_conv.weight, g=g_yS, src=x, dw=gws, B=B, GH=u.Ho, GW=u.Ho,
-                                         Cout=u.depth, SH=u.H, SW=u.H, SC=u.cin, KH=1, KW=1, stride=u.stride, pad=0,
-                                         ldg=u.depth, lda=u.cin, pro=0, nsplit=_wgrad_slices(rout, tiles))
-                else:
-                    ready.append(u.sc_conv.weight)  # frozen: never reported anyway (on_ready filters requires_grad)
-                ready += [u.sc_bn.weight, u.sc_bn.bias]
-            # conv2: data gradient with the PReLU backward epilogue, then the weight gradient
-            g_y1 = self.g_y1s[par][:rin * u.depth]
-            c2 = dict(src=g_y2, w=d["wt2"], out=g_y1, B=B, RH=u.H, RW=u.H, SH=u.Ho, SW=u.Ho, SC=u.depth, N=u.depth,
-                      KH=3, KW=3, stride=u.stride, pad=1, lda=u.depth, ldc=u.depth, ldaux=u.depth, pro=0,
-                      epi=ops.EPI_PRELU_BWD, aux=d["y1"], epi_a=u.prelu.weight)
-            # The PReLU-slope partial sums of this data gradient feed nothing downstream (a parameter gradient): with the
-            # side stream they go to a buffer of their own (one per buffer set) and are added there, off the main chain.
-            gsl = self.grad_of(u.prelu.weight)
-            gsl = gsl if gsl is not None else self.sums[2, :u.depth]
-            if self.side_slope and self.part_slope[par] is None:  # this unit's own rows: [<= 4 classes x strips][2][depth] floats
-                probe = []
-                rows = self._conv_launch(probe, mode=2 if (u.stride == 2 and u.H % 2 == 0) else 1, par_h=-1, par_w=-1,
-                                         part=self.part, **c2)
-                self.part_slope[par] = torch.zeros(rows * 2 * u.depth + 4096, device=self.device)
-            part2 = self.part_slope[par] if self.side_slope else self.part
-            if u.stride == 2 and u.H % 2 == 0:
-                # one launch per output-pixel parity class: 9/4 taps per pixel instead of 9 (3/4 of them misses)
-                # (all four classes in one launch: par = -1; partial rows come back as [class][M tile])
-                mt = self._conv(L, mode=2, par_h=-1, par_w=-1, part=part2, **c2)
-            else:
-                mt = self._conv(L, mode=1, part=part2, **c2)
-            gw2 = self.grad_of(u.conv2.weight)
-            if self.side_slope:
-                edge()  # g_y1 / the slope partials, g_y2 (BN2 backward) and y1 are final
-                r = ops.call("fr_reduce_parts", part2, mt, 2, u.depth, gsl, None, None, self.stream2)
-                r.tstream = self.stream2_t
-                S2.append(r)
-                if u.se is not None and se_wgrad is not None:
-                    S2.append(se_wgrad)
-            else:
-                self._reduce(L, mt, 2, u.depth, gsl, None)
-            if gw2 is not None:
-                tiles = ((u.depth + 127) // 128) ** 2 * 9
-                if not self.side_slope:
-                    edge()
-                kw2 = dict(param=u.conv2.weight, g=g_y2, src=d["y1"], dw=gw2, B=B, GH=u.Ho, GW=u.Ho,
-                           Cout=u.depth, SH=u.H, SW=u.H, SC=u.depth, KH=3, KW=3, stride=u.stride, pad=1,
-                           ldg=u.depth, lda=u.depth, pro=ops.PRO_PRELU, pro_a=u.prelu.weight,
-                           nsplit=_wgrad_slices(rout, tiles))
-                ready += self._wgrad(S2, **kw2)
-            else:
-                ready.append(u.conv2.weight)
-            # conv1: data gradient with the BN1-backward sums epilogue, then the weight gradient
-            g_xh = self.g_xh[:rin * u.cin]
-            db, dg = self._bn_grads(bn1)
-            mt = self._conv(L, src=g_y1, w=d["wt1"], out=g_xh, B=B, RH=u.H, RW=u.H, SH=u.H, SW=u.H,
-                            SC=u.depth, N=u.cin, KH=3, KW=3, stride=1, pad=1, mode=1, lda=u.depth, ldc=u.cin,
-                            ldaux=u.cin, pro=0, epi=ops.EPI_BNBWD, aux=x, epi_a=bn1.mean, epi_b=bn1.invstd,
-                            part=self.part)
-            self._reduce(L, mt, 2, u.cin, db, dg)
-            gw1 = self.grad_of(u.conv1.weight)
-            if gw1 is not None:
-                tiles = ((u.depth + 127) // 128) * ((u.cin + 127) // 128) * 9
-                edge()  # g_y1 (conv2 data gradient) is final on the main stream
-                ready += self._wgrad(S, param=u.conv1.weight, g=g_y1, src=x, dw=gw1, B=B, GH=u.H, GW=u.H, Cout=u.depth,
-                                     SH=u.H, SW=u.H, SC=u.cin, KH=3, KW=3, stride=1, pad=1, ldg=u.depth, lda=u.cin,
-                                     pro=ops.PRO_BN, pro_a=bn1.scale, pro_b=bn1.shift, nsplit=_wgrad_slices(rin, tiles))
-            else:
-                ready.append(u.conv1.weight)
-            ready += [u.prelu.weight, u.bn1.weight, u.bn1.bias]
-            # unit input gradient = BN1 backward of g_xh + shortcut gradient
-            nxt = 1 - cur
-            g_x = self.g_pp[nxt][:rin * u.cin]
-            s0, s1 = self._s01(bn1, db, dg)
-            kw = dict(g=g_xh, x=x, gx=g_x, mean=bn1.mean, invstd=bn1.invstd, gamma=u.bn1.weight, s0=s0, s1=s1,
-                      rows=rin, inv_count=1.0 / rin, C=u.cin, rows_per_image=u.H * u.H,
-                      nblocks=ops.grid_blocks(rin, u.cin, fr))
-            if u.sc_conv is not None:
-                kw.update(add=g_xS, add_kind=2, H=u.H, W=u.H, add_stride=u.stride)
-            elif u.stride == 1:
-                kw.update(add=g_out, add_kind=1)
-            else:
-                kw.update(add=g_out, add_kind=2, H=u.H, W=u.H, add_stride=u.stride)
-            # Round 6: the first unit's input gradient is read by exactly one kernel, the stem's backward sums, and both are
-            # HBM-bound passes over 3.2 M rows x 64 channels: fr_stem_bwd_sums_from forms it on the way (bit-identical gx and
-            # sums, 411 MB less traffic at batch 256; FRHIP_STEM_FROM_UNIT=0: the two launches)
-            self._unit0_apply = None
-            if (i == 0 and not self.body_only and self.stem_recompute and fr == FR_BF16 and u.cin == 64 and
-                    self.M0 < (1 << 24) and self.bn0.mod.training and _switch("FRHIP_STEM_FROM_UNIT", 1)):
-                # ... and x, the unit's input, is the stem's own output: recomputed from the rows instead of read (x = NULL)
-                kw0 = dict(kw, x=None) if (x is self.z0 and _switch("FRHIP_STEM_RECOMPUTE_X", 1)) else kw
-                self._unit0_apply = ops._fill(_lib.FrBnBwdArgs(), **kw0)
-                self._unit0_apply_keep = kw0
-            else:
-                # Round 6: where the unit in front has no gate and the tensor only streams through HBM, this launch also takes
-                # the sums BN2's backward of that unit needs (FrBnBwdArgs.nx) -- fr_bn_bwd_reduce, a pass over (g_x, y2) right
-                # behind this one, is gone there.  FRHIP_BN_NEXT_MB: smallest tensor (MB) it is done for, 0 = never
-                sums_left = 0
-                lim = _switch("FRHIP_BN_NEXT_MB", 20)
-                if (i > 0 and fr == FR_BF16 and lim > 0 and self.units[i - 1].se is None and
-                        rin * u.cin * 2 >= lim << 20):
-                    pb = self.ubuf[i - 1]
-                    kw.update(nx=pb["y2"], nmean=pb["bn2"].mean, ninvstd=pb["bn2"].invstd, npart=self.part)
-                    sums_left = kw["nblocks"]
-                L.append(ops.bn_bwd_apply(st, fr, **kw))
+            g_y2 = self.g_y2s[par][:self.B * u.Ho * u.Ho * u.depth]
+            se_wgrad = self._bwd_bn2(L, u, d, g_out, g_y2, sums_left, ready)
+            g_xS = self._bwd_shortcut(L, u, d, g_out, x, par, ready) if u.sc_conv is not None else None
+            g_y1 = self._bwd_conv2(L, u, d, g_y2, par, se_wgrad, ready)
+            g_xh, db, dg = self._bwd_conv1(L, u, d, g_y1, x, ready)
+            cur = 1 - cur
+            g_x = self.g_pp[cur][:self.B * u.H * u.H * u.cin]
+            sums_left = self._bwd_bn1(L, i, g_xh, g_x, x, g_out, g_xS, db, dg)
             done = None
             if self.dual:
                 done = torch.cuda.Event()
@@ -1354,7 +1163,7 @@ class BackbonePlan(object):
             self.ready_marks.append((len(L), ready, done))
             if u.Ho < _switch("FRHIP_DP_GATE_HO", 28):  # 14x14 / 7x7 layers: one workgroup per compute unit and launch (see comm_gate below)
                 self._gate_end = len(L)
-            g_out, cur = g_x, nxt
+            g_out = g_x
         # the slabs of the last deferring weight-gradient launch are summed by a launch of their own
         flushed = self._flush_pending(L)
         tail_ready = [flushed] if flushed is not None else []
@@ -1366,12 +1175,216 @@ class BackbonePlan(object):
             self.g_input = g_out
             if tail_ready:
                 self.ready_marks.append((len(L), tail_ready, unit_done.get(-1)))
-            self._order_ready_marks()
-            if self.dual and unit_done:
-                L.append(_EvWait(self.stream1_t, unit_done[min(unit_done)]))  # join: the side stream is FIFO
-            self.bwd_list = L
-            return
-        # ---- stem: z0 = PReLU(BN0(y0)); y0 = X0 * W0p^T
+        else:
+            self._build_backward_stem(L, g_out, unit_done)
+        if self.dual and unit_done:
+            L.append(_EvWait(self.stream1_t, unit_done[min(unit_done)]))  # join: the side stream is FIFO
+        if not self.body_only:
+            sc, sb, sp = self.stem
+            self.ready_marks.append((len(L), [sb.weight, sb.bias, sp.weight, sc.weight] + tail_ready, None))
+        self._order_ready_marks()
+        self.bwd_list = L
+
+    def _bwd_bn2(self, L, u, d, g_out, g_y2, sums_left, ready):
+        """SE backward and BN2 backward: g_y2 = dL/dy2.  sums_left: rows of BN2-backward sums the launch that formed g_out
+        left in self.part (0: none).  Returns the SE weight-gradient launch left for the side stream, or None."""
+        B, fr, st, rout, HWo = self.B, self.fr, self.stream, self.B * u.Ho * u.Ho, u.Ho * u.Ho
+        bn2 = d["bn2"]
+        se_kw, se_wgrad, se_sums = {}, None, False
+        if u.se is not None:
+            R = u.se.fc1.out_channels
+            g1, g2 = self.grad_of(u.se.fc1.weight), self.grad_of(u.se.fc2.weight)
+            if g1 is None:
+                g1 = self.se_scratch[0, :R * u.depth]
+            if g2 is None:
+                g2 = self.se_scratch[1, :R * u.depth]
+            # gradient wrt the excite scale (a pass over g and y2) + the MLP backward of the same image in one launch.
+            # Round 5: with fewer images than CUs the squeeze runs over row slices of an image in 256-thread workgroups
+            # (IR-SE-101 + CosFace(28000), bs 128: 17.57 against 17.66-17.81 ms per step; at bs 256 -- pSp -- the one
+            # 1024-thread workgroup per image is the faster one: 16.05 against 16.17; profiles/r05_ab_se_slices.txt).
+            # (Round 4, measured and removed: the same pass also leaving the per-image sums BN2's backward needs, so that
+            # fr_bn_bwd_reduce disappears from the IR-SE units -- IR-SE-101 + CosFace(28000), bs 128: 19.50-19.52 against
+            # 19.22-19.30 ms per step; pSp bs 256: 17.31 against 17.22; profiles/r04_ab_se_sums.txt: the pass it deleted ran
+            # beside the weight gradients of the side stream, the extra work sat in a 128-workgroup launch.)
+            # Round 6: the weight gradients of the two 1x1 convolutions of the MLP (one launch, 6-13 us, 4 workgroups) feed
+            # nothing downstream: with two streams they run on the weight-gradient stream behind conv2's data gradient
+            # (IR-SE-101 bs 128: 49 launches off a main stream whose channel-wise chain is longer than its convolutions)
+            # Round 6: the squeeze pass also takes the per-image sums from which BN2's backward sums follow (the gate and
+            # its gradient are constant over an image): fr_bn_bwd_reduce -- a third pass over (g, y2) behind the MLP,
+            # 14-19 us per unit on the main stream's chain -- is gone (bf16 path)
+            se_sums = fr == FR_BF16 and u.depth % 8 == 0 and (u.depth // 8) <= 256 and 256 % (u.depth // 8) == 0
+            if se_sums:
+                L.append(ops.call("fr_se_gscale_mlp_bwd_sums", g_out, d["y2"], bn2.scale, bn2.shift, bn2.mean, bn2.invstd,
+                                  d["s"], d["hidden"], u.se.fc1.weight, u.se.fc2.weight, d["gpooled"], d["gz"], d["gh"],
+                                  self.se_gs_part, self.part, B, u.depth, R, HWo, fr, st))
+                if not self.dual:
+                    L.append(ops.call("fr_se_mlp_wgrad", d["gz"], d["gh"], d["hidden"], d["pooled"], g1, g2, B, u.depth, R, st))
+            else:
+                L.append(ops.call("fr_se_gscale_mlp_bwd", g_out, d["y2"], bn2.scale, bn2.shift, d["s"], d["hidden"],
+                                  d["pooled"], u.se.fc1.weight, u.se.fc2.weight, d["gpooled"], None if self.dual else g1,
+                                  None if self.dual else g2, d["gz"], d["gh"], self.se_gs_part if B <= 160 else None, B,
+                                  u.depth, R, HWo, fr, st))
+            if self.dual:
+                se_wgrad = ops.call("fr_se_mlp_wgrad", d["gz"], d["gh"], d["hidden"], d["pooled"], g1, g2, B, u.depth, R,
+                                    self.stream2)
+                se_wgrad.tstream = self.stream2_t
+            se_kw = dict(se=d["s"], gse=d["gpooled"])
+            ready += [u.se.fc1.weight, u.se.fc2.weight]
+        nb = ops.grid_blocks(rout, u.depth, fr)
+        db, dg = self._bn_grads(bn2)
+        common = dict(g=g_out, x=d["y2"], mean=bn2.mean, invstd=bn2.invstd, rows=rout, C=u.depth,
+                      rows_per_image=HWo, nblocks=nb, **se_kw)
+        if se_sums:
+            self._reduce(L, B, 2, u.depth, db, dg)  # one row pair per image, left by fr_se_gscale_mlp_bwd_sums
+        elif sums_left:
+            self._reduce(L, sums_left, 2, u.depth, db, dg)  # left by the launch that formed g_out (nx, _bwd_bn1)
+        else:
+            L.append(ops.bn_bwd_reduce(st, fr, part=self.part, **common))
+            self._reduce(L, nb, 3, u.depth, db, dg)
+        s0, s1 = self._s01(bn2, db, dg)
+        L.append(ops.bn_bwd_apply(st, fr, gx=g_y2, gamma=u.bn2.weight, s0=s0, s1=s1, inv_count=1.0 / rout,
+                                  **common))
+        return se_wgrad
+
+    def _bwd_shortcut(self, L, u, d, g_out, x, par, ready):
+        """Backward of the shortcut's BN and 1x1 convolution.  Returns the shortcut's share of the unit input gradient."""
+        B, fr, st, rout = self.B, self.fr, self.stream, self.B * u.Ho * u.Ho
+        bnS = d["bnS"]
+        g_yS = self.g_ySs[par][:rout * u.depth]
+        db, dg = self._bn_grads(bnS)
+        common = dict(g=g_out, x=d["yS"], mean=bnS.mean, invstd=bnS.invstd, rows=rout, C=u.depth,
+                      rows_per_image=u.Ho * u.Ho, nblocks=ops.grid_blocks(rout, u.depth, fr))
+        L.append(ops.bn_bwd_reduce(st, fr, part=self.part, **common))
+        self._reduce(L, common["nblocks"], 3, u.depth, db, dg)
+        s0, s1 = self._s01(bnS, db, dg)
+        L.append(ops.bn_bwd_apply(st, fr, gx=g_yS, gamma=u.sc_bn.weight, s0=s0, s1=s1, inv_count=1.0 / rout, **common))
+        # 1x1 stride-s data gradient = dense GEMM on the Ho x Ho grid; it lands on the pixels (s*i, s*j) of
+        # the unit input, which the final bn_bwd_apply adds as a strided scatter (add_kind 2)
+        g_xS = self.g_xS[:rout * u.cin]
+        kws = dict(src=g_yS, w=d["wtS"], out=g_xS, B=B, RH=u.Ho, RW=u.Ho, SH=u.Ho, SW=u.Ho, SC=u.depth, N=u.cin, KH=1,
+                   KW=1, stride=1, pad=0, mode=0, lda=u.depth, ldc=u.cin, pro=0, epi=ops.EPI_STORE)
+        if self._c1_parts(B, u.Ho, u.depth, u.cin, 1, u.Ho):
+            L.append(ops.conv1x1_stream(st, **kws))
+        else:
+            L.append(ops.conv(st, fr, **kws))
+        gws = self.grad_of(u.sc_conv.weight)
+        if gws is not None:
+            tiles = ((u.depth + 127) // 128) * ((u.cin + 127) // 128)
+            self._side_after_main(L)
+            ready += self._wgrad(L, param=u.sc_conv.weight, g=g_yS, src=x, dw=gws, B=B, GH=u.Ho, GW=u.Ho,
+                                 Cout=u.depth, SH=u.H, SW=u.H, SC=u.cin, KH=1, KW=1, stride=u.stride, pad=0,
+                                 ldg=u.depth, lda=u.cin, pro=0, nsplit=_wgrad_slices(rout, tiles))
+        else:
+            ready.append(u.sc_conv.weight)  # frozen: never reported anyway (on_ready filters requires_grad)
+        ready += [u.sc_bn.weight, u.sc_bn.bias]
+        return g_xS
+
+    def _bwd_conv2(self, L, u, d, g_y2, par, se_wgrad, ready):
+        """conv2: data gradient with the PReLU backward epilogue, then the weight gradient.  Returns g_y1 = dL/dy1."""
+        B, rin, rout = self.B, self.B * u.H * u.H, self.B * u.Ho * u.Ho
+        g_y1 = self.g_y1s[par][:rin * u.depth]
+        c2 = dict(src=g_y2, w=d["wt2"], out=g_y1, B=B, RH=u.H, RW=u.H, SH=u.Ho, SW=u.Ho, SC=u.depth, N=u.depth,
+                  KH=3, KW=3, stride=u.stride, pad=1, lda=u.depth, ldc=u.depth, ldaux=u.depth, pro=0,
+                  epi=ops.EPI_PRELU_BWD, aux=d["y1"], epi_a=u.prelu.weight)
+        if u.stride == 2 and u.H % 2 == 0:
+            # one launch per output-pixel parity class: 9/4 taps per pixel instead of 9 (3/4 of them misses)
+            # (all four classes in one launch: par = -1; partial rows come back as [class][M tile])
+            c2.update(mode=2, par_h=-1, par_w=-1)
+        else:
+            c2.update(mode=1)
+        # The PReLU-slope partial sums of this data gradient feed nothing downstream (a parameter gradient): with the
+        # side stream they go to a buffer of their own (one per buffer set) and are added there, off the main chain.
+        gsl = self.grad_of(u.prelu.weight)
+        gsl = gsl if gsl is not None else self.sums[2, :u.depth]
+        if self.side_slope and self.part_slope[par] is None:  # this unit's own rows: [<= 4 classes x strips][2][depth] floats
+            rows = self._conv_route(c2)[1]
+            self.part_slope[par] = torch.zeros(rows * 2 * u.depth + 4096, device=self.device)
+        mt = self._conv(L, part=self.part_slope[par] if self.side_slope else self.part, **c2)
+        if self.side_slope:
+            self._side_after_main(L)  # g_y1 / the slope partials, g_y2 (BN2 backward) and y1 are final
+            r = ops.call("fr_reduce_parts", self.part_slope[par], mt, 2, u.depth, gsl, None, None, self.stream2)
+            r.tstream = self.stream2_t
+            L.append(r)
+            if se_wgrad is not None:
+                L.append(se_wgrad)
+        else:
+            self._reduce(L, mt, 2, u.depth, gsl, None)
+        gw2 = self.grad_of(u.conv2.weight)
+        if gw2 is not None:
+            tiles = ((u.depth + 127) // 128) ** 2 * 9
+            if not self.side_slope:
+                self._side_after_main(L)
+            ready += self._wgrad(L, param=u.conv2.weight, g=g_y2, src=d["y1"], dw=gw2, B=B, GH=u.Ho, GW=u.Ho,
+                                 Cout=u.depth, SH=u.H, SW=u.H, SC=u.depth, KH=3, KW=3, stride=u.stride, pad=1,
+                                 ldg=u.depth, lda=u.depth, pro=ops.PRO_PRELU, pro_a=u.prelu.weight,
+                                 nsplit=_wgrad_slices(rout, tiles))
+        else:
+            ready.append(u.conv2.weight)
+        return g_y1
+
+    def _bwd_conv1(self, L, u, d, g_y1, x, ready):
+        """conv1: data gradient with the BN1-backward sums epilogue, then the weight gradient.  Returns (g_xh = dL/d BN1(x),
+        BN1's dbeta and dgamma targets, which hold the backward sums)."""
+        B, rin = self.B, self.B * u.H * u.H
+        bn1 = d["bn1"]
+        g_xh = self.g_xh[:rin * u.cin]
+        db, dg = self._bn_grads(bn1)
+        mt = self._conv(L, src=g_y1, w=d["wt1"], out=g_xh, B=B, RH=u.H, RW=u.H, SH=u.H, SW=u.H,
+                        SC=u.depth, N=u.cin, KH=3, KW=3, stride=1, pad=1, mode=1, lda=u.depth, ldc=u.cin,
+                        ldaux=u.cin, pro=0, epi=ops.EPI_BNBWD, aux=x, epi_a=bn1.mean, epi_b=bn1.invstd,
+                        part=self.part)
+        self._reduce(L, mt, 2, u.cin, db, dg)
+        gw1 = self.grad_of(u.conv1.weight)
+        if gw1 is not None:
+            tiles = ((u.depth + 127) // 128) * ((u.cin + 127) // 128) * 9
+            self._side_after_main(L)  # g_y1 (conv2 data gradient) is final on the main stream
+            ready += self._wgrad(L, param=u.conv1.weight, g=g_y1, src=x, dw=gw1, B=B, GH=u.H, GW=u.H, Cout=u.depth,
+                                 SH=u.H, SW=u.H, SC=u.cin, KH=3, KW=3, stride=1, pad=1, ldg=u.depth, lda=u.cin,
+                                 pro=ops.PRO_BN, pro_a=bn1.scale, pro_b=bn1.shift, nsplit=_wgrad_slices(rin, tiles))
+        else:
+            ready.append(u.conv1.weight)
+        ready += [u.prelu.weight, u.bn1.weight, u.bn1.bias]
+        return g_xh, db, dg
+
+    def _bwd_bn1(self, L, i, g_xh, g_x, x, g_out, g_xS, db, dg):
+        """Unit input gradient g_x = BN1 backward of g_xh + the shortcut's gradient.  Returns the rows of BN2-backward sums
+        of unit i - 1 this launch leaves in self.part (0: none)."""
+        u, bn1, fr = self.units[i], self.ubuf[i]["bn1"], self.fr
+        rin = self.B * u.H * u.H
+        s0, s1 = self._s01(bn1, db, dg)
+        kw = dict(g=g_xh, x=x, gx=g_x, mean=bn1.mean, invstd=bn1.invstd, gamma=u.bn1.weight, s0=s0, s1=s1,
+                  rows=rin, inv_count=1.0 / rin, C=u.cin, rows_per_image=u.H * u.H,
+                  nblocks=ops.grid_blocks(rin, u.cin, fr))
+        if u.sc_conv is not None:
+            kw.update(add=g_xS, add_kind=2, H=u.H, W=u.H, add_stride=u.stride)
+        elif u.stride == 1:
+            kw.update(add=g_out, add_kind=1)
+        else:
+            kw.update(add=g_out, add_kind=2, H=u.H, W=u.H, add_stride=u.stride)
+        # Round 6: the first unit's input gradient is read by exactly one kernel, the stem's backward sums, and both are
+        # HBM-bound passes over 3.2 M rows x 64 channels: fr_stem_bwd_sums_from forms it on the way (bit-identical gx and
+        # sums, 411 MB less traffic at batch 256)
+        if (i == 0 and not self.body_only and self.stem_recompute and fr == FR_BF16 and u.cin == 64 and
+                self.M0 < (1 << 24) and self.bn0.mod.training):
+            # ... and x, the unit's input, is the stem's own output: recomputed from the rows instead of read (x = NULL)
+            kw0 = dict(kw, x=None)
+            self._unit0_apply = ops._fill(_lib.FrBnBwdArgs(), **kw0)
+            self._unit0_apply_keep = kw0
+            return 0
+        # Round 6: where the unit in front has no gate and the tensor only streams through HBM, this launch also takes
+        # the sums BN2's backward of that unit needs (FrBnBwdArgs.nx) -- fr_bn_bwd_reduce, a pass over (g_x, y2) right
+        # behind this one, is gone there (tensors of _BN_NEXT_MB and more)
+        sums_left = 0
+        if i > 0 and fr == FR_BF16 and self.units[i - 1].se is None and rin * u.cin * 2 >= _BN_NEXT_MB << 20:
+            pb = self.ubuf[i - 1]
+            kw.update(nx=pb["y2"], nmean=pb["bn2"].mean, ninvstd=pb["bn2"].invstd, npart=self.part)
+            sums_left = kw["nblocks"]
+        L.append(ops.bn_bwd_apply(self.stream, fr, **kw))
+        return sums_left
+
+    def _build_backward_stem(self, L, g_out, unit_done):
+        """Stem backward: z0 = PReLU(BN0(y0)); y0 = X0 * W0p^T.  g_out = dL/dz0."""
+        fr, st = self.fr, self.stream
         sc, sb, sp = self.stem
         nb = ops.grid_blocks(self.M0, 64, fr)
         db, dg = self._bn_grads(self.bn0)
@@ -1381,62 +1394,48 @@ class BackbonePlan(object):
                       nblocks=nb)
         if self.stem_recompute:  # the sums of fr_bn_bwd_reduce over (g, y0) with y0 recomputed from the rows
             nb = int(min(2048, (self.M0 + 63) // 64))
-            if getattr(self, "_unit0_apply", None) is not None:
+            if self._unit0_apply is not None:
                 L.append(ops.call("fr_stem_bwd_sums_from", self._unit0_apply, self.X0, self.W0p, self.bn0.mean,
                                   self.bn0.invstd, self.bn0.scale, self.bn0.shift, sp.weight, self.part, self.M0, self.K0,
                                   nb, st))
             else:
                 L.append(ops.call("fr_stem_bwd_sums", self.X0, self.W0p, g_out, self.bn0.mean, self.bn0.invstd,
                                   self.bn0.scale, self.bn0.shift, sp.weight, self.part, self.M0, self.K0, nb, st))
-            self._reduce(L, nb, 3, 64, db, dg, gsl if gsl is not None else self.sums[2, :64])
         else:
             L.append(ops.bn_bwd_reduce(st, fr, part=self.part, **common))
-            self._reduce(L, nb, 3, 64, db, dg, gsl if gsl is not None else self.sums[2, :64])
+        self._reduce(L, nb, 3, 64, db, dg, gsl if gsl is not None else self.sums[2, :64])
         s0, s1 = self._s01(self.bn0, db, dg)
         gw0 = self.grad_of(sc.weight)
-        fuse = self.use_stem_gemm  # BN0 / PReLU backward applied while the weight gradient stages its rows
-        g_y0 = None
-        if gw0 is not None and not fuse:  # the materialised stem-output gradient (fp32 path)
+        if gw0 is None:
+            return
+        if self.use_stem_gemm:
+            # BN0 backward is applied while the gradient rows are staged: g_y0 is never materialised
+            nsl = int(min(1024 if self.K0 == 32 else 512, (self.M0 + 63) // 64))  # partials live in self.part
+            if self.stem_recompute:
+                L.append(ops.call("fr_stem_wgrad_bn_r", g_out, self.X0, self.W0p, self.bn0.mean, self.bn0.invstd,
+                                  self.bn0.scale, self.bn0.shift, sp.weight, sb.weight, s0, s1, 1.0 / self.M0,
+                                  self.part, self.M0, self.K0, nsl, st))
+            else:
+                L.append(ops.call("fr_stem_wgrad_bn", g_out, self.y0, self.X0, self.bn0.mean, self.bn0.invstd,
+                                  self.bn0.scale, self.bn0.shift, sp.weight, sb.weight, s0, s1, 1.0 / self.M0,
+                                  self.part, self.M0, self.K0, nsl, st))
+            L.append(ops.call("fr_reduce_parts", self.part, nsl, 1, 64 * self.K0, self.gW0p, None, None, st))
+        else:  # the materialised stem-output gradient (fp32 path)
             if self.per_unit_sets:
                 g_y0 = self._act(self.M0 * 64, 1).view(-1)
             else:
                 g_y0 = self.g_y1s[1 if self.dual else 0][:self.M0 * 64]  # unit 0's wgrads (side stream) still read set 0
                 if self.dual and 1 in unit_done:
                     L.append(_EvWait(self.stream1_t, unit_done[1]))  # set 1 was last read by unit 1's weight gradients
-        if gw0 is not None and not fuse:
-            L.append(ops.bn_bwd_apply(st, fr, gx=g_y0, gamma=sb.weight, s0=s0, s1=s1, inv_count=1.0 / self.M0,
-                                      **common))
-        if gw0 is not None:
-            if self.use_stem_gemm and not fuse:
-                nsl = int(min(1024 if self.K0 == 32 else 512, (self.M0 + 63) // 64))
-                L.append(ops.call("fr_stem_wgrad", g_y0, self.X0, self.part, self.M0, self.K0, nsl, st))
-                L.append(ops.call("fr_reduce_parts", self.part, nsl, 1, 64 * self.K0, self.gW0p, None, None, st))
-            elif fuse:
-                # BN0 backward is applied while the gradient rows are staged: g_y0 is never materialised
-                nsl = int(min(1024 if self.K0 == 32 else 512, (self.M0 + 63) // 64))  # partials live in self.part
-                if self.stem_recompute:
-                    L.append(ops.call("fr_stem_wgrad_bn_r", g_out, self.X0, self.W0p, self.bn0.mean, self.bn0.invstd,
-                                      self.bn0.scale, self.bn0.shift, sp.weight, sb.weight, s0, s1, 1.0 / self.M0,
-                                      self.part, self.M0, self.K0, nsl, st))
-                else:
-                    L.append(ops.call("fr_stem_wgrad_bn", g_out, self.y0, self.X0, self.bn0.mean, self.bn0.invstd,
-                                      self.bn0.scale, self.bn0.shift, sp.weight, sb.weight, s0, s1, 1.0 / self.M0,
-                                      self.part, self.M0, self.K0, nsl, st))
-                L.append(ops.call("fr_reduce_parts", self.part, nsl, 1, 64 * self.K0, self.gW0p, None, None, st))
-            else:
-                nsl = int(min(_wgrad_slices(self.M0, 1), self.part.numel() // (64 * self.K0)))
-                if nsl == 1:  # a single slice adds onto the buffer: clear it first
-                    L.append(ops.call("fr_fill_rows", self.gW0p, None, 64, self.K0, st))
-                L.append(ops.wgrad(st, fr, g=g_y0, src=self.X0, dw=self.gW0p, B=self.M0, GH=1, GW=1, Cout=64, SH=1,
-                                   SW=1, SC=self.K0, KH=1, KW=1, stride=1, pad=0, ldg=64, lda=self.K0, pro=0,
-                                   nsplit=nsl, slab=self.part if nsl > 1 else None))
-            L.append(ops.call("fr_unpack_stem_grad", self.gW0p, gw0, gw0.stride(0), gw0.stride(1), gw0.stride(2),
-                              gw0.stride(3), 64, sc.weight.shape[1], self.K0, st))
-        if self.dual and unit_done:
-            L.append(_EvWait(self.stream1_t, unit_done[min(unit_done)]))  # join: the side stream is FIFO
-        self.ready_marks.append((len(L), [sb.weight, sb.bias, sp.weight, sc.weight] + tail_ready, None))
-        self._order_ready_marks()
-        self.bwd_list = L
+            L.append(ops.bn_bwd_apply(st, fr, gx=g_y0, gamma=sb.weight, s0=s0, s1=s1, inv_count=1.0 / self.M0, **common))
+            nsl = int(min(_wgrad_slices(self.M0, 1), self.part.numel() // (64 * self.K0)))
+            if nsl == 1:  # a single slice adds onto the buffer: clear it first
+                L.append(ops.call("fr_fill_rows", self.gW0p, None, 64, self.K0, st))
+            L.append(ops.wgrad(st, fr, g=g_y0, src=self.X0, dw=self.gW0p, B=self.M0, GH=1, GW=1, Cout=64, SH=1,
+                               SW=1, SC=self.K0, KH=1, KW=1, stride=1, pad=0, ldg=64, lda=self.K0, pro=0,
+                               nsplit=nsl, slab=self.part if nsl > 1 else None))
+        L.append(ops.call("fr_unpack_stem_grad", self.gW0p, gw0, gw0.stride(0), gw0.stride(1), gw0.stride(2),
+                          gw0.stride(3), 64, sc.weight.shape[1], self.K0, st))
 
     def _order_ready_marks(self):
         """Announce gradients in ARENA order (data-parallel buckets are contiguous arena slices that complete front to

@@ -16,8 +16,8 @@ from .engine import _side_stream
 
 
 def _head_side_stream(dev):
-    """The device's weight-gradient stream (engine.py: one per device), or None: FRHIP_HEAD_SIDE=0 / FRHIP_SINGLE_STREAM=1."""
-    if os.environ.get("FRHIP_HEAD_SIDE", "1") == "0" or os.environ.get("FRHIP_SINGLE_STREAM", "0") != "0":
+    """The device's weight-gradient stream (engine.py: one per device), or None: FRHIP_SINGLE_STREAM=1."""
+    if os.environ.get("FRHIP_SINGLE_STREAM", "0") != "0":
         return None
     return _side_stream(dev, 1)
 

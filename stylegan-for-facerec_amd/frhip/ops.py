@@ -68,8 +68,10 @@ class Launch(object):
     def __call__(self):
         if self.stop_event is not None:
             lib.fr_arm_stop_event(self.stop_handle)
-            rc = self.fn(*self.args)
-            n = lib.fr_finish_stop_event(self.stop_stream)  # records the ordinary way unless exactly one kernel took the event
+            try:
+                rc = self.fn(*self.args)
+            finally:  # disarms the event even when the call raises
+                n = lib.fr_finish_stop_event(self.stop_stream)  # records the ordinary way unless exactly one kernel took the event
             if n < 0:
                 _lib.check(n, "fr_finish_stop_event")
         else:
@@ -177,7 +179,7 @@ def set_option(name, value):
 
 # Switches the LIBRARY reads (kernel-family A/B switches and test hooks; README "Switches").  The library caches a switch at
 # its first use, so the environment is pushed again whenever a plan is built (and by tests that flip one in-process).
-LIB_SWITCHES = {"FRHIP_ROLL64": 1, "FRHIP_WGRAD_ROLL": 1, "FRHIP_WGRAD_DEFER": 1, "FRHIP_SPLIT_STRIPS": 0, "FRHIP_XCD_ORDER": 1,
+LIB_SWITCHES = {"FRHIP_ROLL64": 1, "FRHIP_WGRAD_ROLL": 1, "FRHIP_SPLIT_STRIPS": 0, "FRHIP_XCD_ORDER": 1,
                 "FRHIP_IGEMM_BN": 0, "FRHIP_ROLL_NSEG": -1, "FRHIP_S2ROLL_NSEG": -1}
 
 
