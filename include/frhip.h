@@ -506,6 +506,36 @@ int fr_margin_bwd(const float* g, const int64_t* label, const float* cos_t, void
 /* backward through F.normalize: gx = (G - xhat*(xhat.G)) * inv, xhat = x*inv, rows of D */
 int fr_normalize_bwd(const float* G, const float* x, const float* inv, float* gx, int rows, int D, void* stream);
 
+/* ---- SphereFace / Am_softmax heads (head/metrics.py:200-277, :280-333), fp32.  The cosines come raw from fr_conv_igemm
+ *      (FR_EPI_STORE, out_f32) in [rows][ld] (ld a multiple of 4 >= N); the margin is applied by these row kernels, and the
+ *      backward pass reads the same raw cosines for its clamp mask.  kind 2 = SphereFace, 3 = Am_softmax; any other kind
+ *      returns FR_UNSUPPORTED.  c = clamp(cos, -1, 1) (NaN passes), lab = label[m]:
+ *   kind 2 (:236-268): out = ||x_m|| * (n == lab ? (phi - c) / p0 + c : c), phi = (-1)^k T_mi(c) - 2k,
+ *                      k = floor(mi * acos(c) / 3.14159265) in fp32, T_mi the Chebyshev polynomial of mlambda (:227-234),
+ *                      mi in 0..5, p0 = 1 + lambda, ||x_m|| = 1 / inv_x[m] of fr_row_normalize
+ *   kind 3 (:310-331): out = p1 * (n == lab ? c - p0 : c), p0 = m, p1 = s (inv_x unused)
+ * Columns N..ld of out are written as 0. */
+int fr_margin_apply(const float* cos, const int64_t* label, const float* inv_x, float* out, int rows, int N, int ld,
+                    int kind, int mi, float p0, float p1, void* stream);
+/* gcos[m][n] = g[m][n] * d out / d cos, 0 where the clamp saturated (the closed interval passes, as torch.clamp does) and
+ * in the padding columns N..ldg (the layout of fr_margin_bwd).  g is [rows][N] contiguous.  kind 2 also writes
+ * r_part[m][p] = sum over the p-th column chunk of g * out / ||x_m||, p < fr_margin_apply_parts(ldg) (NULL for kind 3). */
+int fr_margin_apply_bwd(const float* g, const float* cos, const int64_t* label, const float* inv_x, float* gcos,
+                        float* r_part, int rows, int N, int ld, int ldg, int kind, int mi, float p0, float p1, void* stream);
+/* number of column chunks of fr_margin_apply_bwd: r_part has [rows][fr_margin_apply_parts(ldg)] entries */
+int fr_margin_apply_parts(int ldg);
+/* fr_normalize_bwd plus the radial term of SphereFace's row scale ||x|| (torch.norm(input, 2, 1), :255,268):
+ * gx = (G - xhat*(xhat.G)) * inv + r * xhat, r = r_part[m][0] + ... + r_part[m][nparts-1] in that order */
+int fr_normalize_bwd_radial(const float* G, const float* x, const float* inv, const float* r_part, int nparts, float* gx,
+                            int rows, int D, void* stream);
+/* Am_softmax's l2_norm(kernel, axis=0) (:280-284, no eps: a zero column gives inf / NaN as in the reference) of
+ * K [D][N]: kt [D][Np] = K / ||K[:, j]|| (columns N..Np zero), kn [Np][D] = kt^T (the GEMM's B operand, rows N..Np zero),
+ * inv [N] = 1 / ||K[:, j]|| */
+int fr_col_normalize(const float* K, float* kn, float* kt, float* inv, int D, int N, int Np, void* stream);
+/* backward of fr_col_normalize: gK[d][j] = (GW[j][d] - kn[j][d] * (kn[j].GW[j])) * inv[j], GW [>= N][D] (the weight
+ * gradient GEMM's rows), gK in K's [D][N] layout */
+int fr_col_normalize_bwd(const float* GW, const float* kn, const float* inv, float* gK, int D, int N, void* stream);
+
 /* ---- focal loss on the batch-mean cross entropy (loss/focal.py:17-21) + top-k (util/utils.py:343-358) */
 /* per row: lse[m], ce[m] = lse - z[label], rank[m] = #{n: z[n] > z[label]} */
 int fr_ce_rows(const float* logits, const int64_t* label, float* lse, float* ce, int32_t* rank, int rows, int N,

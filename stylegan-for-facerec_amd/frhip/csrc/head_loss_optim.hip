@@ -3,6 +3,8 @@
 // Reference arithmetic replaced (paths under /root/reference):
 //   F.normalize(x), F.normalize(W) (eps 1e-12) + their autograd      head/metrics.py:103, :167
 //   d phi / d cos of the ArcFace / CosFace margin, label select       head/metrics.py:115-138, :181-189
+//   SphereFace margin (clamp, k, Chebyshev phi, lambda blend, *||x||)  head/metrics.py:236-268
+//   Am_softmax l2_norm(kernel, axis=0), clamp, label margin, *s         head/metrics.py:280-284, :302-331
 //   FocalLoss on mean CE                                              loss/focal.py:17-21
 //   accuracy top-1/5                                                  util/utils.py:343-358
 //   optim.SGD(momentum, coupled weight decay on group 0)              train.py:196, :313-316
@@ -92,6 +94,176 @@ __global__ void margin_bwd_kernel(const float* __restrict__ g, const long long* 
     float v = 0.f;
     if (n < N) v = scale * g[(size_t)m * N + n] * (n == lab ? dphi : 1.f);
     Elt<T>::st(gcos + (size_t)m * ldg + n, v);
+  }
+}
+
+// ------------------------------------------------------------------------------------------ SphereFace / Am_softmax
+// Margin on the raw cosines the GEMM stored (FR_EPI_STORE): the GEMM epilogue, shared with the backbone, stays as it is,
+// and the saved raw cosines give the backward pass its clamp mask.  Block = 4 waves = 4 rows, one f32x4 per lane, 1024
+// columns per block (blockIdx.x); ld and ldg are multiples of 4.
+constexpr int MARGIN_COLS = 1024;
+
+// torch.clamp(c, -1, 1): NaN passes through (fminf / fmaxf would turn it into a bound)
+__device__ __forceinline__ float clamp1(float c) { return c > 1.f ? 1.f : (c < -1.f ? -1.f : c); }
+
+// SphereFace on the label column (head/metrics.py:227-268): phi = (-1)^k T_m(c) - 2k, k = floor(m acos(c) / 3.14159265)
+// in fp32, detached; returns (phi - c) / div + c and d/dc of it
+__device__ __forceinline__ float sphere_label(float c, int mi, float div, float* dout) {
+  const float c2 = c * c;
+  float t, dt;
+  switch (mi) {
+    case 0: t = 1.f; dt = 0.f; break;
+    case 1: t = c; dt = 1.f; break;
+    case 2: t = 2.f * c2 - 1.f; dt = 4.f * c; break;
+    case 3: t = 4.f * c2 * c - 3.f * c; dt = 12.f * c2 - 3.f; break;
+    case 4: t = 8.f * (c2 * c2) - 8.f * c2 + 1.f; dt = 32.f * c2 * c - 16.f * c; break;
+    default: t = 16.f * (c2 * c2 * c) - 20.f * (c2 * c) + 5.f * c; dt = 80.f * (c2 * c2) - 60.f * c2 + 5.f; break;
+  }
+  const float k = floorf((float)mi * acosf(c) / 3.14159265f);
+  const float sg = ((int)k & 1) ? -1.f : 1.f;
+  const float phi = sg * t - 2.f * k;
+  *dout = 1.f + (sg * dt - 1.f) / div;
+  return (phi - c) / div + c;
+}
+
+// kind 2: out = nrm * (label ? sphere : c), nrm = ||x_m|| (p0 = 1 + lambda);  kind 3: out = p1 * (label ? c - p0 : c)
+__global__ __launch_bounds__(256) void margin_apply_kernel(const float* __restrict__ cos, const long long* __restrict__ label,
+                                                           const float* __restrict__ inv_x, float* __restrict__ out,
+                                                           int rows, int N, int ld, int kind, int mi, float p0, float p1) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const long long lab = label[row];
+  const float scale = kind == 2 ? 1.f / inv_x[row] : p1;
+  const int end = min(ld, (int)(blockIdx.x + 1) * MARGIN_COLS);
+  for (int n = blockIdx.x * MARGIN_COLS + lane * 4; n < end; n += 256) {
+    const f32x4 ch = *reinterpret_cast<const f32x4*>(cos + (size_t)row * ld + n);
+    f32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float c = clamp1(ch[j]);
+      float v = c;
+      if (n + j == lab) {
+        float unused;
+        v = kind == 2 ? sphere_label(c, mi, p0, &unused) : c - p0;
+      }
+      o[j] = n + j < N ? v * scale : 0.f;
+    }
+    *reinterpret_cast<f32x4*>(out + (size_t)row * ld + n) = o;
+  }
+}
+
+// gcos = g * d out / d cos, 0 where the clamp saturated (torch.clamp passes gradient on the closed interval) and in the
+// padding columns [N, ldg).  kind 2 also leaves r_part[row][blockIdx.x] = sum over the block's columns of g * out / nrm.
+__global__ __launch_bounds__(256) void margin_apply_bwd_kernel(const float* __restrict__ g, const float* __restrict__ cos,
+                                                               const long long* __restrict__ label,
+                                                               const float* __restrict__ inv_x, float* __restrict__ gcos,
+                                                               float* __restrict__ r_part, int rows, int N, int ld, int ldg,
+                                                               int kind, int mi, float p0, float p1) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const long long lab = label[row];
+  const float scale = kind == 2 ? 1.f / inv_x[row] : p1;
+  const int end = min(ldg, (int)(blockIdx.x + 1) * MARGIN_COLS);
+  float r = 0.f;
+  for (int n = blockIdx.x * MARGIN_COLS + lane * 4; n < end; n += 256) {
+    f32x4 ch = {0.f, 0.f, 0.f, 0.f};
+    if (n < ld) ch = *reinterpret_cast<const f32x4*>(cos + (size_t)row * ld + n);
+    f32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float v = 0.f;
+      if (n + j < N) {
+        const float gg = g[(size_t)row * N + n + j];
+        const float c = clamp1(ch[j]);
+        const bool pass = ch[j] >= -1.f && ch[j] <= 1.f;
+        float a = c, d = 1.f;
+        if (kind == 2 && n + j == lab) a = sphere_label(c, mi, p0, &d);
+        if (kind == 2) r = fmaf(gg, a, r);
+        v = pass ? gg * scale * d : 0.f;
+      }
+      o[j] = v;
+    }
+    *reinterpret_cast<f32x4*>(gcos + (size_t)row * ldg + n) = o;
+  }
+  if (kind == 2) {
+    r = wave_sum(r);
+    if (lane == 0) r_part[(size_t)row * gridDim.x + blockIdx.x] = r;
+  }
+}
+
+// normalise backward plus the radial term of a row scale ||x|| (SphereFace's NormOfFeature, head/metrics.py:255,268):
+// gx = (G - xh (xh . G)) inv + r xh, r = the row's r_part added in order
+__global__ void normalize_bwd_radial_kernel(const float* __restrict__ G, const float* __restrict__ x,
+                                            const float* __restrict__ inv, const float* __restrict__ r_part, int nparts,
+                                            float* __restrict__ gx, int rows, int D) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const float iv = inv[row];
+  float r = 0.f;
+  for (int p = 0; p < nparts; ++p) r += r_part[(size_t)row * nparts + p];
+  float dot = 0.f;
+  for (int d = lane; d < D; d += 64) dot = fmaf(x[(size_t)row * D + d] * iv, G[(size_t)row * D + d], dot);
+  dot = wave_sum(dot);
+  for (int d = lane; d < D; d += 64) {
+    const float xh = x[(size_t)row * D + d] * iv;
+    gx[(size_t)row * D + d] = (G[(size_t)row * D + d] - xh * dot) * iv + r * xh;
+  }
+}
+
+// Am_softmax's l2_norm(kernel, axis=0) (head/metrics.py:280-284, no eps): kt[d][j] = K[d][j] / ||K[:, j]|| in the [D][Np]
+// layout of K (columns N..Np zero), inv[j] = 1 / ||K[:, j]||.  Block = 64 columns x 4 slices of D, slices added in order.
+__global__ __launch_bounds__(256) void col_normalize_kernel(const float* __restrict__ K, float* __restrict__ kt,
+                                                            float* __restrict__ inv, int D, int N, int Np) {
+  __shared__ float part[4][64];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int j = blockIdx.x * 64 + tx;
+  float ss = 0.f;
+  if (j < N)
+    for (int d = ty; d < D; d += 4) {
+      const float v = K[(size_t)d * N + j];
+      ss = fmaf(v, v, ss);
+    }
+  part[ty][tx] = ss;
+  __syncthreads();
+  if (j >= Np) return;
+  const float nrm = sqrtf(part[0][tx] + part[1][tx] + part[2][tx] + part[3][tx]);
+  if (j < N && ty == 0) inv[j] = 1.f / nrm;
+  for (int d = ty; d < D; d += 4) kt[(size_t)d * Np + j] = j < N ? K[(size_t)d * N + j] / nrm : 0.f;
+}
+
+// gK[d][j] = (GW[j][d] - kn[j][d] (kn[j] . GW[j])) inv[j]: the backward of the column normalisation, written back in K's
+// [D][N] layout through 64 x 64 LDS tiles.  Block = 64 columns.
+__global__ __launch_bounds__(256) void col_normalize_bwd_kernel(const float* __restrict__ GW, const float* __restrict__ kn,
+                                                                const float* __restrict__ inv, float* __restrict__ gK,
+                                                                int D, int N) {
+  __shared__ float dot[64];
+  __shared__ float tile[64][65];
+  const int j0 = blockIdx.x * 64, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  for (int q = 0; q < 16; ++q) {
+    const int j = j0 + w * 16 + q;
+    float s = 0.f;
+    if (j < N)
+      for (int d = lane; d < D; d += 64) s = fmaf(kn[(size_t)j * D + d], GW[(size_t)j * D + d], s);
+    s = wave_sum(s);
+    if (lane == 0) dot[w * 16 + q] = s;
+  }
+  __syncthreads();
+  for (int d0 = 0; d0 < D; d0 += 64) {
+    for (int jj = w; jj < 64; jj += 4) {
+      const int j = j0 + jj, d = d0 + lane;
+      float v = 0.f;
+      if (j < N && d < D) v = (GW[(size_t)j * D + d] - kn[(size_t)j * D + d] * dot[jj]) * inv[j];
+      tile[jj][lane] = v;
+    }
+    __syncthreads();
+    for (int dd = w; dd < 64; dd += 4) {
+      const int d = d0 + dd, j = j0 + lane;
+      if (d < D && j < N) gK[(size_t)d * N + j] = tile[lane][dd];
+    }
+    __syncthreads();
   }
 }
 
@@ -370,6 +542,57 @@ extern "C" int fr_margin_bwd(const float* g, const int64_t* label, const float* 
                        (bf16_t*)gcos, rows, N, ldg, kind, easy, cos_m, sin_m, th, scale);
   else
     FR_UNSUPPORTED("fr_margin_bwd: dtype");
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_margin_apply_parts(int ldg) { return (ldg + MARGIN_COLS - 1) / MARGIN_COLS; }
+
+extern "C" int fr_margin_apply(const float* cos, const int64_t* label, const float* inv_x, float* out, int rows, int N,
+                               int ld, int kind, int mi, float p0, float p1, void* stream) {
+  if (kind != 2 && kind != 3) FR_UNSUPPORTED("fr_margin_apply: kind 2 (SphereFace) or 3 (Am_softmax)");
+  if (kind == 2 && (mi < 0 || mi > 5)) FR_UNSUPPORTED("fr_margin_apply: SphereFace m in 0..5");
+  if (rows <= 0 || N <= 0 || ld < N || ld % 4) FR_UNSUPPORTED("fr_margin_apply: shape (ld >= N, multiple of 4)");
+  hipLaunchKernelGGL(margin_apply_kernel, dim3(fr_margin_apply_parts(ld), (rows + 3) / 4), dim3(256), 0,
+                     (hipStream_t)stream, cos, (const long long*)label, inv_x, out, rows, N, ld, kind, mi, p0, p1);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_margin_apply_bwd(const float* g, const float* cos, const int64_t* label, const float* inv_x, float* gcos,
+                                   float* r_part, int rows, int N, int ld, int ldg, int kind, int mi, float p0, float p1,
+                                   void* stream) {
+  if (kind != 2 && kind != 3) FR_UNSUPPORTED("fr_margin_apply_bwd: kind 2 (SphereFace) or 3 (Am_softmax)");
+  if (kind == 2 && (mi < 0 || mi > 5)) FR_UNSUPPORTED("fr_margin_apply_bwd: SphereFace m in 0..5");
+  if (rows <= 0 || N <= 0 || ld < N || ld % 4 || ldg < ld || ldg % 4)
+    FR_UNSUPPORTED("fr_margin_apply_bwd: shape (ldg >= ld >= N, multiples of 4)");
+  hipLaunchKernelGGL(margin_apply_bwd_kernel, dim3(fr_margin_apply_parts(ldg), (rows + 3) / 4), dim3(256), 0,
+                     (hipStream_t)stream, g, cos, (const long long*)label, inv_x, gcos, r_part, rows, N, ld, ldg, kind, mi,
+                     p0, p1);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_normalize_bwd_radial(const float* G, const float* x, const float* inv, const float* r_part, int nparts,
+                                       float* gx, int rows, int D, void* stream) {
+  if (rows <= 0 || nparts <= 0) FR_UNSUPPORTED("fr_normalize_bwd_radial: empty");
+  hipLaunchKernelGGL(normalize_bwd_radial_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, G, x, inv,
+                     r_part, nparts, gx, rows, D);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_col_normalize(const float* K, float* kn, float* kt, float* inv, int D, int N, int Np, void* stream) {
+  if (D <= 0 || N <= 0 || Np < N) FR_UNSUPPORTED("fr_col_normalize: shape (Np >= N)");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(col_normalize_kernel, dim3((Np + 63) / 64), dim3(256), 0, st, K, kt, inv, D, N, Np);
+  // kn [Np][D] = kt^T: the GEMM's B operand, rows >= N zero
+  hipLaunchKernelGGL(transpose_rows_kernel<float>, dim3((Np + 63) / 64, (D + 63) / 64), dim3(256), 0, st,
+                     (const float*)kt, kn, D, Np, D);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_col_normalize_bwd(const float* GW, const float* kn, const float* inv, float* gK, int D, int N,
+                                    void* stream) {
+  if (D <= 0 || N <= 0) FR_UNSUPPORTED("fr_col_normalize_bwd: empty");
+  hipLaunchKernelGGL(col_normalize_bwd_kernel, dim3((N + 63) / 64), dim3(256), 0, (hipStream_t)stream, GW, kn, inv, gK,
+                     D, N);
   FR_LAUNCH_CHECK();
 }
 

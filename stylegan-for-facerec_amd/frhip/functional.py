@@ -138,17 +138,142 @@ class MarginHeadFn(torch.autograd.Function):
         return gx, gw, None, None, None, None, None
 
 
+SPHEREFACE, AM_SOFTMAX = 2, 3  # margin kinds of fr_margin_apply
+
+
+def margin_ext_forward(x, weight, label, kind, mi, p0, p1):
+    """SphereFace (kind 2: ``weight`` [N, D], mi = m, p0 = 1 + lambda) or Am_softmax (kind 3: ``weight`` is the [D, N]
+    kernel, p0 = m, p1 = s) logits for fp32 device tensors.  The GEMM stores the raw cosines; fr_margin_apply turns them
+    into logits, and the backward pass reads them again for its clamp mask.  Returns (logits, saved, cfg)."""
+    B, D = x.shape
+    N = weight.shape[0] if kind == SPHEREFACE else weight.shape[1]
+    dev = x.device
+    st = ops.current_stream_ptr()
+    x = x.contiguous().float()
+    w = weight.contiguous().float()
+    label = label.contiguous().long()
+    Np = _pad(N, 32)
+    wn = torch.empty(Np, D, device=dev)  # GEMM B operand, rows >= N zero
+    wt = torch.empty(D, Np, device=dev)  # its transpose, the B operand of the data gradient
+    inv_w = torch.empty(N, device=dev)
+    if kind == SPHEREFACE:
+        xn = torch.empty(B, D, device=dev)
+        inv_x = torch.empty(B, device=dev)
+        ops.call("fr_row_normalize", x, xn, None, inv_x, B, B, D, 0, FR_F32, st)()
+        ops.call("fr_row_normalize", w, wn, wt, inv_w, N, Np, D, Np, FR_F32, st)()
+    else:  # the embeddings are not normalised (head/metrics.py:302-304)
+        xn, inv_x = x, None
+        ops.call("fr_col_normalize", w, wn, wt, inv_w, D, N, Np, st)()
+    ld = _pad(N, 4)
+    cos = torch.empty(B, ld, device=dev)
+    ops.conv(st, FR_F32, src=xn, w=wn, out=cos, B=B, RH=1, RW=1, SH=1, SW=1, SC=D, N=N, KH=1, KW=1, stride=1, pad=0,
+             mode=0, lda=D, ldc=ld, pro=0, epi=ops.EPI_STORE, out_f32=1)()
+    store = torch.empty(B, ld, device=dev)
+    ops.call("fr_margin_apply", cos, label, inv_x, store, B, N, ld, kind, int(mi), float(p0), float(p1), st)()
+    logits = store if ld == N else store[:, :N]
+    saved = (x, w, label, xn, wn, wt, inv_x, inv_w, cos)
+    cfg = (kind, int(mi), float(p0), float(p1), Np, ld)
+    return logits, saved, cfg
+
+
+def margin_ext_backward(saved, cfg, g, need_x, need_w):
+    """(gx, gweight) of ``margin_ext_forward``; gweight has the weight's own layout ([D, N] for Am_softmax)."""
+    x, w, label, xn, wn, wt, inv_x, inv_w, cos = saved
+    kind, mi, p0, p1, Np, ld = cfg
+    B, D = x.shape
+    N = w.shape[0] if kind == SPHEREFACE else w.shape[1]
+    dev = x.device
+    st = ops.current_stream_ptr()
+    g = g.contiguous().float()
+    gcos = torch.empty(B, Np, device=dev)
+    nparts = int(ops.lib.fr_margin_apply_parts(Np))
+    r_part = torch.empty(B, nparts, device=dev) if kind == SPHEREFACE else None
+    ops.call("fr_margin_apply_bwd", g, cos, label, inv_x, gcos, r_part, B, N, ld, Np, kind, mi, p0, p1, st)()
+    N4 = _pad(N, 4)  # the weight-gradient GEMM wants 16-byte channel counts; gcos columns >= N are zero
+
+    def weight_grad(stream, GW):
+        ops.wgrad(stream, FR_F32, g=gcos, src=xn, dw=GW, B=B, GH=1, GW=1, Cout=N4, SH=1, SW=1, SC=D, KH=1, KW=1,
+                  stride=1, pad=0, ldg=Np, lda=D, pro=0, nsplit=1)()
+        gw = torch.empty_like(w)
+        if kind == SPHEREFACE:
+            ops.call("fr_normalize_bwd", GW, w, inv_w, gw, N, D, stream)()
+        else:
+            ops.call("fr_col_normalize_bwd", GW, wn, inv_w, gw, D, N, stream)()
+        return gw
+
+    gx = gw = None
+    # the weight's half on the weight-gradient stream, as margin_backward does
+    side = _head_side_stream(dev) if (need_x and need_w) else None
+    if side is not None:
+        main = torch.cuda.current_stream(dev)
+        GW = torch.empty(N4, D, device=dev)
+        side.wait_stream(main)
+        sp = ops.stream_ptr(side)
+        ops.call("fr_fill_rows", GW, None, N4, D, sp)()
+        gw = weight_grad(sp, GW)
+        need_w = False
+    if need_x:
+        Gx = torch.empty(B, D, device=dev)
+        nk = Np // 32
+        splitk = max(1, min(nk, 64, nk // 8))
+        slab = torch.empty(splitk, B, D, device=dev)  # K slices to slabs, added in a fixed order (reproducible)
+        ops.conv(st, FR_F32, src=gcos, w=wt, out=slab, B=B, RH=1, RW=1, SH=1, SW=1, SC=Np, N=D, KH=1, KW=1,
+                 stride=1, pad=0, mode=0, lda=Np, ldc=D, pro=0, epi=ops.EPI_SLAB, out_f32=1, splitk=splitk)()
+        if kind == SPHEREFACE:
+            ops.call("fr_reduce_parts", slab, splitk, 1, B * D, Gx, None, None, st)()
+            gx = torch.empty(B, D, device=dev)
+            ops.call("fr_normalize_bwd_radial", Gx, x, inv_x, r_part, nparts, gx, B, D, st)()
+        else:
+            gx = Gx
+            ops.call("fr_reduce_parts", slab, splitk, 1, B * D, gx, None, None, st)()
+    if need_w:
+        gw = weight_grad(st, torch.zeros(N4, D, device=dev))
+    if side is not None:
+        main.wait_stream(side)
+    return gx, gw
+
+
+class MarginExtHeadFn(torch.autograd.Function):
+    """SphereFace (head/metrics.py:236-268) and Am_softmax (:302-331) on the HIP path; see ``margin_ext_forward``."""
+
+    @staticmethod
+    def forward(ctx, x, weight, label, kind, mi, p0, p1):
+        logits, saved, cfg = margin_ext_forward(x, weight, label, kind, mi, p0, p1)
+        ctx.save_for_backward(*saved)
+        ctx.cfg = cfg
+        ctx.mark_non_differentiable(label)
+        return logits
+
+    @staticmethod
+    def backward(ctx, g):
+        gx, gw = margin_ext_backward(ctx.saved_tensors, ctx.cfg, g, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return gx, gw, None, None, None, None, None
+
+
 CHECK_LABELS = True  # host-side range check of the labels (one device sync per call); loops with validated data clear it
+
+
+def _check_labels(label, n):
+    if CHECK_LABELS and (label.min() < 0 or label.max() >= n):  # reference: RuntimeError from scatter_ (metrics.py:134)
+        raise RuntimeError("index %d is out of bounds for dimension 1 with size %d" % (int(label.max()), n))
 
 
 def margin_head(x, weight, label, kind, s, m, easy_margin=False):
     if x.shape[0] == 0:  # the reference returns empty logits (F.linear / scatter_ on zero rows); nothing to launch
         ops.ptr(x)  # host tensors still fail loudly
         return x.new_zeros((0, weight.shape[0]), dtype=torch.float32) + 0.0 * (x.sum() + weight.sum())
-    if CHECK_LABELS and (label.min() < 0 or label.max() >= weight.shape[0]):  # reference: RuntimeError from scatter_ (metrics.py:134)
-        raise RuntimeError("index %d is out of bounds for dimension 1 with size %d"
-                           % (int(label.max()), weight.shape[0]))
+    _check_labels(label, weight.shape[0])
     return MarginHeadFn.apply(x, weight, label, kind, s, m, easy_margin)
+
+
+def margin_ext_head(x, weight, label, kind, mi, p0, p1):
+    """SphereFace (kind 2) / Am_softmax (kind 3) logits; the empty batch and label check of ``margin_head``."""
+    n = weight.shape[0] if kind == SPHEREFACE else weight.shape[1]
+    if x.shape[0] == 0:
+        ops.ptr(x)
+        return x.new_zeros((0, n), dtype=torch.float32) + 0.0 * (x.sum() + weight.sum())
+    _check_labels(label, n)
+    return MarginExtHeadFn.apply(x, weight, label, kind, mi, p0, p1)
 
 
 class FocalLossFn(torch.autograd.Function):

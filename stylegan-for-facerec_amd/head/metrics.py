@@ -2,10 +2,17 @@
 
     from head.metrics import ArcFace, CosFace, SphereFace, Am_softmax        (reference train.py:9)
 
-``ArcFace`` / ``CosFace`` (the two heads the shipped configs and BASELINE.json name) run on the HIP kernels
-(row normalise -> MFMA cosine GEMM with the margin / label-select / scale epilogue -> closed-form backward).
-``SphereFace`` / ``Am_softmax`` are constructed eagerly by the reference driver (train.py:178-181) and are
-therefore provided too, as small plain-PyTorch modules outside the accelerated path.
+All four heads the reference driver can select (``HEAD_NAME``, train.py:56,178-182) run on the HIP kernels when their
+input is a device tensor:
+  * ``ArcFace`` / ``CosFace`` (the two heads the shipped configs and BASELINE.json name): row normalise -> MFMA cosine
+    GEMM with the margin / label-select / scale epilogue -> closed-form backward;
+  * ``SphereFace`` / ``Am_softmax``: the same cosine GEMM stores the raw cosines, a row kernel applies the clamp and the
+    margin (SphereFace: Chebyshev phi, lambda blend, times ||x||; Am_softmax: c - m on the label, times s), and the
+    backward pass reads the raw cosines again for the clamp mask.  Am_softmax normalises the columns of its [in, out]
+    ``kernel`` (no eps) and not the embeddings.
+On host tensors ``SphereFace`` / ``Am_softmax`` run the reference's plain-PyTorch arithmetic (the restatement the tests
+compare with); ``ArcFace`` / ``CosFace`` refuse host tensors.  ``SphereFace.iter`` counts forward calls on either path, as
+in the reference; train.py carries it across a resume in the State_* file.
 
 Differences from the reference that a caller can observe:
   * ``device_id`` is accepted for signature compatibility but the class-dimension ``.cuda(i)`` split of
@@ -81,7 +88,7 @@ class CosFace(_MarginHead):
 
 
 class SphereFace(nn.Module):
-    """cos(m*theta) head (reference head/metrics.py:200-277).  Not on the accelerated path; plain PyTorch."""
+    """cos(m*theta) head (reference head/metrics.py:200-277): HIP kernels on device tensors, plain PyTorch on the host."""
 
     def __init__(self, in_features, out_features, device_id, m=4):
         super().__init__()
@@ -98,6 +105,11 @@ class SphereFace(nn.Module):
     def forward(self, input, label):
         self.iter += 1
         self.lamb = max(self.LambdaMin, self.base * (1 + self.gamma * self.iter) ** (-1 * self.power))
+        if input.is_cuda:
+            if self.weight.device != input.device:
+                self.to(input.device)  # moved once, next to the features (the reference copies W every step)
+            return FRF.margin_ext_head(input, self.weight, label.to(input.device), FRF.SPHEREFACE, self.m,
+                                       1 + self.lamb, 0.0)
         w = self.weight.to(input.device)
         c = F.linear(F.normalize(input), F.normalize(w)).clamp(-1, 1)
         k = (self.m * c.detach().acos() / 3.14159265).floor()
@@ -108,7 +120,8 @@ class SphereFace(nn.Module):
 
 
 class Am_softmax(nn.Module):
-    """Additive-margin softmax with a [in, out] ``kernel`` (reference head/metrics.py:287-333). Plain PyTorch."""
+    """Additive-margin softmax with a [in, out] ``kernel`` (reference head/metrics.py:287-333): HIP kernels on device
+    tensors, plain PyTorch on the host."""
 
     def __init__(self, in_features, out_features, device_id, m=0.35, s=30.0):
         super().__init__()
@@ -117,6 +130,11 @@ class Am_softmax(nn.Module):
         self.kernel.data.uniform_(-1, 1).renorm_(2, 1, 1e-5).mul_(1e5)
 
     def forward(self, embbedings, label):
+        if embbedings.is_cuda:
+            if self.kernel.device != embbedings.device:
+                self.to(embbedings.device)
+            return FRF.margin_ext_head(embbedings, self.kernel, label.to(embbedings.device), FRF.AM_SOFTMAX, 0,
+                                       self.m, self.s)
         kn = self.kernel.to(embbedings.device)
         c = torch.mm(embbedings, kn / kn.norm(2, 0, True)).clamp(-1, 1)
         hot = torch.zeros_like(c).scatter_(1, label.view(-1, 1), 1).bool()

@@ -243,6 +243,8 @@ def main():
         if state.get("lr_stage_applied") is not None and not optimizer_loaded:
             print("State file marks the LR stage of epoch {} as applied, but no optimizer checkpoint was loaded: "
                   "the stage is applied again".format(state.get("lr_stage_applied")))
+        if "head_iter" in state and hasattr(head, "iter"):  # SphereFace's lambda schedule (older State_ files: no key)
+            head.iter = int(state["head_iter"])
         if "torch_rng" in state:
             torch.set_rng_state(state["torch_rng"])
             n = state["numpy_rng"]
@@ -258,6 +260,7 @@ def main():
     FRF.CHECK_LABELS = False  # labels come from the dataset's own class index
     for epoch in range(start_epoch, cfg["NUM_EPOCH"]):
         epoch_first_batch = batch
+        epoch_first_iter = getattr(head, "iter", None)
         if epoch in cfg["STAGES"] and epoch != lr_stage_done:
             schedule_lr(optimizer)
         backbone.train()
@@ -359,12 +362,14 @@ def main():
             finished = not (args.max_steps and batch >= args.max_steps and (batch - epoch_first_batch) < epoch_len)
             # the repeated epoch restarts the batch counter at its first batch (warm-up, logging axis) and must not divide
             # the LR a second time if it is a stage epoch (the Optimizer_* file already holds the divided LR)
-            torch.save({"epoch": epoch + 1 if finished else epoch, "batch": batch if finished else epoch_first_batch,
-                        "dropout_stream": runner.step_seed, "epoch_finished": finished,
-                        "lr_stage_applied": int(epoch) if (not finished and epoch in cfg["STAGES"]) else None,
-                        "torch_rng": torch.get_rng_state(),
-                        "numpy_rng": _np_state_plain(np.random.get_state())},
-                       os.path.join(root, "State_{}_{}".format(cfg["HEAD_NAME"], tag)))
+            run_state = {"epoch": epoch + 1 if finished else epoch, "batch": batch if finished else epoch_first_batch,
+                         "dropout_stream": runner.step_seed, "epoch_finished": finished,
+                         "lr_stage_applied": int(epoch) if (not finished and epoch in cfg["STAGES"]) else None,
+                         "torch_rng": torch.get_rng_state(),
+                         "numpy_rng": _np_state_plain(np.random.get_state())}
+            if epoch_first_iter is not None:  # the head's forward counter (SphereFace: lambda), at the same point as "batch"
+                run_state["head_iter"] = int(head.iter if finished else epoch_first_iter)
+            torch.save(run_state, os.path.join(root, "State_{}_{}".format(cfg["HEAD_NAME"], tag)))
         if args.max_steps and batch >= args.max_steps:
             break
     if world > 1:
