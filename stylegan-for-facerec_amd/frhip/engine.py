@@ -281,14 +281,16 @@ class BackbonePlan(object):
         # its consumer: the next conv1 loads y2 and x, writes out = a*y2 + b + x (same bits as fr_bn_apply) on the way and
         # applies BN1 to it (FR_PRO_RESBN).  Per fused edge: bn_apply + one finalize launch gone.  Identity units without SE
         # whose conv2 and whose successor's conv1 run on LDS-strip instances (IR-50: 17 of 24 units).  FRHIP_RES_MOMENTS=0:
-        # A/B switch.
+        # A/B switch.  Behind squeeze-excite units (out = gate[image][c] * BN2(y2) + x) the moments are kept PER IMAGE and
+        # combined with the gates by the launch that computes them (fr_se_pool_parts_mlp_fwd_res); the moments of x are
+        # carried from unit to unit (one fr_image_moments pass at the head of a stage).
         self.res_moments = bool(_switch("FRHIP_RES_MOMENTS", 1)) and self.fr == FR_BF16 and self.use_strip and not self.fold
-        # ... and behind squeeze-excite units (out = gate[image][c] * BN2(y2) + x): the same moments PER IMAGE, combined with
-        # the gates by the launch that computes them (fr_se_pool_parts_mlp_fwd_res); the moments of x are carried from unit to
-        # unit (one fr_image_moments pass at the head of a stage).
-        self.res_moments_se = self.res_moments
         self.use_stem_gemm = self.fr == FR_BF16 and not _switch("FRHIP_NO_STEM_GEMM", 0) and not self.body_only
-        self.use_s2 = self.use_strip  # the stride-2 strip kernels follow FRHIP_NO_STRIP
+        # Round 4: the stem forward as two passes over the rows (statistics, then GEMM + BN + PReLU in one kernel) and its
+        # backward on a RECOMPUTED y0: the GEMM is 13 GFLOP at batch 256, its output 411 MB -- y0 is never written or read,
+        # the fr_bn_apply pass over it is gone (-0.06 ... -0.09 ms per step, profiles/r04_ab_stem_two_pass.txt).  Only the
+        # folded inference plan keeps y0 on the stem GEMM; a plan with a backward list never folds.
+        self.stem_two_pass = self.use_stem_gemm and not self.fold
         self.slab, self._slab_users = None, []
         # deferred slab sums (FrWgradArgs.defer / prev_*): a weight-gradient launch that supports it leaves the sum of its
         # slabs to the NEXT such launch of the side stream (two slab buffers alternate); fr_reduce_slabs flushes the last
@@ -326,12 +328,7 @@ class BackbonePlan(object):
             # (Round 4 also carried the stem GEMMs on implicit im2col rows, FRHIP_STEM_IMPLICIT: 205 MB less memory, +0.05-0.09
             # ms per step, profiles/r04_ab_stem_implicit.txt; removed in round 5.)
             self.X0 = self._act(M0, self.K0)
-            # Round 4: the stem forward as two passes over the rows (statistics, then GEMM + BN + PReLU in one kernel) and its
-            # backward on a RECOMPUTED y0: the GEMM is 13 GFLOP at batch 256, its output 411 MB -- y0 is never written or
-            # read, the fr_bn_apply pass over it is gone (-0.06 ... -0.09 ms per step, profiles/r04_ab_stem_two_pass.txt).
-            self.stem_two_pass = self.use_stem_gemm and not self.fold
-            self.stem_recompute = self.stem_two_pass
-            self.y0 = None if (self.stem_recompute or (self.stem_two_pass and self.infer)) else self._act(M0, 64)
+            self.y0 = None if self.stem_two_pass else self._act(M0, 64)
             self.W0p = torch.empty(64, self.K0, device=dev, dtype=self.tdtype)
             self.gW0p = torch.zeros(64, self.K0, device=dev)
             self.bn0 = _BN(self.stem[1], self.pool)
@@ -501,9 +498,6 @@ class BackbonePlan(object):
         """Gradient target of a parameter: its arena view when it trains, else None."""
         return self.gviews[id(p)] if p.requires_grad else None
 
-    def _conv_master(self, conv):
-        return conv.weight
-
     # ---- conv dispatch ----------------------------------------------------------------------------
     def _check_part(self, n, kw):
         """Fail loudly (instead of a GPU memory fault) if an epilogue's partial rows would not fit their buffer."""
@@ -517,7 +511,12 @@ class BackbonePlan(object):
     def _conv(self, L, **kw):
         """Append a convolution launch; returns the number of partial rows its epilogue writes.  bf16 stride-1
         3x3 layers whose shape is in the strip table run with the input strip resident in LDS."""
-        return self._check_part(self._conv_launch(L, **kw), kw)
+        family, n, frag = self._conv_route(kw)
+        if self._note_weight(kw["w"], frag):
+            kw = dict(kw, w_frag=1)
+        make = {"strip": ops.conv_strip, "s2": ops.conv_s2_strip}.get(family)
+        L.append(make(self.stream, **kw) if make else ops.conv(self.stream, self.fr, **kw))
+        return self._check_part(n, kw)
 
     def _conv_route(self, kw):
         """Which kernel family runs a convolution, without side effects: (family, partial rows, fragment-order weights).
@@ -535,7 +534,7 @@ class BackbonePlan(object):
                 return "strip", n, self.w_frag and kw["SC"] % 64 == 0 and kw["N"] % 64 == 0 and bool(
                     _lib.lib.fr_conv3x3_strip_takes_frag(kw["B"], kw["SC"], kw["N"], kw["SW"]))
         mode = kw.get("mode", 0)
-        if (self.fr == FR_BF16 and self.use_strip and self.use_s2 and kw["KH"] == 3 and kw["stride"] == 2 and
+        if (self.fr == FR_BF16 and self.use_strip and kw["KH"] == 3 and kw["stride"] == 2 and
                 mode in (0, 2)):
             wl = kw["RW"] if mode == 0 else kw["SW"]
             n = ops.s2_strip_parts(kw["B"], kw["SC"], kw["N"], wl, mode)
@@ -544,16 +543,6 @@ class BackbonePlan(object):
         if mode == 2:  # all four parity classes in one launch: [class][M tile] partial rows
             return "igemm", 4 * ((kw["B"] * (kw["RH"] // 2) * (kw["RW"] // 2) + 127) // 128), False
         return "igemm", (kw["B"] * kw["RH"] * kw["RW"] + 127) // 128, False
-
-    def _conv_launch(self, L, **kw):
-        family, n, frag = self._conv_route(kw)
-        if self._note_weight(kw["w"], frag):
-            kw = dict(kw, w_frag=1)
-        make = {"strip": ops.conv_strip, "s2": ops.conv_s2_strip}.get(family)
-        L.append(make(self.stream, **kw) if make else ops.conv(self.stream, self.fr, **kw))
-        # partial rows that are strips, image-major (forward launches of the strip families), else 0
-        self._last_conv_strips = n if family == "strip" or (family == "s2" and kw.get("mode", 0) == 0) else 0
-        return n
 
     def _note_weight(self, w, frag):
         """Book-keeping of the weight layouts: a packed weight tensor has ONE layout, so every launch that reads it must agree.
@@ -590,7 +579,7 @@ class BackbonePlan(object):
             fills = kw["B"] * (kw["SW"] // rows) // (4 if kw["SW"] == 7 else 1)
             groups = int(max(1, min(fills, _WGRAD_WGS // tiles if tiles <= _WGRAD_WGS else 1)))
             return self._slab_launch(L, dict(kw, nsplit=groups), groups * kw["Cout"] * 9 * kw["SC"], param=param)
-        if (self.fr == FR_BF16 and self.use_strip and self.use_s2 and kw["KH"] == 3 and kw["stride"] == 2 and
+        if (self.fr == FR_BF16 and self.use_strip and kw["KH"] == 3 and kw["stride"] == 2 and
                 kw["GW"] in (56, 28, 14, 7) and kw["SW"] == 2 * kw["GW"] and kw["Cout"] % 64 == 0 and kw["SC"] % 64 == 0):
             # stride-2 layers: the same kernel on the four parity planes of the input (conv_wgrad_strip.hip, S2)
             tiles = (kw["Cout"] // 64) * (kw["SC"] // 64)
@@ -682,7 +671,7 @@ class BackbonePlan(object):
         """Non-zero when unit i's output is formed by unit i+1's conv1 and its statistics come from moments: 1 = plain unit
         (FR_PRO_RESBN, fr_bn_finalize_res), 2 = squeeze-excite unit (FR_PRO_RESBN_SE, per-image moments through
         fr_se_pool_parts_mlp_fwd_res)."""
-        if not self.res_moments or i < 0 or i + 1 >= len(self.units):
+        if not self.res_moments or i + 1 >= len(self.units):
             return 0
         u, n = self.units[i], self.units[i + 1]
         if u.sc_conv is not None or u.stride != 1 or n.cin != u.depth:
@@ -701,7 +690,7 @@ class BackbonePlan(object):
             return 1
         # squeeze-excite: the gates weigh every image differently, so the moments are kept per image -- conv2's partial rows
         # must be strips of single images (not the multi-image 7x7 workgroups) and so must the consumer's workgroups
-        if not self.res_moments_se or self.B > 65535:
+        if self.B > 65535:
             return 0
         rows2 = ops.strip_parts(self.B, u.depth, u.depth, u.Ho, ops.EPI_STATS_X)
         rows1 = ops.strip_parts(self.B, n.cin, n.depth, n.H, ops.EPI_STORE) if n.cin != n.depth else rows2
@@ -737,244 +726,258 @@ class BackbonePlan(object):
                               bn.C, bn.mean, bn.invstd, bn.scale, bn.shift, st))
 
     def _build_forward(self):
-        B, S, st, fr = self.B, self.S, self.stream, self.fr
-        P = []  # weight packing (runs every step: master weights change)
-        L = []
+        P, L = [], []  # weight packing (runs every step: master weights change), forward pass
         self._pack_reqs = []  # (master, wp|None, wt|None, Cout, taps, Cin[, oscale]) -> one multi-tensor launch
         self._fold_bns = []   # fold mode: every BatchNorm whose eval coefficients the multi launch computes
-        fold = self.fold
-        stats_epi = ops.EPI_STORE if fold else ops.EPI_STATS  # eval mode: nobody reads the partial sums
-        stats_part = None if fold else self.part
-        first_bn = self.ubuf[0]["bn1"]
-        if self.body_only:
-            # a bare stack of residual units: the caller's activation sits in z0; its statistics for the first BN1
-            C0 = self.units[0].cin
-            nb = ops.grid_blocks(self.M0, C0, fr)
-            if not fold:
-                L.append(ops.call("fr_channel_stats", self.z0, self.M0, C0, self.part, nb, fr, st))
-            self._bn_train_launches(L, first_bn, self.part, nb, self.M0)
-        else:
-            sc, sb, sp = self.stem
-            # ---- stem: im2col -> GEMM(+stats) -> BN+PReLU apply (+stats for unit 0's BN1)
-            w0 = sc.weight
-            P.append(ops.call("fr_pack_stem", w0, w0.stride(0), w0.stride(1), w0.stride(2), w0.stride(3), self.W0p, 64,
-                              w0.shape[1], self.K0, fr, st))
-            self.l_im2col = None  # bound per call (input pointer changes)
-            two_pass = self.stem_two_pass
-            if two_pass:
-                # Round 4: the GEMM is 13 GFLOP, its output 411 MB.  Pass 1 leaves only the statistics of y0; pass 2 recomputes
-                # y0 and writes z0 = PReLU(BN0(y0)) (+ y0 for the backward pass) with the statistics of z0 in its epilogue:
-                # the fr_bn_apply pass over the stem output (822 MB of traffic, 161 us at batch 256) is gone.
-                mt0 = int(min(2048, (self.M0 + 63) // 64))
-                if self.bn0.mod.training:
-                    L.append(ops.call("fr_stem_gemm", self.X0, self.W0p, None, self.part, self.M0, self.K0, mt0, st))
-                self._bn_train_launches(L, self.bn0, self.part, mt0, self.M0)
-                L.append(ops.call("fr_stem_gemm_bn_prelu", self.X0, self.W0p, self.bn0.scale, self.bn0.shift, sp.weight,
-                                  self.y0, self.z0, stats_part, self.M0, self.K0, mt0, st))
-                self._bn_train_launches(L, first_bn, self.part, mt0, self.M0)
-            elif self.use_stem_gemm:  # 3.2 M rows x 64 columns x K0: the row-streaming kernels of stem_gemm.hip
-                mt0 = int(min(2048, (self.M0 + 63) // 64))
-                L.append(ops.call("fr_stem_gemm", self.X0, self.W0p, self.y0, self.part, self.M0, self.K0, mt0, st))
-            else:
-                mt0 = (self.M0 + 127) // 128
-                L.append(ops.conv(st, fr, src=self.X0, w=self.W0p, out=self.y0, B=self.M0, RH=1, RW=1, SH=1, SW=1,
-                                  SC=self.K0, N=64, KH=1, KW=1, stride=1, pad=0, mode=0, lda=self.K0, ldc=64, pro=0,
-                                  epi=ops.EPI_STATS, part=self.part))
-            if not two_pass:
-                self._bn_train_launches(L, self.bn0, self.part, mt0, self.M0)
-                nb = ops.grid_blocks(self.M0, 64, fr)
-                L.append(ops.bn_apply(st, fr, x=self.y0, out=self.z0, scale=self.bn0.scale, shift=self.bn0.shift,
-                                      slope=sp.weight, part=stats_part, B=B, H=S, W=S, C=64, res_kind=0, res_stride=1,
-                                      nblocks=nb))
-                self._bn_train_launches(L, first_bn, self.part, nb, self.M0)
-        x = self.z0
+        self._dropout_args = []  # (launch, position of the dropout probability; the seed follows it): set by run_forward
+        x = self._fwd_input(P, L)
         # Round 6: the packing of the 3x3 weights (350 MB of traffic, 60 us) runs on the weight-gradient stream, idle in the
         # forward pass, beside the stem (im2col rows + two GEMM passes, HBM-bound but below the HBM rate on their own); the main
         # stream waits for it in front of the first residual unit.  Training plans with two streams
-        self.pack_side = self.dual and not fold and not self.infer and not self.body_only
+        self.pack_side = self.dual and not self.fold and not self.infer and not self.body_only
         if self.pack_side:
             self._pack_ev0, self._pack_ev1 = torch.cuda.Event(), torch.cuda.Event()
             L.append(_EvWait(self.stream1_t, self._pack_ev1))
+        edges = [self._res_edge(i) for i in range(len(self.units))]
+        x_prev = None  # the previous unit's input
         for i, u in enumerate(self.units):
             d = self.ubuf[i]
-            rin, rout = B * u.H * u.H, B * u.Ho * u.Ho
-            w1, w2 = self._conv_master(u.conv1), self._conv_master(u.conv2)
-            if fr == FR_BF16:
-                self._pack_reqs.append((w1, d["wp1"], d["wt1"], u.depth, 9, u.cin))
-                self._pack_reqs.append((w2, d["wp2"], d["wt2"], u.depth, 9, u.depth))
-                wp1, wp2 = d["wp1"], d["wp2"]
+            w1, w2 = self._packed(u.conv1.weight, d, "1"), self._packed(u.conv2.weight, d, "2")
+            edge_in = edges[i - 1] if i else 0
+            self._fwd_conv1(L, i, x, x_prev, w1, edge_in)
+            if self.fold and u.se is None and (u.sc_conv is not None or u.stride == 1):
+                self._fwd_folded(L, i, x)
+            elif edges[i]:
+                self._fwd_res_edge(L, i, x, w2, edge_in, edges[i])
             else:
-                self._pack_reqs.append((w1, None, d["wt1"], u.depth, 9, u.cin))
-                self._pack_reqs.append((w2, None, d["wt2"], u.depth, 9, u.depth))
-                wp1, wp2 = w1, w2
-            bn1, bn2 = d["bn1"], d["bn2"]
-            folded = fold and u.se is None and (u.sc_conv is not None or u.stride == 1)
-            edge_in, edge_out = self._res_edge(i - 1), self._res_edge(i)
-            if edge_in:
-                # x (the previous unit's output) does not exist yet: this launch forms it from that unit's y2 and input,
-                # stores it, and applies BN1 to it
-                pd = self.ubuf[i - 1]
-                se_kw = dict(pro=ops.PRO_RESBN_SE, pro_g=pd["s"]) if edge_in == 2 else dict(pro=ops.PRO_RESBN)
-                self._conv(L, src=pd["y2"], src2=x_in, pro_out=x, w=wp1, out=d["y1"], B=B, RH=u.H, RW=u.H, SH=u.H, SW=u.H,
-                           SC=u.cin, N=u.depth, KH=3, KW=3, stride=1, pad=1, mode=0, lda=u.cin, ldc=u.depth,
-                           pro_a=pd["bn2"].scale, pro_b=pd["bn2"].shift, pro_c=bn1.scale, pro_d=bn1.shift,
-                           epi=ops.EPI_STORE, **se_kw)
-            else:
-                self._conv(L, src=x, w=wp1, out=d["y1"], B=B, RH=u.H, RW=u.H, SH=u.H, SW=u.H, SC=u.cin,
-                           N=u.depth, KH=3, KW=3, stride=1, pad=1, mode=0, lda=u.cin, ldc=u.depth,
-                           pro=ops.PRO_BN, pro_a=bn1.scale, pro_b=bn1.shift, epi=ops.EPI_STORE)
-            x_in = x  # this unit's input (the residual term of its output)
+                self._fwd_unit(L, i, x, w2)
+            x_prev, x = x, d["out"]  # behind a residual edge, out is written by the next unit's conv1
+        if self.body_only:
+            self.feat = x
+        else:
+            self._fwd_output(P, L, x)
+        self._place_packing(P)
+        self.pack_list, self.fwd_list = P, L
+
+    def _packed(self, w, d, k):
+        """Queue the packing of conv weight w into d["wp" + k] (compute dtype, bf16 path) and d["wt" + k] (transposed, read
+        by the data gradient).  Returns the operand a forward launch reads: the packed copy, or the fp32 master itself."""
+        wp = d.get("wp" + k)
+        self._pack_reqs.append((w, wp, d["wt" + k], w.shape[0], w.shape[2] * w.shape[3], w.shape[1]))
+        return w if wp is None else wp
+
+    def _next_bn(self, i):
+        """The BatchNorm that reads unit i's output: the next unit's BN1, the output layer's BN, or None (a bare stack)."""
+        if i + 1 < len(self.units):
+            return self.ubuf[i + 1]["bn1"]
+        return None if self.body_only else self.bn_out
+
+    def _fwd_input(self, P, L):
+        """z0, the first unit's input, and its statistics for the first BN1.  A bare stack: the caller's activation.  Else
+        the stem, z0 = PReLU(BN0(y0)), y0 = X0 * W0p^T: two passes of the stem GEMM (y0 never stored), or y0 stored by the
+        stem GEMM (folded inference) or the generic GEMM (fp32 path) and an fr_bn_apply pass over it."""
+        M0, st, fr = self.M0, self.stream, self.fr
+        first_bn = self.ubuf[0]["bn1"]
+        if self.body_only:
+            C0 = self.units[0].cin
+            nb = ops.grid_blocks(M0, C0, fr)
+            if not self.fold:
+                L.append(ops.call("fr_channel_stats", self.z0, M0, C0, self.part, nb, fr, st))
+            self._bn_train_launches(L, first_bn, self.part, nb, M0)
+            return self.z0
+        w0, sp = self.stem[0].weight, self.stem[2]
+        P.append(ops.call("fr_pack_stem", w0, w0.stride(0), w0.stride(1), w0.stride(2), w0.stride(3), self.W0p, 64,
+                          w0.shape[1], self.K0, fr, st))
+        stats_part = None if self.fold else self.part
+        mt0 = int(min(2048, (M0 + 63) // 64))  # 3.2 M rows x 64 columns x K0: the row-streaming kernels of stem_gemm.hip
+        if self.stem_two_pass:
+            # Round 4: the GEMM is 13 GFLOP, its output 411 MB.  Pass 1 leaves only the statistics of y0; pass 2 recomputes y0
+            # and writes z0 = PReLU(BN0(y0)) with the statistics of z0 in its epilogue: the fr_bn_apply pass over the stem
+            # output (822 MB of traffic, 161 us at batch 256) is gone.
+            if self.bn0.mod.training:
+                L.append(ops.call("fr_stem_gemm", self.X0, self.W0p, None, self.part, M0, self.K0, mt0, st))
+            self._bn_train_launches(L, self.bn0, self.part, mt0, M0)
+            L.append(ops.call("fr_stem_gemm_bn_prelu", self.X0, self.W0p, self.bn0.scale, self.bn0.shift, sp.weight, None,
+                              self.z0, stats_part, M0, self.K0, mt0, st))
+            self._bn_train_launches(L, first_bn, self.part, mt0, M0)
+            return self.z0
+        if self.use_stem_gemm:
+            L.append(ops.call("fr_stem_gemm", self.X0, self.W0p, self.y0, self.part, M0, self.K0, mt0, st))
+        else:
+            mt0 = (M0 + 127) // 128
+            L.append(ops.conv(st, fr, src=self.X0, w=self.W0p, out=self.y0, B=M0, RH=1, RW=1, SH=1, SW=1, SC=self.K0, N=64,
+                              KH=1, KW=1, stride=1, pad=0, mode=0, lda=self.K0, ldc=64, pro=0, epi=ops.EPI_STATS,
+                              part=self.part))
+        self._bn_train_launches(L, self.bn0, self.part, mt0, M0)
+        nb = ops.grid_blocks(M0, 64, fr)
+        L.append(ops.bn_apply(st, fr, x=self.y0, out=self.z0, scale=self.bn0.scale, shift=self.bn0.shift, slope=sp.weight,
+                              part=stats_part, B=self.B, H=self.S, W=self.S, C=64, res_kind=0, res_stride=1, nblocks=nb))
+        self._bn_train_launches(L, first_bn, self.part, nb, M0)
+        return self.z0
+
+    def _fwd_conv1(self, L, i, x, x_prev, w, edge_in):
+        """conv1 of unit i: y1 = conv3x3(BN1(x)).  Behind a residual edge (edge_in, see _res_edge) x, the previous unit's
+        output, does not exist yet: this launch forms it from that unit's y2 and its input x_prev, stores it and applies BN1
+        to it."""
+        u, d = self.units[i], self.ubuf[i]
+        bn1 = d["bn1"]
+        kw = dict(w=w, out=d["y1"], B=self.B, RH=u.H, RW=u.H, SH=u.H, SW=u.H, SC=u.cin, N=u.depth, KH=3, KW=3, stride=1,
+                  pad=1, mode=0, lda=u.cin, ldc=u.depth, epi=ops.EPI_STORE)
+        if not edge_in:
+            self._conv(L, src=x, pro=ops.PRO_BN, pro_a=bn1.scale, pro_b=bn1.shift, **kw)
+            return
+        pd = self.ubuf[i - 1]
+        pro = dict(pro=ops.PRO_RESBN_SE, pro_g=pd["s"]) if edge_in == 2 else dict(pro=ops.PRO_RESBN)
+        self._conv(L, src=pd["y2"], src2=x_prev, pro_out=x, pro_a=pd["bn2"].scale, pro_b=pd["bn2"].shift, pro_c=bn1.scale,
+                   pro_d=bn1.shift, **pro, **kw)
+
+    def _fwd_folded(self, L, i, x):
+        """The rest of unit i in inference with BN2 (and the shortcut BN) folded into the packed weights: out =
+        conv2'(PReLU(y1)) + shift2 [+ shiftS] + shortcut straight from conv2's epilogue -- y2 is never written, no BN-apply
+        pass."""
+        u, d, B = self.units[i], self.ubuf[i], self.B
+        bn2 = d["bn2"]
+        self._fold_bns += [bn for bn in (bn2, d.get("bnS"), self._next_bn(i)) if bn is not None]
+        self._pack_reqs.append((u.conv2.weight, d["wf2"], None, u.depth, 9, u.depth, bn2.scale))
+        if u.sc_conv is not None:
+            self._pack_reqs.append((u.sc_conv.weight, d["wfS"], None, u.depth, 1, u.cin, d["bnS"].scale))
+            L.append(ops.conv(self.stream, self.fr, src=x, w=d["wfS"], out=d["yS"], B=B, RH=u.Ho, RW=u.Ho, SH=u.H, SW=u.H,
+                              SC=u.cin, N=u.depth, KH=1, KW=1, stride=u.stride, pad=0, mode=0, lda=u.cin, ldc=u.depth,
+                              pro=0, epi=ops.EPI_STORE))
+            res, shift_s = d["yS"], d["bnS"].shift
+        else:
+            res, shift_s = x, self.zeros_c[:u.depth]
+        self._conv(L, src=d["y1"], w=d["wf2"], out=d["out"], B=B, RH=u.Ho, RW=u.Ho, SH=u.H, SW=u.H, SC=u.depth, N=u.depth,
+                   KH=3, KW=3, stride=u.stride, pad=1, mode=0, lda=u.depth, ldc=u.depth, ldaux=u.depth, pro=ops.PRO_PRELU,
+                   pro_a=u.prelu.weight, epi=ops.EPI_BIAS_RES, epi_a=bn2.shift, epi_b=shift_s, aux=res)
+
+    def _fwd_res_edge(self, L, i, x, w, edge_in, edge):
+        """The rest of unit i, whose output the next unit's conv1 forms (edge, see _res_edge): conv2's epilogue also sums
+        y2 * x (FR_EPI_STATS_X), from which BN2's coefficients and the next BN1's statistics follow without a pass over
+        out = BN2(y2) [* gate] + x."""
+        u, d, B, st = self.units[i], self.ubuf[i], self.B, self.stream
+        bn1, bn2, nxt = d["bn1"], d["bn2"], self._next_bn(i)
+        rout = B * u.Ho * u.Ho
+        if edge == 2 and edge_in != 2:  # head of a squeeze-excite chain: per-image moments of its input
+            d["xm"] = torch.empty(B, 2, u.depth, device=self.device)
+            L.append(ops.call("fr_image_moments", x, B, u.H * u.H, u.depth, d["xm"], st))
+        np2 = self._conv(L, src=d["y1"], w=w, out=d["y2"], B=B, RH=u.Ho, RW=u.Ho, SH=u.H, SW=u.H, SC=u.depth, N=u.depth,
+                         KH=3, KW=3, stride=1, pad=1, mode=0, lda=u.depth, ldc=u.depth, ldaux=u.depth, pro=ops.PRO_PRELU,
+                         pro_a=u.prelu.weight, epi=ops.EPI_STATS_X, aux=x, part=self.part)
+        if edge == 1:
+            L.append(ops.call("fr_bn_finalize_res", self.part, np2, u.depth, self._bn_fields(bn2, rout), bn1.mean,
+                              bn1.invstd, float(bn1.mod.eps), self._bn_fields(nxt, rout), st))
+            return
+        L.append(ops.call("fr_bn_finalize_res", self.part, np2, u.depth, self._bn_fields(bn2, rout), None, None, 0.0, None,
+                          st))
+        d["om"] = torch.empty(B, 2, u.depth, device=self.device)
+        xm = self.ubuf[i - 1]["om"] if edge_in == 2 else d["xm"]
+        L.append(ops.call("fr_se_pool_parts_mlp_fwd_res", self.part, np2 // B, 3, bn2.scale, bn2.shift, u.se.fc1.weight,
+                          u.se.fc2.weight, d["pooled"], d["hidden"], d["s"], B, u.Ho * u.Ho, u.depth,
+                          u.se.fc1.out_channels, xm, d["om"], st))
+        self._bn_train_launches(L, nxt, d["om"], B, rout)
+
+    def _fwd_unit(self, L, i, x, w):
+        """The rest of an ordinary unit i: conv2 (+ statistics of y2), the shortcut, the squeeze-excite gate, and one
+        fr_bn_apply pass out = BN2(y2) [* s] + shortcut (+ the statistics of out for the next BatchNorm)."""
+        u, d, B, st, fr = self.units[i], self.ubuf[i], self.B, self.stream, self.fr
+        rout = B * u.Ho * u.Ho
+        bn2, bnS, nxt = d["bn2"], d.get("bnS"), self._next_bn(i)
+        stats_epi = ops.EPI_STORE if self.fold else ops.EPI_STATS  # eval mode: nobody reads the partial sums
+        stats_part = None if self.fold else self.part
+        c2 = dict(src=d["y1"], w=w, out=d["y2"], B=B, RH=u.Ho, RW=u.Ho, SH=u.H, SW=u.H, SC=u.depth, N=u.depth, KH=3, KW=3,
+                  stride=u.stride, pad=1, mode=0, lda=u.depth, ldc=u.depth, pro=ops.PRO_PRELU, pro_a=u.prelu.weight,
+                  epi=stats_epi, part=stats_part)
+        np2 = self._conv(L, **c2)
+        self._bn_train_launches(L, bn2, self.part, np2, rout)
+        if u.sc_conv is not None:
             # (Round 4, measured and removed: the convolved shortcut of a stage entry + its statistics launch on the side stream
             # beside conv2 -- the side stream idles during the forward pass and the three launches take 24-51 us each on the
             # generic GEMM: 15.01-15.05 against 14.98-15.00 ms per step, profiles/r04_ab_shortcut_on_side_stream.txt: the two
             # event edges cost what the overlap saves.)
-            if folded:
-                # inference with BN2 (and the shortcut BN) folded into the packed weights: out = conv2'(PReLU(y1)) +
-                # shift2 [+ shiftS] + shortcut straight from conv2's epilogue -- y2 is never written, no BN-apply pass
-                self._fold_bns += [bn2] + ([d["bnS"]] if u.sc_conv is not None else [])
-                self._pack_reqs.append((w2, d["wf2"], None, u.depth, 9, u.depth, bn2.scale))
-                if u.sc_conv is not None:
-                    ws = self._conv_master(u.sc_conv)
-                    self._pack_reqs.append((ws, d["wfS"], None, u.depth, 1, u.cin, d["bnS"].scale))
-                    L.append(ops.conv(st, fr, src=x, w=d["wfS"], out=d["yS"], B=B, RH=u.Ho, RW=u.Ho, SH=u.H, SW=u.H,
-                                      SC=u.cin, N=u.depth, KH=1, KW=1, stride=u.stride, pad=0, mode=0, lda=u.cin,
-                                      ldc=u.depth, pro=0, epi=ops.EPI_STORE))
-                    res, shift_s = d["yS"], d["bnS"].shift
-                else:
-                    res, shift_s = x, self.zeros_c[:u.depth]
-                self._conv(L, src=d["y1"], w=d["wf2"], out=d["out"], B=B, RH=u.Ho, RW=u.Ho, SH=u.H, SW=u.H, SC=u.depth,
-                           N=u.depth, KH=3, KW=3, stride=u.stride, pad=1, mode=0, lda=u.depth, ldc=u.depth,
-                           ldaux=u.depth, pro=ops.PRO_PRELU, pro_a=u.prelu.weight, epi=ops.EPI_BIAS_RES, epi_a=bn2.shift,
-                           epi_b=shift_s, aux=res)
-                nxt = self.ubuf[i + 1]["bn1"] if i + 1 < len(self.units) else (None if self.body_only else self.bn_out)
-                if nxt is not None:
-                    self._bn_train_launches(L, nxt, None, 0, rout)
-                x = d["out"]
-                continue
-            if edge_out:
-                if edge_out == 2 and edge_in != 2:  # head of a squeeze-excite chain: per-image moments of its input
-                    d["xm"] = torch.empty(B, 2, u.depth, device=self.device)
-                    L.append(ops.call("fr_image_moments", x_in, B, u.H * u.H, u.depth, d["xm"], st))
-                np2 = self._conv(L, src=d["y1"], w=wp2, out=d["y2"], B=B, RH=u.Ho, RW=u.Ho, SH=u.H, SW=u.H, SC=u.depth,
-                                 N=u.depth, KH=3, KW=3, stride=1, pad=1, mode=0, lda=u.depth, ldc=u.depth, ldaux=u.depth,
-                                 pro=ops.PRO_PRELU, pro_a=u.prelu.weight, epi=ops.EPI_STATS_X, aux=x_in, part=self.part)
-                nxt = self.ubuf[i + 1]["bn1"]
-                if edge_out == 1:
-                    L.append(ops.call("fr_bn_finalize_res", self.part, np2, u.depth, self._bn_fields(bn2, rout), bn1.mean,
-                                      bn1.invstd, float(bn1.mod.eps), self._bn_fields(nxt, rout), st))
-                else:
-                    L.append(ops.call("fr_bn_finalize_res", self.part, np2, u.depth, self._bn_fields(bn2, rout), None, None,
-                                      0.0, None, st))
-                    d["om"] = torch.empty(B, 2, u.depth, device=self.device)
-                    xm = self.ubuf[i - 1]["om"] if edge_in == 2 else d["xm"]
-                    L.append(ops.call("fr_se_pool_parts_mlp_fwd_res", self.part, np2 // B, 3, bn2.scale, bn2.shift,
-                                      u.se.fc1.weight, u.se.fc2.weight, d["pooled"], d["hidden"], d["s"], B, u.Ho * u.Ho,
-                                      u.depth, u.se.fc1.out_channels, xm, d["om"], st))
-                    self._bn_train_launches(L, nxt, d["om"], B, rout)
-                x = d["out"]  # written by the next unit's conv1
-                continue
-            np2 = self._conv(L, src=d["y1"], w=wp2, out=d["y2"], B=B, RH=u.Ho, RW=u.Ho, SH=u.H, SW=u.H,
-                             SC=u.depth, N=u.depth, KH=3, KW=3, stride=u.stride, pad=1, mode=0, lda=u.depth,
-                             ldc=u.depth, pro=ops.PRO_PRELU, pro_a=u.prelu.weight, epi=stats_epi, part=stats_part)
-            self._bn_train_launches(L, bn2, self.part, np2, rout)
-            strips2 = self._last_conv_strips if not fold else 0  # conv2's partial rows, if they are whole strips of single images
-            if u.sc_conv is not None:
-                ws = self._conv_master(u.sc_conv)
-                if fr == FR_BF16:
-                    self._pack_reqs.append((ws, d["wpS"], d["wtS"], u.depth, 1, u.cin))
-                    wps = d["wpS"]
-                else:
-                    self._pack_reqs.append((ws, None, d["wtS"], u.depth, 1, u.cin))
-                    wps = ws
-                kws = dict(src=x, w=wps, out=d["yS"], B=B, RH=u.Ho, RW=u.Ho, SH=u.H, SW=u.H, SC=u.cin, N=u.depth, KH=1, KW=1,
-                           stride=u.stride, pad=0, mode=0, lda=u.cin, ldc=u.depth, pro=0, epi=stats_epi, part=stats_part)
-                nps = self._c1_parts(B, u.Ho, u.cin, u.depth, u.stride, u.H)
-                if nps:
-                    # Round 4: the convolved shortcut as a row-streaming GEMM with its weights in registers (conv1x1_stream.hip)
-                    L.append(ops.conv1x1_stream(st, **kws))
-                    self._bn_train_launches(L, d["bnS"], self.part, nps, rout)
-                else:
-                    L.append(ops.conv(st, fr, **kws))
-                    self._bn_train_launches(L, d["bnS"], self.part, (rout + 127) // 128, rout)
-            if u.se is not None:
-                R = u.se.fc1.out_channels
-                if strips2 and strips2 % B == 0 and u.sc_conv is None:
-                    # the squeeze from conv2's per-strip column sums (still in self.part): no pass over y2, and in the
-                    # same launch as the MLP
-                    L.append(ops.call("fr_se_pool_parts_mlp_fwd", self.part, strips2 // B, bn2.scale, bn2.shift,
-                                      u.se.fc1.weight, u.se.fc2.weight, d["pooled"], d["hidden"], d["s"], B,
-                                      u.Ho * u.Ho, u.depth, R, st))
-                else:
-                    L.append(ops.call("fr_se_pool", d["y2"], bn2.scale, bn2.shift, d["pooled"], B, u.Ho * u.Ho,
-                                      u.depth, fr, st))
-                    L.append(ops.call("fr_se_mlp_fwd", d["pooled"], u.se.fc1.weight, u.se.fc2.weight, d["hidden"],
-                                      d["s"], B, u.depth, R, st))
-            nb = ops.grid_blocks(rout, u.depth, fr)
-            kw = dict(x=d["y2"], out=d["out"], scale=bn2.scale, shift=bn2.shift, part=stats_part, B=B, H=u.Ho, W=u.Ho,
-                      C=u.depth, nblocks=nb)
-            if u.se is not None:
-                kw["se"] = d["s"]
-            if u.sc_conv is None:
-                kw.update(res=x, res_kind=1, res_stride=u.stride)
+            kws = dict(src=x, w=self._packed(u.sc_conv.weight, d, "S"), out=d["yS"], B=B, RH=u.Ho, RW=u.Ho, SH=u.H, SW=u.H,
+                       SC=u.cin, N=u.depth, KH=1, KW=1, stride=u.stride, pad=0, mode=0, lda=u.cin, ldc=u.depth, pro=0,
+                       epi=stats_epi, part=stats_part)
+            nps = self._c1_parts(B, u.Ho, u.cin, u.depth, u.stride, u.H)
+            if nps:
+                # Round 4: the convolved shortcut as a row-streaming GEMM with its weights in registers (conv1x1_stream.hip)
+                L.append(ops.conv1x1_stream(st, **kws))
+                self._bn_train_launches(L, bnS, self.part, nps, rout)
             else:
-                kw.update(res=d["yS"], res_kind=2, res_stride=1, rscale=d["bnS"].scale, rshift=d["bnS"].shift)
-            nxt = self.ubuf[i + 1]["bn1"] if i + 1 < len(self.units) else (None if self.body_only else self.bn_out)
-            if nxt is None:
-                kw["part"] = None  # nobody consumes the statistics of a bare stack's output
-            L.append(ops.bn_apply(st, fr, **kw))
-            if nxt is not None:
-                self._bn_train_launches(L, nxt, self.part, nb, rout)
-            x = d["out"]
-        if self.body_only:
-            self.feat = x
-            P.append(self._pack_launch())
-            if fold:
-                P.insert(0, self._eval_coeffs_launch())
-            self.pack_list, self.fwd_list = P, L
-            return
-        # ---- output layer: BN -> Dropout -> Flatten -> Linear(+bias) -> BN1d
-        ob, od, ol, ob1 = self.out
-        last = self.units[-1]
-        C = last.depth
+                L.append(ops.conv(st, fr, **kws))
+                self._bn_train_launches(L, bnS, self.part, (rout + 127) // 128, rout)
+        if u.se is not None:
+            R = u.se.fc1.out_channels
+            # conv2's partial rows, where a strip family ran it, are whole strips of single images, image-major
+            strips2 = 0 if self.fold or self._conv_route(c2)[0] == "igemm" else np2
+            if strips2 and strips2 % B == 0 and u.sc_conv is None:
+                # the squeeze from conv2's per-strip column sums (still in self.part): no pass over y2, and in the same
+                # launch as the MLP
+                L.append(ops.call("fr_se_pool_parts_mlp_fwd", self.part, strips2 // B, bn2.scale, bn2.shift,
+                                  u.se.fc1.weight, u.se.fc2.weight, d["pooled"], d["hidden"], d["s"], B, u.Ho * u.Ho,
+                                  u.depth, R, st))
+            else:
+                L.append(ops.call("fr_se_pool", d["y2"], bn2.scale, bn2.shift, d["pooled"], B, u.Ho * u.Ho, u.depth, fr,
+                                  st))
+                L.append(ops.call("fr_se_mlp_fwd", d["pooled"], u.se.fc1.weight, u.se.fc2.weight, d["hidden"], d["s"], B,
+                                  u.depth, R, st))
+        nb = ops.grid_blocks(rout, u.depth, fr)
+        kw = dict(x=d["y2"], out=d["out"], scale=bn2.scale, shift=bn2.shift, B=B, H=u.Ho, W=u.Ho, C=u.depth, nblocks=nb,
+                  part=stats_part if nxt is not None else None)  # nobody consumes the statistics of a bare stack's output
+        if u.se is not None:
+            kw["se"] = d["s"]
+        if u.sc_conv is None:
+            kw.update(res=x, res_kind=1, res_stride=u.stride)
+        else:
+            kw.update(res=d["yS"], res_kind=2, res_stride=1, rscale=bnS.scale, rshift=bnS.shift)
+        L.append(ops.bn_apply(st, fr, **kw))
+        if nxt is not None:
+            self._bn_train_launches(L, nxt, self.part, nb, rout)
+
+    def _fwd_output(self, P, L, x):
+        """The output layer on x, the last unit's output: BN -> Dropout -> Flatten -> Linear(+bias) -> BN1d."""
+        B, st, fr = self.B, self.stream, self.fr
+        ol, C = self.out[2], self.units[-1].depth
+        if self.lin_cm:
+            self.lin_splitk = int(_lib.lib.fr_linear_slices(512, self.feat_in))
+        else:
+            # split-K over 25088: every K slice stores its [B][512] partial (+ bias in slice 0) to its own slab and the
+            # slabs are added in a fixed order -- reproducible, unlike atomics, and the sums are formed in double
+            self.lin_splitk = max(1, min(64, self.feat_in // 32 // 16))
+        self.lin_slab = torch.empty(self.lin_splitk * B * 512, device=self.device)
         if self.lin_cm:
             drop = ops.call("fr_bn_dropout_cm", x, self.a, self.bn_out.scale, self.bn_out.shift, B, C, self.HWo, 0.0, 0, fr,
                             st)
-            L.append(drop)
-            self.l_drop_fwd = drop
-            self.lin_splitk = int(_lib.lib.fr_linear_slices(512, self.feat_in))
-            self.lin_slab = torch.empty(self.lin_splitk * B * 512, device=self.device)
-            L.append(ops.call("fr_linear_fwd", self.a, ol.weight, ol.bias, self.lin_slab, B, 512, self.feat_in,
-                              self.lin_splitk, st))
+            lin = ops.call("fr_linear_fwd", self.a, ol.weight, ol.bias, self.lin_slab, B, 512, self.feat_in, self.lin_splitk,
+                           st)
         else:
             P.append(ops.call("fr_permute_linear", ol.weight, self.Wlin, self.WlinT, 512, C, self.HWo, 0, fr, st))
-            drop = ops.call("fr_bn_dropout", x, self.a, self.bn_out.scale, self.bn_out.shift, B * self.HWo, C, self.HWo,
-                            0.0, 0, fr, st)
-            L.append(drop)
-            self.l_drop_fwd = drop
-            # split-K over 25088: every K slice stores its [B][512] partial (+ bias in slice 0) to its own slab and the
-            # slabs are added in a fixed order -- reproducible, unlike atomics, and the sums are formed in double
-            nk = self.feat_in // 32
-            self.lin_splitk = max(1, min(64, nk // 16))
-            self.lin_slab = torch.empty(self.lin_splitk * B * 512, device=self.device)
-            L.append(ops.conv(st, fr, src=self.a, w=self.Wlin, out=self.lin_slab, B=B, RH=1, RW=1, SH=1, SW=1,
-                              SC=self.feat_in, N=512, KH=1, KW=1, stride=1, pad=0, mode=0, lda=self.feat_in, ldc=512, pro=0,
-                              epi=ops.EPI_SLAB, out_f32=1, splitk=self.lin_splitk, bias=ol.bias))
+            drop = ops.call("fr_bn_dropout", x, self.a, self.bn_out.scale, self.bn_out.shift, B * self.HWo, C, self.HWo, 0.0,
+                            0, fr, st)
+            lin = ops.conv(st, fr, src=self.a, w=self.Wlin, out=self.lin_slab, B=B, RH=1, RW=1, SH=1, SW=1, SC=self.feat_in,
+                           N=512, KH=1, KW=1, stride=1, pad=0, mode=0, lda=self.feat_in, ldc=512, pro=0, epi=ops.EPI_SLAB,
+                           out_f32=1, splitk=self.lin_splitk, bias=ol.bias)
+        self._dropout_args.append((drop, 7))  # both dropout launches: p, seed = arguments 7, 8 (the 0.0, 0 above)
+        L += [drop, lin]
         L.append(ops.call("fr_reduce_parts", self.lin_slab, self.lin_splitk, 1, B * 512, self.f, None, None, st))
         nbf = ops.grid_blocks(B, 512, FR_F32)
-        if not fold:
+        if not self.fold:
             L.append(ops.call("fr_channel_stats", self.f, B, 512, self.part, nbf, FR_F32, st))
         self._bn_train_launches(L, self.bn1d, self.part, nbf, B)
-        L.append(ops.bn_apply(st, FR_F32, x=self.f, out=self.feat, scale=self.bn1d.scale, shift=self.bn1d.shift, B=B,
-                              H=1, W=1, C=512, res_kind=0, res_stride=1, nblocks=nbf))
+        L.append(ops.bn_apply(st, FR_F32, x=self.f, out=self.feat, scale=self.bn1d.scale, shift=self.bn1d.shift, B=B, H=1,
+                              W=1, C=512, res_kind=0, res_stride=1, nblocks=nbf))
+
+    def _place_packing(self, P):
+        """The weight-packing launch: on the side stream (pack_side), else at the end of the packing list -- behind the
+        launch that computes the eval coefficients the folded weights are scaled by."""
         if self.pack_side:
             pl = self._pack_launch(self.stream2)
             pl.tstream = self.stream2_t
             self.pack_side_list = [pl]
         else:
             P.append(self._pack_launch())
-        if fold:  # the coefficients feed the weight folding: first launch of the step
+        if self.fold:  # the coefficients feed the weight folding: first launch of the step
             P.insert(0, self._eval_coeffs_launch())
-        self.pack_list, self.fwd_list = P, L
 
     def _finish_pack(self):
         """Behind the forward AND backward lists: tell the packing launch which copies are read in fragment order."""
@@ -1100,7 +1103,7 @@ class BackbonePlan(object):
             # Linear data gradient (c-major) -> dropout backward + back to NHWC -> BN(out) backward
             L.append(ops.call("fr_linear_dgrad", gfT, ol.weight, self.g_cm, B, 512, self.feat_in, st))
             dropb = ops.call("fr_dropout_bwd_cm", self.g_cm, g_a, B, C, self.HWo, 0.0, 0, fr, st)
-            self._drop_bwd_idx = (5, 6)
+            self._dropout_args.append((dropb, 5))  # p, seed = arguments 5, 6 (the 0.0, 0 above)
         else:
             if glw is not None:
                 L.append(ops.call("fr_fill_rows", self.gWlin, None, 512, self.feat_in, st))
@@ -1112,9 +1115,8 @@ class BackbonePlan(object):
             L.append(ops.conv(st, fr, src=gfT, w=self.WlinT, out=g_a, B=B, RH=1, RW=1, SH=1, SW=1, SC=512, N=self.feat_in,
                               KH=1, KW=1, stride=1, pad=0, mode=0, lda=512, ldc=self.feat_in, pro=0, epi=ops.EPI_STORE))
             dropb = ops.call("fr_dropout_bwd", g_a, rows_o, C, self.HWo, 0.0, 0, fr, st)
-            self._drop_bwd_idx = (4, 5)
+            self._dropout_args.append((dropb, 4))  # p, seed = arguments 4, 5 (the 0.0, 0 above)
         L.append(dropb)
-        self.l_drop_bwd = dropb
         x_last = self.ubuf[-1]["out"]
         nb = ops.grid_blocks(rows_o, C, fr)
         db, dg = self._bn_grads(self.bn_out)
@@ -1364,8 +1366,7 @@ class BackbonePlan(object):
         # Round 6: the first unit's input gradient is read by exactly one kernel, the stem's backward sums, and both are
         # HBM-bound passes over 3.2 M rows x 64 channels: fr_stem_bwd_sums_from forms it on the way (bit-identical gx and
         # sums, 411 MB less traffic at batch 256)
-        if (i == 0 and not self.body_only and self.stem_recompute and fr == FR_BF16 and u.cin == 64 and
-                self.M0 < (1 << 24) and self.bn0.mod.training):
+        if i == 0 and self.stem_two_pass and u.cin == 64 and self.M0 < (1 << 24) and self.bn0.mod.training:
             # ... and x, the unit's input, is the stem's own output: recomputed from the rows instead of read (x = NULL)
             kw0 = dict(kw, x=None)
             self._unit0_apply = ops._fill(_lib.FrBnBwdArgs(), **kw0)
@@ -1383,7 +1384,8 @@ class BackbonePlan(object):
         return sums_left
 
     def _build_backward_stem(self, L, g_out, unit_done):
-        """Stem backward: z0 = PReLU(BN0(y0)); y0 = X0 * W0p^T.  g_out = dL/dz0."""
+        """Stem backward: z0 = PReLU(BN0(y0)); y0 = X0 * W0p^T.  g_out = dL/dz0.  A plan with a backward list never folds:
+        on the stem GEMM it is always the two-pass stem, which recomputes y0 instead of storing it."""
         fr, st = self.fr, self.stream
         sc, sb, sp = self.stem
         nb = ops.grid_blocks(self.M0, 64, fr)
@@ -1392,7 +1394,7 @@ class BackbonePlan(object):
         common = dict(g=g_out, x=self.y0, mean=self.bn0.mean, invstd=self.bn0.invstd, scale=self.bn0.scale,
                       shift=self.bn0.shift, slope=sp.weight, rows=self.M0, C=64, rows_per_image=self.S * self.S,
                       nblocks=nb)
-        if self.stem_recompute:  # the sums of fr_bn_bwd_reduce over (g, y0) with y0 recomputed from the rows
+        if self.stem_two_pass:  # the sums of fr_bn_bwd_reduce over (g, y0) with y0 recomputed from the rows
             nb = int(min(2048, (self.M0 + 63) // 64))
             if self._unit0_apply is not None:
                 L.append(ops.call("fr_stem_bwd_sums_from", self._unit0_apply, self.X0, self.W0p, self.bn0.mean,
@@ -1408,17 +1410,12 @@ class BackbonePlan(object):
         gw0 = self.grad_of(sc.weight)
         if gw0 is None:
             return
-        if self.use_stem_gemm:
+        if self.stem_two_pass:
             # BN0 backward is applied while the gradient rows are staged: g_y0 is never materialised
             nsl = int(min(1024 if self.K0 == 32 else 512, (self.M0 + 63) // 64))  # partials live in self.part
-            if self.stem_recompute:
-                L.append(ops.call("fr_stem_wgrad_bn_r", g_out, self.X0, self.W0p, self.bn0.mean, self.bn0.invstd,
-                                  self.bn0.scale, self.bn0.shift, sp.weight, sb.weight, s0, s1, 1.0 / self.M0,
-                                  self.part, self.M0, self.K0, nsl, st))
-            else:
-                L.append(ops.call("fr_stem_wgrad_bn", g_out, self.y0, self.X0, self.bn0.mean, self.bn0.invstd,
-                                  self.bn0.scale, self.bn0.shift, sp.weight, sb.weight, s0, s1, 1.0 / self.M0,
-                                  self.part, self.M0, self.K0, nsl, st))
+            L.append(ops.call("fr_stem_wgrad_bn_r", g_out, self.X0, self.W0p, self.bn0.mean, self.bn0.invstd,
+                              self.bn0.scale, self.bn0.shift, sp.weight, sb.weight, s0, s1, 1.0 / self.M0, self.part,
+                              self.M0, self.K0, nsl, st))
             L.append(ops.call("fr_reduce_parts", self.part, nsl, 1, 64 * self.K0, self.gW0p, None, None, st))
         else:  # the materialised stem-output gradient (fp32 path)
             if self.per_unit_sets:
@@ -1504,11 +1501,8 @@ class BackbonePlan(object):
         ops.call("fr_stem_im2col", x, avg, self.X0, B, S, S, self.in_channels, self.avg_channels, self.K0, self.fr, st)()
         od = self.out[1]
         p = float(od.p) if od.training else 0.0
-        self.l_drop_fwd.args[7] = p
-        self.l_drop_fwd.args[8] = seed
-        if not self.infer:
-            self.l_drop_bwd.args[self._drop_bwd_idx[0]] = p
-            self.l_drop_bwd.args[self._drop_bwd_idx[1]] = seed
+        for l, k in self._dropout_args:
+            l.args[k], l.args[k + 1] = p, seed
         ops.run(self.pack_list)
         ops.run(self.fwd_list)
         self.generation += 1
