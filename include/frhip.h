@@ -248,6 +248,19 @@ int fr_stem_wgrad(const void* G, const void* X, float* slab, long long M, int K,
 int fr_stem_wgrad_bn(const void* G, const void* Y, const void* X, const float* mean, const float* invstd,
                      const float* scale, const float* shift, const float* slope, const float* gamma, const float* s0,
                      const float* s1, float inv_count, float* slab, long long M, int K, int nblocks, void* stream);
+/* The data gradient of the same stem, for gradients with respect to the input images: G = dL/dz0 [M][64] (M = B*H*W rows of
+ * the im2col layout above, Ct = C + Cavg channels per tap), the BatchNorm / PReLU coefficients and s0 / s1 with the meaning
+ * they have for fr_stem_wgrad_bn_r (s0 = s1 = 0 in eval mode) ->
+ *   gx[b][c][h][w] = sum over (kh, kw) of (g_y * Wp)[(b, h-kh+1, w-kw+1)][(kh*3+kw)*Ct + c],  c < C only (the average-image
+ *   channels get none), taps outside the image dropped; written, not accumulated; fp32 NCHW [B][C][H][W].
+ * dtype FR_BF16: y = X * Wp^T recomputed from the rows (rounded as the forward pass rounded it) when Y is NULL, else read
+ * from Y; dtype FR_F32: Y (the stored stem output) is required.  Deterministic (no atomics).
+ * Replaces the autograd of input_layer = Conv2d -> BatchNorm2d -> PReLU (backbone/model_irse.py:140-142) with respect to
+ * its input. */
+int fr_stem_dgrad(const void* G, const void* X, const void* Y, const void* Wp, const float* mean, const float* invstd,
+                  const float* scale, const float* shift, const float* slope, const float* gamma, const float* s0,
+                  const float* s1, float inv_count, float* gx, int B, int H, int W, int C, int Ct, int K, int dtype,
+                  void* stream);
 
 /* ---- BatchNorm statistics (train mode; torch defaults eps 1e-5, momentum 0.1 -- SURVEY App. B 13)
  * part: [nparts][2][C] partial (sum, sum of squares) rows; count = elements per channel.
@@ -580,6 +593,10 @@ int fr_augment_u8(const uint8_t* src, const int32_t* xtab, const int32_t* ytab, 
 /* F.interpolate(x, size, mode='bilinear') of pSp.forward (backbone/restyle_psp.py:440-443: align_corners = False, no
  * antialias) on fp32 NCHW planes: in [planes][Hin][Win] -> out [planes][Hout][Wout]; planes = B * C <= 65535. */
 int fr_resize_bilinear(const float* in, float* out, int planes, int Hin, int Win, int Hout, int Wout, void* stream);
+/* Its adjoint: gin [planes][Hin][Win] = the gradient of fr_resize_bilinear's input for gout [planes][Hout][Wout]; a gather
+ * over the outputs each input pixel entered (no atomics).  Same argument checks as the forward.  Replaces the autograd of
+ * F.interpolate(..., mode='bilinear') in pSp.forward (backbone/restyle_psp.py:440-443). */
+int fr_resize_bilinear_bwd(const float* gout, float* gin, int planes, int Hin, int Win, int Hout, int Wout, void* stream);
 
 /* ---- multi-tensor SGD with momentum (torch.optim.SGD defaults; train.py:196)
  *   d = g + wd*p ; buf = momentum*buf + d ; p -= lr*buf      (buf starts at 0, so the first step gives buf = d)

@@ -59,6 +59,33 @@ class BackboneEncoderDiffHead(Module):
         return self._runner[0](x, avg_image)
 
 
+def _resize(xin, size):
+    """fr_resize_bilinear of a contiguous fp32 NCHW batch to size x size."""
+    from frhip import ops
+    x = torch.empty(xin.shape[0], xin.shape[1], size, size, device=xin.device)
+    ops.call("fr_resize_bilinear", xin, x, xin.shape[0] * xin.shape[1], xin.shape[2], xin.shape[3], size, size,
+             ops.current_stream_ptr())()
+    return x
+
+
+class _ResizeFn(torch.autograd.Function):
+    """The resize with its adjoint (fr_resize_bilinear_bwd) as the backward: gradients reach the caller's images."""
+
+    @staticmethod
+    def forward(ctx, xin, size):
+        ctx.in_hw = tuple(xin.shape[2:])
+        return _resize(xin, size)
+
+    @staticmethod
+    def backward(ctx, g):
+        from frhip import ops
+        g = g.contiguous().float()
+        gin = torch.empty(g.shape[0], g.shape[1], ctx.in_hw[0], ctx.in_hw[1], device=g.device)
+        ops.call("fr_resize_bilinear_bwd", g, gin, g.shape[0] * g.shape[1], gin.shape[2], gin.shape[3], g.shape[2],
+                 g.shape[3], ops.current_stream_ptr())()
+        return gin, None
+
+
 class pSp(nn.Module):
     def __init__(self, size=256, encoder_type="BackboneEncoder", checkpoint_path=None, avg_image=None,
                  num_diff_blocks=1, include_dropout=None, include_attblocks=None, attblock_init_strategy="ones",
@@ -123,11 +150,12 @@ class pSp(nn.Module):
         if x.size(2) != self.size:
             # F.interpolate(x, self.size, mode='bilinear') of the reference (:440-443), one HIP launch
             print('[interpolating ', x.size(2), ' to ', self.size, ']')
-            from frhip import _lib, ops
+            from frhip import _lib
             if not x.is_cuda:
                 raise _lib.FrhipError("frhip: pSp runs on the HIP path only -- got a %s tensor" % x.device)
             xin = x.contiguous().float()
-            x = torch.empty(xin.shape[0], xin.shape[1], self.size, self.size, device=xin.device)
-            ops.call("fr_resize_bilinear", xin, x, xin.shape[0] * xin.shape[1], xin.shape[2], xin.shape[3], self.size,
-                     self.size, ops.current_stream_ptr())()
+            if torch.is_grad_enabled() and xin.requires_grad:
+                x = _ResizeFn.apply(xin, self.size)
+            else:
+                x = _resize(xin, self.size)
         return self.encoder(x, races=races, avg_image=self.avg_image)

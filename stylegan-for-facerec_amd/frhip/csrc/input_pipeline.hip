@@ -114,3 +114,65 @@ extern "C" int fr_resize_bilinear(const float* in, float* out, int planes, int H
                      out, Hin, Win, Hout, Wout, sh, sw);
   FR_LAUNCH_CHECK();
 }
+
+// ------------------------------------------------------------------------------------------ ... and its adjoint
+// gin[plane][iy][ix] = sum over (oy, ox) of gout[plane][oy][ox] * wy(oy, iy) * wx(ox, ix), the weights with which input
+// (iy, ix) entered output (oy, ox) above.  A gather, one thread per INPUT pixel: the outputs that read input index i along
+// an axis are those whose first tap is i - 1 or i (the first tap is non-decreasing in the output index), found by stepping
+// from a lower estimate; fixed summation order, no atomics.
+namespace {
+struct Taps {
+  int i0, i1;
+  float w0, w1;
+};
+__device__ __forceinline__ Taps bilinear_taps(int o, float s, int n) {  // resize_bilinear_kernel's expressions
+  float f = s * ((float)o + 0.5f) - 0.5f;
+  f = f < 0.f ? 0.f : f;
+  const int i0 = (int)f;
+  const float l = f - (float)i0;
+  return {i0, i0 + (i0 < n - 1 ? 1 : 0), 1.f - l, l};
+}
+__device__ __forceinline__ float tap_weight(const Taps& t, int i) {
+  return (t.i0 == i ? t.w0 : 0.f) + (t.i1 == i ? t.w1 : 0.f);
+}
+__device__ __forceinline__ int first_reader(int i, float s, int n_in, int n_out) {  // smallest o with first tap >= i - 1
+  int o = (int)floorf(((float)i - 0.5f) / s - 0.5f) - 2;
+  o = o < 0 ? 0 : o;
+  while (o < n_out && bilinear_taps(o, s, n_in).i0 < i - 1) ++o;
+  return o;
+}
+
+__global__ __launch_bounds__(256) void resize_bilinear_bwd_kernel(const float* __restrict__ gout, float* __restrict__ gin,
+                                                                  int Hin, int Win, int Hout, int Wout, float sh, float sw) {
+  const int pix = blockIdx.x * 256 + threadIdx.x;
+  if (pix >= Hin * Win) return;
+  const int iy = pix / Win, ix = pix - iy * Win;
+  const float* pl = gout + (size_t)blockIdx.y * Hout * Wout;
+  const int ox0 = first_reader(ix, sw, Win, Wout);
+  float acc = 0.f;
+  for (int oy = first_reader(iy, sh, Hin, Hout); oy < Hout; ++oy) {
+    const Taps ty = bilinear_taps(oy, sh, Hin);
+    if (ty.i0 > iy) break;
+    const float wy = tap_weight(ty, iy);
+    float row = 0.f;
+    for (int ox = ox0; ox < Wout; ++ox) {
+      const Taps tx = bilinear_taps(ox, sw, Win);
+      if (tx.i0 > ix) break;
+      row = fmaf(tap_weight(tx, ix), pl[(size_t)oy * Wout + ox], row);
+    }
+    acc = fmaf(wy, row, acc);
+  }
+  gin[(size_t)blockIdx.y * Hin * Win + pix] = acc;
+}
+}  // namespace
+
+extern "C" int fr_resize_bilinear_bwd(const float* gout, float* gin, int planes, int Hin, int Win, int Hout, int Wout,
+                                      void* stream) {
+  if (planes < 1 || Hin < 1 || Win < 1 || Hout < 1 || Wout < 1 || planes > 65535)
+    FR_UNSUPPORTED("fr_resize_bilinear_bwd: planes in 1..65535 and positive sizes");
+  if (!gout || !gin) FR_UNSUPPORTED("fr_resize_bilinear_bwd: gout and gin are required");
+  const float sh = (float)Hin / (float)Hout, sw = (float)Win / (float)Wout;
+  hipLaunchKernelGGL(resize_bilinear_bwd_kernel, dim3((Hin * Win + 255) / 256, planes), dim3(256), 0, (hipStream_t)stream,
+                     gout, gin, Hin, Win, Hout, Wout, sh, sw);
+  FR_LAUNCH_CHECK();
+}

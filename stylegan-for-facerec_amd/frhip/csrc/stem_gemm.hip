@@ -652,6 +652,211 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const bf16_t* __restric
     for (int r = 0; r < 4; ++r) o[(size_t)(wave * 16 + lq * 4 + r) * K + k * 16 + li] = acc[k][r];
 }
 
+
+// ------------------------------------------------------------------------------------------ data gradient (input images)
+// gx[b][c][h][w] = dL/dx for the image channels c < C of the stem input (the average-image channels of pSp get none):
+//   g' = G * prelu'(u), u = y*scale + shift;  g_y = gamma*invstd*(g' - s0/M - (y - mean)*invstd*s1/M)  (s0 = s1 = 0 in eval)
+//   gX = g_y * Wp  [M][K];  gx[b][c][h][w] = sum over the taps (kh, kw) of gX[(b, h-kh+1, w-kw+1)][(kh*3+kw)*Ct + c]
+// A workgroup walks a band of RB image rows of one column segment of one image.  Per SOURCE row (the band's rows plus a
+// one-row halo above and below) its four waves form gX for the segment's pixels plus a one-pixel halo, 16 pixels per tile:
+// y recomputed from the rows (MFMA 1, K deep) -- or read (RY) --, g_y in registers, gX = g_y * Wp (MFMA 2, 64 deep) into a
+// three-row fp32 ring in LDS.  Behind each source row the finished output row is gathered from the ring (col2im: the nine
+// taps in a fixed order, no atomics) and stored along w.  Only the halo rows are formed twice: (RB + 2) / RB.
+// MFMA 1 runs on a permuted channel order: A-tile j row i is channel 16*(i>>2) + 4j + (i&3), so that a lane's accumulators
+// hold the 16 consecutive channels 16*fq .. +15 of its pixel -- the 32 contiguous bytes of G it loads -- and, in that order,
+// the two 32-deep B operands of MFMA 2 (step s: channels 16*fq + 8s .. +7) with no lane movement.
+struct StemDgrad {
+  const float *scale, *shift, *slope, *mean, *invstd, *gamma, *s0, *s1;
+  float inv_count;
+  int B, H, W, C, Ct;
+  int WS, nseg, RB, nband;  // column segment width, segments per image row, image rows per band, bands per image
+};
+
+template <int K, bool RY>
+__global__ __launch_bounds__(256) void stem_dgrad_kernel(const bf16_t* __restrict__ G, const bf16_t* __restrict__ X,
+                                                         const bf16_t* __restrict__ Y, const bf16_t* __restrict__ Wp,
+                                                         float* __restrict__ gx, const StemDgrad a) {
+  constexpr int KS = K / 32;
+  constexpr int NT = K == 32 ? 2 : 1;  // 16-pixel tiles per wave and source row
+  constexpr int SP = 4 * NT * 16;      // pixel slots of a ring row (>= segment width + 2)
+  constexpr int KP = K + 1;            // odd row stride: the gather's lanes (consecutive pixels) hit distinct banks
+  __shared__ float ring[3 * SP * KP];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int fr = lane & 15, fq = lane >> 4;
+  int bid = blockIdx.x;
+  const int seg = bid % a.nseg;
+  bid /= a.nseg;
+  const int band = bid % a.nband, b = bid / a.nband;
+  const int w0 = seg * a.WS, h0 = band * a.RB;
+  const int ws = min(a.WS, a.W - w0), hend = min(h0 + a.RB, a.H);
+  const int npx = ws + 2;
+  const int H = a.H, W = a.W;
+  s16x8 wf[4][RY ? 1 : KS];
+  if (!RY) {
+    const int ch = 16 * (fr >> 2) + (fr & 3);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int kk = 0; kk < KS; ++kk)
+        wf[j][kk] = *reinterpret_cast<const s16x8*>(Wp + (size_t)(ch + 4 * j) * K + kk * 32 + fq * 8);
+  }
+  s16x8 wt[K / 16][2];  // MFMA 2's A operand: row kt*16 + fr of Wp^T, element e of step s = channel 16*fq + 8s + e
+#pragma unroll
+  for (int kt = 0; kt < K / 16; ++kt)
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) wt[kt][s][e] = (short)Wp[(size_t)(16 * fq + 8 * s + e) * K + kt * 16 + fr];
+  float sc[16], sh[16], sl[16], cA[16], cB[16], cD[16];  // g_y = cA*g' - cB*y + cD
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    const int n = 16 * fq + q;
+    const float is = a.invstd[n];
+    sc[q] = a.scale[n];
+    sh[q] = a.shift[n];
+    sl[q] = a.slope[n];
+    cA[q] = a.gamma[n] * is;
+    cB[q] = cA[q] * is * (a.s1[n] * a.inv_count);
+    cD[q] = cB[q] * a.mean[n] - cA[q] * (a.s0[n] * a.inv_count);
+  }
+  s16x8 xf[NT][RY ? 1 : KS];
+  U128 gv[NT][2], yv[NT][RY ? 2 : 1];
+  bool ok[NT];
+  auto load = [&](int sr) {
+#pragma unroll
+    for (int u = 0; u < NT; ++u) {
+      const int p = (wave * NT + u) * 16 + fr, wc = w0 - 1 + p;
+      ok[u] = p < npx && (unsigned)sr < (unsigned)H && (unsigned)wc < (unsigned)W;
+      const size_t m = ((size_t)b * H + (ok[u] ? sr : 0)) * W + (ok[u] ? wc : 0);
+#pragma unroll
+      for (int v = 0; v < 2; ++v) {
+        gv[u][v] = zero16();
+        if (ok[u]) gv[u][v] = ld16(G + m * SN + 16 * fq + 8 * v);
+        if (RY) {
+          yv[u][v] = zero16();
+          if (ok[u]) yv[u][v] = ld16(Y + m * SN + 16 * fq + 8 * v);
+        }
+      }
+      if (!RY) {
+#pragma unroll
+        for (int kk = 0; kk < KS; ++kk) {
+          xf[u][kk] = (s16x8){0, 0, 0, 0, 0, 0, 0, 0};
+          if (ok[u]) xf[u][kk] = *reinterpret_cast<const s16x8*>(X + m * K + kk * 32 + fq * 8);
+        }
+      }
+    }
+  };
+  load(h0 - 1);
+  for (int sr = h0 - 1; sr <= hend; ++sr) {
+    float* slot = ring + ((sr + 3) % 3) * SP * KP;
+#pragma unroll
+    for (int u = 0; u < NT; ++u) {
+      float y[16], g[16];
+      if (RY) {
+        unpack16<bf16_t>(yv[u][0], y);
+        unpack16<bf16_t>(yv[u][1], y + 8);
+      } else {
+        f32x4 acc[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kk = 0; kk < KS; ++kk)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j][kk], xf[u][kk], acc[j], 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)  // rounded as the forward pass rounded y
+#pragma unroll
+          for (int r = 0; r < 4; ++r) y[4 * j + r] = bf2f(f2bf(acc[j][r]));
+      }
+      unpack16<bf16_t>(gv[u][0], g);
+      unpack16<bf16_t>(gv[u][1], g + 8);
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const float uu = fmaf(y[q], sc[q], sh[q]);
+        const float gp = uu > 0.f ? g[q] : g[q] * sl[q];
+        g[q] = fmaf(cA[q], gp, fmaf(-cB[q], y[q], cD[q]));
+      }
+      const U128 b0 = pack16<bf16_t>(g), b1 = pack16<bf16_t>(g + 8);
+      const s16x8 gb0 = __builtin_bit_cast(s16x8, b0), gb1 = __builtin_bit_cast(s16x8, b1);
+      float* row = slot + ((wave * NT + u) * 16 + fr) * KP + 4 * fq;
+#pragma unroll
+      for (int kt = 0; kt < K / 16; ++kt) {
+        f32x4 d = (f32x4){0.f, 0.f, 0.f, 0.f};
+        d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wt[kt][0], gb0, d, 0, 0, 0);
+        d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wt[kt][1], gb1, d, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) row[kt * 16 + r] = ok[u] ? d[r] : 0.f;  // pixels outside the image add nothing
+      }
+    }
+    if (sr < hend) load(sr + 1);  // in flight across the gather below
+    __syncthreads();
+    const int orow = sr - 1;
+    if (orow >= h0) {
+      for (int i = tid; i < a.C * ws; i += 256) {
+        const int c = i / ws, cw = i - c * ws;
+        float s = 0.f;
+#pragma unroll
+        for (int kh = 0; kh < 3; ++kh) {
+          const float* src = ring + ((orow - kh + 4) % 3) * SP * KP;
+#pragma unroll
+          for (int kw = 0; kw < 3; ++kw) s += src[(cw - kw + 2) * KP + (kh * 3 + kw) * a.Ct + c];
+        }
+        gx[(((size_t)b * a.C + c) * H + orow) * W + w0 + cw] = s;
+      }
+    }
+    __syncthreads();  // the next source row overwrites the ring row of sr - 2
+  }
+}
+
+// fp32 path: y is stored by the forward pass (fr_conv_igemm over the same rows), so it is read; one thread per output pixel
+// forms g_y for the nine neighbours and contracts it with Wp from LDS.  Same expression, summation in a fixed order.
+template <int K>
+__global__ __launch_bounds__(256) void stem_dgrad_f32_kernel(const float* __restrict__ G, const float* __restrict__ Y,
+                                                             const float* __restrict__ Wp, float* __restrict__ gx,
+                                                             const StemDgrad a) {
+  __shared__ float ws[SN * K];
+  __shared__ float cf[6][SN];
+  for (int i = threadIdx.x; i < SN * K; i += 256) ws[i] = Wp[i];
+  if (threadIdx.x < SN) {
+    const int n = threadIdx.x;
+    const float is = a.invstd[n], ca = a.gamma[n] * is, cb = ca * is * (a.s1[n] * a.inv_count);
+    cf[0][n] = a.scale[n];
+    cf[1][n] = a.shift[n];
+    cf[2][n] = a.slope[n];
+    cf[3][n] = ca;
+    cf[4][n] = cb;
+    cf[5][n] = cb * a.mean[n] - ca * (a.s0[n] * a.inv_count);
+  }
+  __syncthreads();
+  const int H = a.H, W = a.W;
+  const long long pix = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (pix >= (long long)a.B * H * W) return;
+  const int w = (int)(pix % W), h = (int)((pix / W) % H), b = (int)(pix / ((long long)W * H));
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int tap = 0; tap < 9; ++tap) {
+    const int sh = h - tap / 3 + 1, sw = w - tap % 3 + 1;
+    if ((unsigned)sh >= (unsigned)H || (unsigned)sw >= (unsigned)W) continue;
+    const size_t m = ((size_t)b * H + sh) * W + sw;
+    const float* wk = ws + tap * a.Ct;
+    for (int n0 = 0; n0 < SN; n0 += 4) {
+      float y[4], g[4];
+      unpack16<float>(ld16(Y + m * SN + n0), y);
+      unpack16<float>(ld16(G + m * SN + n0), g);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int n = n0 + q;
+        const float uu = fmaf(y[q], cf[0][n], cf[1][n]);
+        const float gp = uu > 0.f ? g[q] : g[q] * cf[2][n];
+        const float gy = fmaf(cf[3][n], gp, fmaf(-cf[4][n], y[q], cf[5][n]));
+#pragma unroll
+        for (int c = 0; c < 8; ++c)
+          if (c < a.C) acc[c] = fmaf(gy, wk[n * K + c], acc[c]);
+      }
+    }
+  }
+  for (int c = 0; c < a.C; ++c) gx[(((size_t)b * a.C + c) * H + h) * W + w] = acc[c];
+}
+
 }  // namespace
 
 extern "C" int fr_stem_gemm(const void* X, const void* Wp, void* out, float* part, long long M, int K, int nblocks,
@@ -798,5 +1003,50 @@ extern "C" int fr_stem_wgrad_bn(const void* G, const void* Y, const void* X, con
   else
     hipLaunchKernelGGL((stem_wgrad_kernel<64, true>), dim3(nblocks), dim3(256), 0, st, (const bf16_t*)G, (const bf16_t*)X,
                        slab, (int)M, bn);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_stem_dgrad(const void* G, const void* X, const void* Y, const void* Wp, const float* mean,
+                             const float* invstd, const float* scale, const float* shift, const float* slope,
+                             const float* gamma, const float* s0, const float* s1, float inv_count, float* gx, int B, int H,
+                             int W, int C, int Ct, int K, int dtype, void* stream) {
+  if (K != 32 && K != 64) FR_UNSUPPORTED("fr_stem_dgrad: K must be 32 or 64");
+  if (Ct < 1 || 9 * Ct > K || C < 1 || C > Ct) FR_UNSUPPORTED("fr_stem_dgrad: need 1 <= C <= Ct and 9 * Ct <= K");
+  if (B < 1 || H < 1 || W < 1 || (long long)B * H * W >= (1ll << 31) - 64)
+    FR_UNSUPPORTED("fr_stem_dgrad: need positive B, H, W with 0 < M = B*H*W < 2^31 - 64");
+  if (dtype != FR_F32 && dtype != FR_BF16) FR_UNSUPPORTED("fr_stem_dgrad: dtype must be FR_F32 or FR_BF16");
+  if (!G || !Wp || !gx || !mean || !invstd || !scale || !shift || !slope || !gamma || !s0 || !s1)
+    FR_UNSUPPORTED("fr_stem_dgrad: G, Wp, gx and every BatchNorm / PReLU coefficient vector are required");
+  if (dtype == FR_F32 ? !Y : (!Y && !X)) FR_UNSUPPORTED("fr_stem_dgrad: fp32 needs Y; bf16 needs X (recompute) or Y");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  StemDgrad a = {scale, shift, slope, mean, invstd, gamma, s0, s1, inv_count, B, H, W, C, Ct, 0, 0, 0, 0};
+  if (dtype == FR_F32) {
+    const long long nb = ((long long)B * H * W + 255) / 256;
+    if (K == 32)
+      hipLaunchKernelGGL((stem_dgrad_f32_kernel<32>), dim3((unsigned)nb), dim3(256), 0, st, (const float*)G, (const float*)Y,
+                         (const float*)Wp, gx, a);
+    else
+      hipLaunchKernelGGL((stem_dgrad_f32_kernel<64>), dim3((unsigned)nb), dim3(256), 0, st, (const float*)G, (const float*)Y,
+                         (const float*)Wp, gx, a);
+    FR_LAUNCH_CHECK();
+  }
+  const int wmax = K == 32 ? 126 : 62;  // a ring row holds 128 / 64 pixels: segment + two halo pixels
+  a.nseg = (W + wmax - 1) / wmax;
+  a.WS = (W + a.nseg - 1) / a.nseg;
+  a.RB = H < 16 ? H : 16;
+  a.nband = (H + a.RB - 1) / a.RB;
+  const long long nb = (long long)B * a.nband * a.nseg;
+  if (nb >= (1ll << 31)) FR_UNSUPPORTED("fr_stem_dgrad: too many workgroups");
+#define DGRAD(KK, RYY)                                                                                                 \
+  hipLaunchKernelGGL((stem_dgrad_kernel<KK, RYY>), dim3((unsigned)nb), dim3(256), 0, st, (const bf16_t*)G,              \
+                     (const bf16_t*)X, (const bf16_t*)Y, (const bf16_t*)Wp, gx, a)
+  if (K == 32) {
+    if (Y) DGRAD(32, true);
+    else DGRAD(32, false);
+  } else {
+    if (Y) DGRAD(64, true);
+    else DGRAD(64, false);
+  }
+#undef DGRAD
   FR_LAUNCH_CHECK();
 }

@@ -21,6 +21,7 @@ which they become ready (output layer first, stem last) so that data-parallel bu
 """
 import ctypes
 import os
+import weakref
 
 import torch
 import torch.nn as nn
@@ -292,6 +293,8 @@ class BackbonePlan(object):
         # folded inference plan keeps y0 on the stem GEMM; a plan with a backward list never folds.
         self.stem_two_pass = self.use_stem_gemm and not self.fold
         self.slab, self._slab_users = None, []
+        self.input_grad_list = None  # run_input_grad: built on first use
+        self.awaiting = None  # weak reference to the autograd context of a forward whose backward has not run
         # deferred slab sums (FrWgradArgs.defer / prev_*): a weight-gradient launch that supports it leaves the sum of its
         # slabs to the NEXT such launch of the side stream (two slab buffers alternate); fr_reduce_slabs flushes the last
         self.slab2, self._slab2_users, self._slab_flip = None, [], 0
@@ -1136,6 +1139,7 @@ class BackbonePlan(object):
         unit_done = {}  # unit index -> event recorded on the side stream after its weight gradients
         sums_left = 0  # rows of BN2-backward sums the previous launch left in self.part (0: none)
         self._unit0_apply = None
+        self._unit0_held = []
         for i in range(len(self.units) - 1, -1, -1):
             u, d = self.units[i], self.ubuf[i]
             x = self.ubuf[i - 1]["out"] if i > 0 else self.z0
@@ -1157,6 +1161,12 @@ class BackbonePlan(object):
             cur = 1 - cur
             g_x = self.g_pp[cur][:self.B * u.H * u.H * u.cin]
             sums_left = self._bwd_bn1(L, i, g_xh, g_x, x, g_out, g_xS, db, dg)
+            if i == 0 and self._unit0_apply is not None:
+                # the fused launch in the stem's backward still reads this BatchNorm's gradients (its s0 / s1): they are
+                # announced with the stem, so that no readiness callback rewrites them (an all-reduce) before that read
+                held = [u.bn1.weight, u.bn1.bias]
+                ready = [p for p in ready if all(p is not q for q in held)]
+                self._unit0_held = held
             done = None
             if self.dual:
                 done = torch.cuda.Event()
@@ -1183,7 +1193,7 @@ class BackbonePlan(object):
             L.append(_EvWait(self.stream1_t, unit_done[min(unit_done)]))  # join: the side stream is FIFO
         if not self.body_only:
             sc, sb, sp = self.stem
-            self.ready_marks.append((len(L), [sb.weight, sb.bias, sp.weight, sc.weight] + tail_ready, None))
+            self.ready_marks.append((len(L), self._unit0_held + [sb.weight, sb.bias, sp.weight, sc.weight] + tail_ready, None))
         self._order_ready_marks()
         self.bwd_list = L
 
@@ -1388,6 +1398,7 @@ class BackbonePlan(object):
         on the stem GEMM it is always the two-pass stem, which recomputes y0 instead of storing it."""
         fr, st = self.fr, self.stream
         sc, sb, sp = self.stem
+        self.g_stem = g_out  # dL/dz0, which run_input_grad reads after this list
         nb = ops.grid_blocks(self.M0, 64, fr)
         db, dg = self._bn_grads(self.bn0)
         gsl = self.grad_of(sp.weight)
@@ -1407,6 +1418,7 @@ class BackbonePlan(object):
             L.append(ops.bn_bwd_reduce(st, fr, part=self.part, **common))
         self._reduce(L, nb, 3, 64, db, dg, gsl if gsl is not None else self.sums[2, :64])
         s0, s1 = self._s01(self.bn0, db, dg)
+        self.stem_s01 = (s0, s1)
         gw0 = self.grad_of(sc.weight)
         if gw0 is None:
             return
@@ -1508,7 +1520,8 @@ class BackbonePlan(object):
         self.generation += 1
         return self.feat
 
-    def run_backward(self, g_feat, on_ready=None):
+    def run_backward(self, g_feat, on_ready=None, input_grad=False):
+        """Parameter gradients into the arena views; with input_grad, returns dL/dx (run_input_grad) as well."""
         self.g_feat_in.copy_(g_feat)
         # frhip.optim's zero_grad() has just cleared the arena with one fill and says so: do not fill 174 MB twice
         if not getattr(self.arena, "_frhip_zeroed", False):
@@ -1521,7 +1534,7 @@ class BackbonePlan(object):
                 p.grad = v
         if on_ready is None:
             ops.run(self.bwd_list)
-            return
+            return self.run_input_grad() if input_grad else None
         # Readiness callbacks (gradient all-reduce): host bookkeeping only.  A callee that enqueues a collective first calls
         # comm_fence(), which orders the communication stream behind the main stream up to this point and behind the side
         # stream's weight gradients of the units announced so far -- the main stream itself never waits for the side stream
@@ -1531,16 +1544,52 @@ class BackbonePlan(object):
         if self.comm_stream_t is None:
             self.comm_stream_t = _side_stream(self.device, -1)  # one communication stream per device, too
             self.comm_events = [torch.cuda.Event() for _ in self.ready_marks]
-        pos, last_done = 0, None
+        pos, last_done, gx = 0, None, None
         for k, (end, params, done) in enumerate(self.ready_marks):
             ops.run(self.bwd_list[pos:end])
             pos = end
+            if input_grad and gx is None and end == len(self.bwd_list):
+                # before the stem's BatchNorm gradients are announced: in train mode s0 / s1 ARE those gradients, and a
+                # callback's in-place all-reduce of them is ordered behind the main stream only up to its fence
+                gx = self.run_input_grad()
             if done is not None:
                 last_done = done  # the side stream is FIFO: the latest event is behind every earlier unit's weight gradients
             self._fence_at = (k, last_done)
             on_ready([p for p in params if p.requires_grad])
         ops.run(self.bwd_list[pos:])
+        if input_grad and gx is None:
+            gx = self.run_input_grad()
         self.stream1_t.wait_stream(self.comm_stream_t)  # whatever the callbacks enqueued themselves (not the async collectives)
+        return gx
+
+    def run_input_grad(self):
+        """dL/dx for the image channels, fp32 [B, C, S, S], from the stem-output gradient dL/dz0 the backward list just left
+        in self.g_stem; run right behind run_backward, on the same stream.  Its launch list is built the first time a backward
+        asks for input gradients and only ever runs for those calls: fwd_list, bwd_list and pack_list are the same with and
+        without it.
+
+        What it reads stays valid until it runs.  g_stem is the input gradient of the first residual unit (written by
+        fr_bn_bwd_apply or, bf16 train mode, by fr_stem_bwd_sums_from); behind that launch the main stream only reads it (the
+        stem's sums and weight gradient; the fp32 path materialises g_y0 in another buffer) and the side stream's weight
+        gradients never write the unit gradients g_pp.  s0 / s1 are reduced by the stem's backward sums before the early return
+        of a frozen stem weight; nothing behind them on the main stream writes those targets (in train mode they are the BN0
+        parameter gradients: run_backward runs this before readiness callbacks see them)."""
+        if self.input_grad_list is None:
+            sc, sb, sp = self.stem
+            s0, s1 = self.stem_s01
+            two_pass = self.stem_two_pass
+            dgrad = ops.call(
+                "fr_stem_dgrad", self.g_stem, self.X0 if two_pass else None, None if two_pass else self.y0, self.W0p,
+                self.bn0.mean, self.bn0.invstd, self.bn0.scale, self.bn0.shift, sp.weight, sb.weight, s0, s1, 1.0 / self.M0,
+                None, self.B, self.S, self.S, self.in_channels, self.in_channels + self.avg_channels, self.K0, self.fr,
+                self.stream)
+            self.input_grad_list = [dgrad]
+            self._gx_slot = (dgrad, _lib.protos["fr_stem_dgrad"][2].index("gx"))  # the output pointer, set per call
+        gx = torch.empty(self.B, self.in_channels, self.S, self.S, device=self.device)
+        launch, k = self._gx_slot
+        launch.args[k] = ops.ptr(gx)  # a fresh tensor per call: the caller owns it
+        ops.run(self.input_grad_list)
+        return gx
 
     def comm_fence(self):
         """Called from inside a readiness callback: orders the communication stream behind every gradient announced so far
@@ -1565,6 +1614,7 @@ class _BackboneFn(torch.autograd.Function):
         ctx.runner = runner
         ctx.plan = runner.plan
         ctx.generation = runner.plan.generation
+        runner.plan.awaiting = weakref.ref(ctx)  # a forward whose backward has not run yet (BackboneRunner._free_plan)
         return feats.clone()
 
     @staticmethod
@@ -1573,8 +1623,9 @@ class _BackboneFn(torch.autograd.Function):
         if plan.generation != ctx.generation:
             raise RuntimeError("frhip: the backbone ran another forward before this backward; the activation "
                                "buffers of the static plan hold one step at a time")
-        plan.run_backward(g.contiguous().float(), ctx.runner.on_grads_ready)
-        return (None, None) + (None,) * (len(ctx.needs_input_grad) - 2)
+        gx = plan.run_backward(g.contiguous().float(), ctx.runner.on_grads_ready, input_grad=ctx.needs_input_grad[1])
+        plan.awaiting = None
+        return (None, gx) + (None,) * (len(ctx.needs_input_grad) - 2)
 
 
 class BackboneRunner(object):
@@ -1600,9 +1651,24 @@ class BackboneRunner(object):
             self.plans = {key: plan}  # one live plan: activations of a 256-batch are several GB
         return plan
 
-    def _forward_impl(self, x, infer=False):
+    def _free_plan(self, x):
+        """The live plan with a backward list when a forward without gradients may run on it: same batch, dtype, device and
+        stem, current stream and parameters, and no forward of it still waiting for its backward (a forward would overwrite
+        the activations that backward reads).  None otherwise."""
+        plan = self.plan
+        if plan is None or plan.infer:
+            return None
         avg = self._avg
-        self.plan = self._get_plan(x, 0 if avg is None else avg.shape[0], infer)
+        dtype = self.compute_dtype or getattr(self.module, "compute_dtype", None) or compute_dtype_default()
+        key = (x.shape[0], dtype, x.device, 0 if avg is None else avg.shape[0], self.single_stream, False)
+        if self.plans.get(key) is not plan or not plan.check_current():
+            return None
+        waiting = plan.awaiting() if plan.awaiting is not None else None
+        return plan if waiting is None else None
+
+    def _forward_impl(self, x, infer=False, plan=None):
+        avg = self._avg
+        self.plan = plan or self._get_plan(x, 0 if avg is None else avg.shape[0], infer)
         self.step_seed = (self.step_seed * 6364136223846793005 + 1442695040888963407) % (1 << 64)
         return self.plan.run_forward(x, avg, self.step_seed)
 
@@ -1622,8 +1688,6 @@ class BackboneRunner(object):
             raise _lib.FrhipError("frhip: the backbone runs on the HIP path only -- got a %s tensor. Move the "
                                   "model and batch to a ROCm device (the CPU restatement is oracle/, for tests)."
                                   % x.device)
-        if x.requires_grad:
-            raise NotImplementedError("frhip: gradients with respect to the input images are not implemented")
         x = x.contiguous().float()
         S = self.module.input_size if isinstance(self.module.input_size, int) else self.module.input_size[0]
         if x.shape[2] != S or x.shape[3] != S:
@@ -1641,8 +1705,14 @@ class BackboneRunner(object):
             raise RuntimeError("frhip: the stem expects %d input channels, got %d from the batch%s" % (
                 self.in_channels, x.shape[1], "" if self._avg is None else " + %d from avg_image" % self._avg.shape[0]))
         params = [p for p in self.module.parameters()]
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+        trains = any(p.requires_grad for p in params)
+        if torch.is_grad_enabled() and (x.requires_grad or trains):
             return _BackboneFn.apply(self, x, *params)
+        # every parameter frozen (an identity loss: calls with and without input gradients alternate): a forward without
+        # gradients runs on the plan the calls with them built instead of replacing it by a forward-only plan
+        free = None if trains else self._free_plan(x)
+        if free is not None:
+            return self._forward_impl(x, plan=free).clone()
         return self._forward_impl(x, infer=True).clone()  # forward-only plan (BatchNorm folded when in eval mode)
 
 
