@@ -11,7 +11,9 @@ GPU, bf16 storage / fp32 accumulate.  A step = forward, margin head, loss, top-1
 all-reduce (N > 1), optimizer step -- everything the reference loop does per iteration (train.py:287-316) except
 its three host syncs.  Rank 0 prints ONE JSON line.
 
-Besides the contract fields the line carries
+A plain run does only what the headline needs: set up, warm up, time the K steps, write --dump-outputs, print the line.
+Everything else it can measure runs only with ``--full`` (each part can be left out with its ``--no-*`` option); with it
+the line also carries
   roofline      dominant kernel FAMILY (by time; prologue variants of one template counted together) of one
                 event-instrumented step after the timed region: algorithmic FLOPs of its launches / their summed
                 duration, against the dense bf16 MFMA peak (2.5 PFLOP/s, MI355X_MICROARCH.md); ``all_mfma`` = the same
@@ -21,6 +23,9 @@ Besides the contract fields the line carries
                 dominant family from the committed rocprofv3 --pmc passes (the newest profiles/rNN_pmc_kernels.json)
   cpu_baseline  the CPU oracle (oracle/irse_ref.py, a port of the reference's PyTorch path) timed on the host
                 cores of this box on a bounded sample of the same workload (N = 1, rank 0 only)
+  other_configs short timings of the other BASELINE.json configs (default workload only)
+  clock         shader clock / board power sampled during the timed loop (inside ``roofline`` when that is there)
+``--kernel-table`` and ``--clock-log`` ask for one of these by themselves and run it without ``--full``.
 """
 import argparse
 import json
@@ -55,12 +60,17 @@ def parse():
     ap.add_argument("--sharded-head", action="store_true",
                     help="class-sharded ArcFace + focal loss over the ranks (frhip/sharded_head.py) instead of the "
                          "replicated head; off by default: the BASELINE configs replicate the head")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure the roofline, the shader clock, the other BASELINE.json configs "
+                         "and the CPU baselines; a plain run times the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the instrumented roofline step")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short timings of the other BASELINE.json configs after the headline")
-    ap.add_argument("--kernel-table", default="", help="write the per-launch timing table of the instrumented step")
-    ap.add_argument("--clock-log", default="", help="write every shader-clock / power sample of the timed loop (rank 0)")
+                    help="with --full: skip the short timings of the other BASELINE.json configs after the headline")
+    ap.add_argument("--kernel-table", default="",
+                    help="write the per-launch timing table of the instrumented step (runs that step, --full or not)")
+    ap.add_argument("--clock-log", default="",
+                    help="write every shader-clock / power sample of the timed loop (rank 0; samples it, --full or not)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the timed loop, write what its last step computed as DIR/<name>.npy (float32, rank 0): "
                          "the loss, top-1 / top-5 precision and a fixed seeded sample of the parameters it updated")
@@ -610,6 +620,20 @@ def run_other_config(label, spec, args, device, rank, world, steps=10, warmup=4)
     return rec
 
 
+def default_workload(args):
+    return (args.model, args.head, args.classes, args.batch, args.dtype) == ("IR_50", "ArcFace", 7000, 256, "bf16")
+
+
+def extras(args, world):
+    """What a run measures besides its headline.  A plain run: nothing; ``--full``: everything its ``--no-*`` options
+    leave in.  ``--kernel-table`` / ``--clock-log`` name a file to write, so they switch on what fills it."""
+    return {"roofline": (args.full and not args.no_roofline) or bool(args.kernel_table),
+            "clock": args.full or bool(args.clock_log),
+            "other_configs": args.full and default_workload(args) and not args.no_other_configs and not args.sharded_head
+            and os.environ.get("FRHIP_BENCH_OTHER", "1") != "0",
+            "cpu_baseline": args.full and world == 1 and not args.no_cpu_baseline}
+
+
 def main():
     args = parse()
     json_out, sys.stdout = sys.stdout, sys.stderr  # the modules print while they build; stdout carries the ONE JSON line
@@ -621,6 +645,7 @@ def main():
     if os.environ.get("FRHIP_BENCH_ONE_DEVICE") == "1":
         local = 0  # test hook: several ranks share GPU 0 (with FRHIP_DIST_BACKEND=gloo; RCCL refuses duplicate devices)
     assert torch.cuda.is_available(), "bench.py needs a ROCm GPU (no CPU fallback for the product path)"
+    want = extras(args, world)
     torch.cuda.set_device(local)
     device = torch.device("cuda", local)
     force_dp = os.environ.get("FRHIP_FORCE_DP", "0") == "1"  # exercise the RCCL path with a single rank (tests)
@@ -641,7 +666,7 @@ def main():
     step = make_step(model, head, loss_fn, opt, sync_timer if dp is not None else None)
     x, y = xs[0], ys[0]
 
-    sampler = ClockSampler(local) if rank == 0 else None
+    sampler = ClockSampler(local) if rank == 0 and want["clock"] else None
     dt, loss_val, clocks = timed_loop(step, xs, ys, args.warmup, args.steps, world, device, sampler, sync_timer)
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, *timed_loop.last, model, head)
@@ -676,7 +701,7 @@ def main():
             out[k] = dp_rec[k]
     fams = None
     inner = model.encoder if hasattr(model, "encoder") else model
-    if not args.no_roofline:
+    if want["roofline"]:
         # per-kernel timing needs the weight gradients back on the main stream (no co-running kernels).  Every rank
         # runs the same two extra steps (they contain the gradient all-reduce); only rank 0 wraps its launches in events.
         inner._runner[0].single_stream = True
@@ -765,9 +790,7 @@ def main():
         elif clocks is not None:
             out["clock"] = clocks
     # ---- the other BASELINE configs (short), then the CPU legs
-    default_workload = (args.model, args.head, args.classes, args.batch, args.dtype) == ("IR_50", "ArcFace", 7000, 256, "bf16")
-    if default_workload and not args.no_other_configs and not args.sharded_head and \
-            os.environ.get("FRHIP_BENCH_OTHER", "1") != "0":
+    if want["other_configs"]:
         import gc
         inner._runner[0].plans.clear()
         inner._runner[0].plan = None
@@ -780,9 +803,9 @@ def main():
         if rank == 0:
             out["other_configs"] = others
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if want["cpu_baseline"]:
             out["cpu_baseline"] = cpu_baseline(args.classes)
-            if default_workload:
+            if default_workload(args):
                 # BASELINE configs[0] (the reference's own CPU-runnable case): pSp IR-SE-50, batch 100, 100 identities
                 out["cpu_baseline_config0"] = cpu_baseline(100, seconds_budget=8.0, model="pSp", B=100)
         print(json.dumps(out), file=json_out, flush=True)

@@ -871,7 +871,7 @@ def test_bench_two_ranks_sharing_one_gpu(tmp_path):
     env = dict(os.environ, FRHIP_BENCH_ONE_DEVICE="1", FRHIP_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", "29541", "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "16", "--classes", "1000", "--no-cpu-baseline"]
+           "--batch", "16", "--classes", "1000", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, cwd=repo, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

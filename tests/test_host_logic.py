@@ -398,6 +398,30 @@ def test_bench_refuses_fewer_than_one_timed_step():
     assert out.returncode == 2 and "--steps must be at least 1" in out.stderr, out.stderr[-2000:]
 
 
+def test_plain_bench_run_measures_the_headline_alone(monkeypatch):
+    """``bench.py --gpus 1 --steps K --warmup W`` times the headline and nothing else; ``--full`` adds the roofline step,
+    the clock sampler, the other BASELINE configs and the CPU baselines, each of which its ``--no-*`` option leaves out.
+    ``--kernel-table`` / ``--clock-log`` switch on what fills the file they name."""
+    import sys
+    import bench
+    monkeypatch.delenv("FRHIP_BENCH_OTHER", raising=False)
+
+    def want(*argv, world=1):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", str(world)] + list(argv))
+        return bench.extras(bench.parse(), world)
+
+    assert not any(want("--steps", "20", "--warmup", "5").values())
+    assert not any(want("--no-roofline", "--no-cpu-baseline", "--no-other-configs").values())
+    assert all(want("--full").values())
+    assert want("--full", world=2) == {"roofline": True, "clock": True, "other_configs": True, "cpu_baseline": False}
+    assert want("--full", "--no-roofline", "--no-cpu-baseline", "--no-other-configs") == {
+        "roofline": False, "clock": True, "other_configs": False, "cpu_baseline": False}
+    assert not want("--full", "--batch", "16")["other_configs"] and want("--full", "--batch", "16")["cpu_baseline"]
+    assert want("--kernel-table", "t.json") == {"roofline": True, "clock": False, "other_configs": False,
+                                                "cpu_baseline": False}
+    assert want("--clock-log", "c.txt") == {"roofline": False, "clock": True, "other_configs": False, "cpu_baseline": False}
+
+
 def test_readiness_marks_follow_the_arena_order():
     """engine.BackbonePlan._order_ready_marks (round 3): a deferring weight-gradient launch completes its predecessor's
     gradient one launch late, possibly in the NEXT unit's mark.  Announcements must still walk the gradient arena front to
