@@ -12,6 +12,7 @@
 // fp32 accumulators in the epilogue (one partial row per workgroup; a wave owns its channels: no exchange between waves).
 // The data gradient of the same layer is the same GEMM with the transposed weight and dense rows.
 #include "common.h"
+#include "conv_epilogue.h"
 #include "frhip_internal.h"
 
 namespace {
@@ -89,17 +90,10 @@ __global__ __launch_bounds__(NW * 64) void conv1x1_stream_kernel(const bf16_t* _
         for (int j = 0; j < NTL; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j][kk], af[u][kk], acc[j], 0, 0, 0);
 #pragma unroll
       for (int j = 0; j < NTL; ++j) {
-        uint2 o;
-        o.x = pack2bf(acc[j][0], acc[j][1]);
-        o.y = pack2bf(acc[j][2], acc[j][3]);
-        *reinterpret_cast<uint2*>(tiles + u * 16 * OSTR + fr * OSTR + (n0 + j * 16 + fq * 4) * 2) = o;
-        if (STATS && ok[u]) {  // the sums of fr_conv_igemm's FR_EPI_STATS: of the fp32 accumulators
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            s0[j][r] += acc[j][r];
-            s1[j][r] = fmaf(acc[j][r], acc[j][r], s1[j][r]);
-          }
-        }
+        float v[4] = {acc[j][0], acc[j][1], acc[j][2], acc[j][3]};
+        *reinterpret_cast<uint2*>(tiles + u * 16 * OSTR + fr * OSTR + (n0 + j * 16 + fq * 4) * 2) = fr_cell_pack(v);
+        // the sums of fr_conv_igemm's FR_EPI_STATS: of the fp32 accumulators
+        if (STATS && ok[u]) fr_epi_cell<FR_EPI_STATS>(v, nullptr, nullptr, nullptr, s0[j], s1[j]);
       }
     }
     __syncthreads();
@@ -119,16 +113,12 @@ __global__ __launch_bounds__(NW * 64) void conv1x1_stream_kernel(const bf16_t* _
     for (int j = 0; j < NTL; ++j)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        float a = s0[j][r], c = s1[j][r];
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) {
-          a += __shfl_xor(a, o, 64);
-          c += __shfl_xor(c, o, 64);
-        }
+        float t[2] = {s0[j][r], s1[j][r]};
+        fr_fold16(t);
         if (fr == 0) {
           float* row = part + (size_t)blockIdx.x * 2 * N + n0 + j * 16 + fq * 4 + r;
-          row[0] = a;
-          row[N] = c;
+          row[0] = t[0];
+          row[N] = t[1];
         }
       }
   }

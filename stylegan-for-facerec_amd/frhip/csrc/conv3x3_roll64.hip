@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "conv_epilogue.h"
 #include "frhip_internal.h"
 
 #ifdef FRHIP_STAMPS
@@ -89,7 +90,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_roll64_kernel(const FrConvArgs
     coef[tid] = PRO != FR_PRO_NONE ? p.pro_a[tid] : 0.f;
     coef[K::C + tid] = PRO == FR_PRO_BN ? p.pro_b[tid] : 0.f;
     coef[2 * K::C + tid] = AUX ? p.epi_a[tid] : 0.f;
-    coef[3 * K::C + tid] = (AUX && (epi == FR_EPI_BNBWD || epi == FR_EPI_BIAS_RES)) ? p.epi_b[tid] : 0.f;
+    coef[3 * K::C + tid] = (AUX && fr_epi_uses_b(epi)) ? p.epi_b[tid] : 0.f;
   }
   __syncthreads();
 
@@ -368,7 +369,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_roll64_kernel(const FrConvArgs
 #pragma unroll
         for (int j = 0; j < K::TN; ++j) {
           float ea[4], eb[4];  // from LDS per use rather than live across the MFMA loop
-          if (E == FR_EPI_PRELU_BWD || E == FR_EPI_BNBWD || E == FR_EPI_BIAS_RES) {
+          if (fr_epi_uses_a(E)) {
             const f32x4 t = *reinterpret_cast<const f32x4*>(coef + 2 * K::C + n0 + j * 16 + fq * 4);
             const f32x4 t2 = *reinterpret_cast<const f32x4*>(coef + 3 * K::C + n0 + j * 16 + fq * 4);
 #pragma unroll
@@ -384,44 +385,14 @@ __global__ __launch_bounds__(512, 2) void conv3x3_roll64_kernel(const FrConvArgs
             float v[4], x[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[r] = acc[i][j][r];
-            if (E == FR_EPI_PRELU_BWD || E == FR_EPI_BNBWD || E == FR_EPI_BIAS_RES) {
-              const uint2 u = *cell;
-              x[0] = __uint_as_float(u.x << 16);
-              x[1] = __uint_as_float(u.x & 0xFFFF0000u);
-              x[2] = __uint_as_float(u.y << 16);
-              x[3] = __uint_as_float(u.y & 0xFFFF0000u);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              if (E == FR_EPI_STATS) {
-                s0[j][r] += v[r];
-                s1[j][r] = fmaf(v[r], v[r], s1[j][r]);
-              } else if (E == FR_EPI_PRELU_BWD) {
-                const bool pos = x[r] > 0.f;
-                s0[j][r] += pos ? 0.f : v[r] * x[r];
-                v[r] = pos ? v[r] : v[r] * ea[r];
-              } else if (E == FR_EPI_BNBWD) {
-                s0[j][r] += v[r];
-                s1[j][r] = fmaf(v[r], (x[r] - ea[r]) * eb[r], s1[j][r]);
-              } else if (E == FR_EPI_BIAS_RES) {
-                v[r] += ea[r] + eb[r] + x[r];
-              }
-            }
-            uint2 o;
-            o.x = pack2bf(v[0], v[1]);
-            o.y = pack2bf(v[2], v[3]);
-            *cell = o;
+            if (fr_epi_reads_aux(E)) fr_cell_unpack(*cell, x);
+            fr_epi_cell<E>(v, x, ea, eb, s0[j], s1[j]);
+            *cell = fr_cell_pack(v);
           }
         }
       };
-      if (AUX) {
-        if (epi == FR_EPI_PRELU_BWD) cells(std::integral_constant<int, FR_EPI_PRELU_BWD>{});
-        else if (epi == FR_EPI_BNBWD) cells(std::integral_constant<int, FR_EPI_BNBWD>{});
-        else cells(std::integral_constant<int, FR_EPI_BIAS_RES>{});
-      } else {
-        if (epi == FR_EPI_STATS) cells(std::integral_constant<int, FR_EPI_STATS>{});
-        else cells(std::integral_constant<int, FR_EPI_STORE>{});
-      }
+      if (AUX) fr_epi_dispatch<FR_EPI_PRELU_BWD, FR_EPI_BNBWD, FR_EPI_BIAS_RES>(epi, cells);
+      else fr_epi_dispatch<FR_EPI_STATS, FR_EPI_STORE>(epi, cells);
       RSTAMP(2);
       __syncthreads();  // the tile is complete; the data-moving waves have committed the rows of it + 1
       RSTAMP(3);
@@ -441,18 +412,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_roll64_kernel(const FrConvArgs
 #pragma unroll
       for (int j = 0; j < K::TN; ++j)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float a = s0[j][r], c = s1[j][r];
-#pragma unroll
-          for (int o2 = 1; o2 < 16; o2 <<= 1) {
-            a += __shfl_xor(a, o2, 64);
-            c += __shfl_xor(c, o2, 64);
-          }
-          if (fr == 0) {
-            red[(wm * 2 + 0) * K::C + n0 + j * 16 + fq * 4 + r] = a;
-            red[(wm * 2 + 1) * K::C + n0 + j * 16 + fq * 4 + r] = c;
-          }
-        }
+        for (int r = 0; r < 4; ++r) fr_fold16_park<2>(red, K::C, wm, n0 + j * 16 + fq * 4 + r, fr, s0[j][r], s1[j][r]);
     }
     __syncthreads();  // end of item (matches the data-moving waves)
     if (sums && tid < 2 * K::C) {

@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "conv_epilogue.h"
 #include "frhip_internal.h"
 
 namespace {
@@ -435,28 +436,12 @@ __global__ __launch_bounds__(512, 2) void conv3x3_s2_roll64_kernel(const FrConvA
 #pragma unroll
             for (int q = 0; q < 4; ++q) v[q] = acc[i][j][q];
             if (KIND == 1) {
-              const uint2 u = *cell;
-              x[0] = __uint_as_float(u.x << 16);
-              x[1] = __uint_as_float(u.x & 0xFFFF0000u);
-              x[2] = __uint_as_float(u.y << 16);
-              x[3] = __uint_as_float(u.y & 0xFFFF0000u);
-#pragma unroll
-              for (int q = 0; q < 4; ++q) {
-                const bool pos = x[q] > 0.f;
-                s0[j][q] += pos ? 0.f : v[q] * x[q];
-                v[q] = pos ? v[q] : v[q] * ea[q];
-              }
+              fr_cell_unpack(*cell, x);
+              fr_epi_cell<FR_EPI_PRELU_BWD>(v, x, ea, nullptr, s0[j], s1[j]);
             } else if (epi == FR_EPI_STATS) {
-#pragma unroll
-              for (int q = 0; q < 4; ++q) {
-                s0[j][q] += v[q];
-                s1[j][q] = fmaf(v[q], v[q], s1[j][q]);
-              }
+              fr_epi_cell<FR_EPI_STATS>(v, nullptr, nullptr, nullptr, s0[j], s1[j]);
             }
-            uint2 o;
-            o.x = pack2bf(v[0], v[1]);
-            o.y = pack2bf(v[2], v[3]);
-            *cell = o;
+            *cell = fr_cell_pack(v);
           }
         }
       };
@@ -489,18 +474,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_s2_roll64_kernel(const FrConvA
 #pragma unroll
       for (int j = 0; j < 2; ++j)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          float a = s0[j][q], c = s1[j][q];
-#pragma unroll
-          for (int o2 = 1; o2 < 16; o2 <<= 1) {
-            a += __shfl_xor(a, o2, 64);
-            c += __shfl_xor(c, o2, 64);
-          }
-          if (fr == 0) {
-            red[(wm * 2 + 0) * K::C + n0 + j * 16 + fq * 4 + q] = a;
-            red[(wm * 2 + 1) * K::C + n0 + j * 16 + fq * 4 + q] = c;
-          }
-        }
+        for (int q = 0; q < 4; ++q) fr_fold16_park<2>(red, K::C, wm, n0 + j * 16 + fq * 4 + q, fr, s0[j][q], s1[j][q]);
     }
     __syncthreads();  // end of item (matches the data-moving waves)
     if (sums && tid < 2 * K::C) {

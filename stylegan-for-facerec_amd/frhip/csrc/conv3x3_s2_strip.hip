@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "conv_epilogue.h"
 #include "frhip_internal.h"
 
 #ifdef FRHIP_STAMPS
@@ -405,8 +406,6 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_s2_kernel(const FrConvArgs
     }
     // weights were the MFMA A operand: a lane holds four consecutive channels (fq*4 + r) of one pixel (fr) per tile
     float* red = reinterpret_cast<float*>(otile + C::OUT_BYTES);  // [WM][2][COUT] column sums, behind the output tile
-    // The epilogue kind is a run-time argument, but inside the per-element loops it must be a compile-time constant:
-    // with `epi` tested per element the compiler emitted a scalar branch per accumulator (8000 instructions, ~10 us).
     auto cells = [&](auto tag) {
       constexpr int E = decltype(tag)::value;
       float ea[C::TN][4], eb[C::TN][4], s0[C::TN][4], s1[C::TN][4];
@@ -415,8 +414,8 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_s2_kernel(const FrConvArgs
   #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int n = ncol0 + n0 + j * 16 + fq * 4 + r;
-          ea[j][r] = (E == FR_EPI_PRELU_BWD || E == FR_EPI_BNBWD || E == FR_EPI_BIAS_RES) ? p.epi_a[n] : 0.f;
-          eb[j][r] = (E == FR_EPI_BNBWD || E == FR_EPI_BIAS_RES) ? p.epi_b[n] : 0.f;
+          ea[j][r] = fr_epi_uses_a(E) ? p.epi_a[n] : 0.f;
+          eb[j][r] = fr_epi_uses_b(E) ? p.epi_b[n] : 0.f;
           s0[j][r] = s1[j][r] = 0.f;
         }
   #pragma unroll
@@ -429,60 +428,19 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_s2_kernel(const FrConvArgs
           float v[4], x[4];
   #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = acc[i][j][r];
-          if (E == FR_EPI_PRELU_BWD || E == FR_EPI_BNBWD || E == FR_EPI_BIAS_RES) {
-            const uint2 u = *cell;
-            x[0] = __uint_as_float(u.x << 16);
-            x[1] = __uint_as_float(u.x & 0xFFFF0000u);
-            x[2] = __uint_as_float(u.y << 16);
-            x[3] = __uint_as_float(u.y & 0xFFFF0000u);
-          }
-  #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            if (E == FR_EPI_STATS) {
-              s0[j][r] += v[r];
-              s1[j][r] = fmaf(v[r], v[r], s1[j][r]);
-            } else if (E == FR_EPI_PRELU_BWD) {
-              const bool pos = x[r] > 0.f;
-              s0[j][r] += pos ? 0.f : v[r] * x[r];
-              v[r] = pos ? v[r] : v[r] * ea[j][r];
-            } else if (E == FR_EPI_BNBWD) {
-              s0[j][r] += v[r];
-              s1[j][r] = fmaf(v[r], (x[r] - ea[j][r]) * eb[j][r], s1[j][r]);
-            } else if (E == FR_EPI_BIAS_RES) {
-              v[r] += ea[j][r] + eb[j][r] + x[r];
-            }
-          }
-          uint2 o;
-          o.x = pack2bf(v[0], v[1]);
-          o.y = pack2bf(v[2], v[3]);
-          *cell = o;
+          if (fr_epi_reads_aux(E)) fr_cell_unpack(*cell, x);
+          fr_epi_cell<E>(v, x, ea[j], eb[j], s0[j], s1[j]);
+          *cell = fr_cell_pack(v);
         }
       }
-      if (E != FR_EPI_STORE && E != FR_EPI_BIAS_RES) {
+      if (fr_epi_has_sums(E)) {
   #pragma unroll
         for (int j = 0; j < C::TN; ++j)
   #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            float a = s0[j][r], c = s1[j][r];
-  #pragma unroll
-            for (int o = 1; o < 16; o <<= 1) {
-              a += __shfl_xor(a, o, 64);
-              c += __shfl_xor(c, o, 64);
-            }
-            if (fr == 0) {
-              red[(wm * 2 + 0) * COUT + n0 + j * 16 + fq * 4 + r] = a;
-              red[(wm * 2 + 1) * COUT + n0 + j * 16 + fq * 4 + r] = c;
-            }
-          }
+          for (int r = 0; r < 4; ++r) fr_fold16_park<2>(red, COUT, wm, n0 + j * 16 + fq * 4 + r, fr, s0[j][r], s1[j][r]);
       }
     };
-    switch (epi) {
-      case FR_EPI_STATS: cells(std::integral_constant<int, FR_EPI_STATS>{}); break;
-      case FR_EPI_PRELU_BWD: cells(std::integral_constant<int, FR_EPI_PRELU_BWD>{}); break;
-      case FR_EPI_BNBWD: cells(std::integral_constant<int, FR_EPI_BNBWD>{}); break;
-      case FR_EPI_BIAS_RES: cells(std::integral_constant<int, FR_EPI_BIAS_RES>{}); break;
-      default: cells(std::integral_constant<int, FR_EPI_STORE>{}); break;
-    }
+    fr_epi_dispatch<FR_EPI_STATS, FR_EPI_PRELU_BWD, FR_EPI_BNBWD, FR_EPI_BIAS_RES, FR_EPI_STORE>(epi, cells);
     hsync();
     for (int idx = htid; idx < C::M * hoch; idx += hnth) {
       const int r = idx / hoch, c8 = hc0 + idx - r * hoch;

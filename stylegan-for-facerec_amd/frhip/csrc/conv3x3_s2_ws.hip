@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "conv_epilogue.h"
 #include "frhip_internal.h"
 
 #ifdef FRHIP_STAMPS
@@ -342,15 +343,9 @@ __global__ __launch_bounds__(512) void conv3x3_s2_ws_kernel(const FrConvArgs p, 
       for (int j = 0; j < C::TN; ++j) {
         float v[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          v[r] = acc[i][j][r];
-          s0[j][r] += v[r];
-          s1[j][r] = fmaf(v[r], v[r], s1[j][r]);
-        }
-        uint2 o;
-        o.x = pack2bf(v[0], v[1]);
-        o.y = pack2bf(v[2], v[3]);
-        *reinterpret_cast<uint2*>(smem + m * C::OSTR + (n0 + j * 16 + fq * 4) * 2) = o;
+        for (int r = 0; r < 4; ++r) v[r] = acc[i][j][r];
+        fr_epi_cell<FR_EPI_STATS>(v, nullptr, nullptr, nullptr, s0[j], s1[j]);
+        *reinterpret_cast<uint2*>(smem + m * C::OSTR + (n0 + j * 16 + fq * 4) * 2) = fr_cell_pack(v);
       }
     }
     if (stats) {  // a wave owns its 32 columns: fold the 16 pixel lanes, one partial row per workgroup
@@ -358,16 +353,12 @@ __global__ __launch_bounds__(512) void conv3x3_s2_ws_kernel(const FrConvArgs p, 
       for (int j = 0; j < C::TN; ++j)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          float a = s0[j][r], c = s1[j][r];
-#pragma unroll
-          for (int o = 1; o < 16; o <<= 1) {
-            a += __shfl_xor(a, o, 64);
-            c += __shfl_xor(c, o, 64);
-          }
+          float t[2] = {s0[j][r], s1[j][r]};
+          fr_fold16(t);
           if (fr == 0) {
             const int n = ncol0 + n0 + j * 16 + fq * 4 + r;
-            st_part(p.part + ((size_t)sblk * 2 + 0) * (CW * NSPL) + n, a);
-            st_part(p.part + ((size_t)sblk * 2 + 1) * (CW * NSPL) + n, c);
+            st_part(p.part + ((size_t)sblk * 2 + 0) * (CW * NSPL) + n, t[0]);
+            st_part(p.part + ((size_t)sblk * 2 + 1) * (CW * NSPL) + n, t[1]);
           }
         }
     }

@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "conv_epilogue.h"
 #include "frhip_internal.h"
 
 #ifdef FRHIP_STAMPS
@@ -261,7 +262,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_strip_kernel(const FrConvA
       for (int j = 0; j < C::TN; ++j) wrow[j] = wgt + (size_t)((ncol0 + n0) / 16 + j) * 16 * 9 * CIN + lane * 8;
     }
     const int epi = p.epi;
-    const bool stats = epi == FR_EPI_STATS || epi == FR_EPI_PRELU_BWD || epi == FR_EPI_BNBWD || epi == FR_EPI_STATS_X;
+    const bool stats = fr_epi_has_sums(epi);
     const int b = NIMG > 1 ? s * NIMG : s / C::NS;  // first image of the strip
     const int row0 = NIMG > 1 ? 0 : (s - b * C::NS) * ROWS;
     f32x4 acc[C::TM][C::TN];
@@ -364,7 +365,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_strip_kernel(const FrConvA
     // barrier that ends the K loop: as a load -> wait -> LDS-store loop it cost one HBM round trip per 16 bytes of a
     // thread (13 of them, ~7 us of a 55-us 14x14 launch); the registers are those of the dead fragment rings.
     constexpr int NAUX = (C::M * OCH + NTH - 1) / NTH;
-    const bool has_aux = epi == FR_EPI_PRELU_BWD || epi == FR_EPI_BNBWD || epi == FR_EPI_BIAS_RES || epi == FR_EPI_STATS_X;
+    const bool has_aux = fr_epi_reads_aux(epi);
     U128 av[NAUX];
     if (has_aux) {
       const bf16_t* __restrict__ aux = reinterpret_cast<const bf16_t*>(p.aux);
@@ -393,22 +394,18 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_strip_kernel(const FrConvA
     // (n = fq*4 + r) of ONE pixel (m = fr): one 8-byte LDS access per tile instead of four 2-byte ones, and the
     // 16 lanes of a ds_write_b64 lane group hit 16 different rows on disjoint banks (row stride = 4 banks mod 64).
     float* red = reinterpret_cast<float*>(smem + C::OUT_BYTES);  // [WM][NV][COUT] column sums, behind the output tile
-    const int NV = epi == FR_EPI_STATS_X ? 3 : 2;
-    // The epilogue kind is a run-time argument, but inside the per-element loops it must be a compile-time constant:
-    // with `epi` tested per element the compiler emitted a scalar branch per accumulator (8000 instructions, ~10 us).
+    const int NV = fr_epi_nsums(epi);
     auto cells = [&](auto tag) {
       constexpr int E = decltype(tag)::value;
-      constexpr bool AUX = E == FR_EPI_PRELU_BWD || E == FR_EPI_BNBWD || E == FR_EPI_BIAS_RES || E == FR_EPI_STATS_X;
-      float ea[C::TN][4], eb[C::TN][4], s0[C::TN][4], s1[C::TN][4], s2[E == FR_EPI_STATS_X ? C::TN : 1][4];
+      float ea[C::TN][4], eb[C::TN][4], s0[C::TN][4], s1[C::TN][4], s2[C::TN][4];
   #pragma unroll
       for (int j = 0; j < C::TN; ++j)
   #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int n = ncol0 + n0 + j * 16 + fq * 4 + r;
-          ea[j][r] = (E == FR_EPI_PRELU_BWD || E == FR_EPI_BNBWD || E == FR_EPI_BIAS_RES) ? p.epi_a[n] : 0.f;
-          eb[j][r] = (E == FR_EPI_BNBWD || E == FR_EPI_BIAS_RES) ? p.epi_b[n] : 0.f;
-          s0[j][r] = s1[j][r] = 0.f;
-          if (E == FR_EPI_STATS_X) s2[j][r] = 0.f;
+          ea[j][r] = fr_epi_uses_a(E) ? p.epi_a[n] : 0.f;
+          eb[j][r] = fr_epi_uses_b(E) ? p.epi_b[n] : 0.f;
+          s0[j][r] = s1[j][r] = s2[j][r] = 0.f;
         }
   #pragma unroll
       for (int i = 0; i < C::TM; ++i) {
@@ -420,69 +417,21 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_strip_kernel(const FrConvA
           float v[4], x[4];
   #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = acc[i][j][r];
-          if (AUX) {
-            const uint2 u = *cell;
-            x[0] = __uint_as_float(u.x << 16);
-            x[1] = __uint_as_float(u.x & 0xFFFF0000u);
-            x[2] = __uint_as_float(u.y << 16);
-            x[3] = __uint_as_float(u.y & 0xFFFF0000u);
-          }
-  #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            if (E == FR_EPI_STATS) {
-              s0[j][r] += v[r];
-              s1[j][r] = fmaf(v[r], v[r], s1[j][r]);
-            } else if (E == FR_EPI_STATS_X) {  // + the cross moment with the residual input (fr_bn_finalize_res)
-              s0[j][r] += v[r];
-              s1[j][r] = fmaf(v[r], v[r], s1[j][r]);
-              s2[j][r] = fmaf(v[r], x[r], s2[j][r]);
-            } else if (E == FR_EPI_PRELU_BWD) {
-              const bool pos = x[r] > 0.f;
-              s0[j][r] += pos ? 0.f : v[r] * x[r];
-              v[r] = pos ? v[r] : v[r] * ea[j][r];
-            } else if (E == FR_EPI_BNBWD) {
-              s0[j][r] += v[r];
-              s1[j][r] = fmaf(v[r], (x[r] - ea[j][r]) * eb[j][r], s1[j][r]);
-            } else if (E == FR_EPI_BIAS_RES) {
-              v[r] += ea[j][r] + eb[j][r] + x[r];
-            }
-          }
-          uint2 o;
-          o.x = pack2bf(v[0], v[1]);
-          o.y = pack2bf(v[2], v[3]);
-          *cell = o;
+          if (fr_epi_reads_aux(E)) fr_cell_unpack(*cell, x);
+          fr_epi_cell<E>(v, x, ea[j], eb[j], s0[j], s1[j], s2[j]);
+          *cell = fr_cell_pack(v);
         }
       }
       // column sums: fold the 16 pixel lanes (fr), then the WM row groups through LDS (behind the output tile)
-      if (E != FR_EPI_STORE && E != FR_EPI_BIAS_RES) {
+      if (fr_epi_has_sums(E)) {
   #pragma unroll
         for (int j = 0; j < C::TN; ++j)
   #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            constexpr int V = E == FR_EPI_STATS_X ? 3 : 2;
-            float a = s0[j][r], c = s1[j][r], d = E == FR_EPI_STATS_X ? s2[j][r] : 0.f;
-  #pragma unroll
-            for (int o = 1; o < 16; o <<= 1) {
-              a += __shfl_xor(a, o, 64);
-              c += __shfl_xor(c, o, 64);
-              if (E == FR_EPI_STATS_X) d += __shfl_xor(d, o, 64);
-            }
-            if (fr == 0) {
-              red[(wm * V + 0) * COUT + n0 + j * 16 + fq * 4 + r] = a;
-              red[(wm * V + 1) * COUT + n0 + j * 16 + fq * 4 + r] = c;
-              if (E == FR_EPI_STATS_X) red[(wm * V + 2) * COUT + n0 + j * 16 + fq * 4 + r] = d;
-            }
-          }
+          for (int r = 0; r < 4; ++r)
+            fr_fold16_park<fr_epi_nsums(E)>(red, COUT, wm, n0 + j * 16 + fq * 4 + r, fr, s0[j][r], s1[j][r], s2[j][r]);
       }
     };
-    switch (epi) {
-      case FR_EPI_STATS: cells(std::integral_constant<int, FR_EPI_STATS>{}); break;
-      case FR_EPI_STATS_X: cells(std::integral_constant<int, FR_EPI_STATS_X>{}); break;
-      case FR_EPI_PRELU_BWD: cells(std::integral_constant<int, FR_EPI_PRELU_BWD>{}); break;
-      case FR_EPI_BNBWD: cells(std::integral_constant<int, FR_EPI_BNBWD>{}); break;
-      case FR_EPI_BIAS_RES: cells(std::integral_constant<int, FR_EPI_BIAS_RES>{}); break;
-      default: cells(std::integral_constant<int, FR_EPI_STORE>{}); break;
-    }
+    fr_epi_dispatch<FR_EPI_STATS, FR_EPI_STATS_X, FR_EPI_PRELU_BWD, FR_EPI_BNBWD, FR_EPI_BIAS_RES, FR_EPI_STORE>(epi, cells);
     __syncthreads();
     FR_STAMP(5);
     {  // all LDS reads of a thread first, then its stores (as a read -> wait -> store loop: one LDS latency per 16 bytes)

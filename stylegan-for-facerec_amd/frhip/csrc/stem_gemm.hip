@@ -7,6 +7,7 @@
 // fragment is one coalesced 16-byte global load: 16 rows x 64 B are contiguous), weights live in registers, every
 // wave streams 16-row tiles, and both are HBM-bound by construction (forward: 64 B in, 128 B out per row).
 #include "common.h"
+#include "conv_epilogue.h"
 #include "frhip_internal.h"
 
 namespace {
@@ -107,28 +108,20 @@ __global__ __launch_bounds__(256) void stem_gemm_kernel(const bf16_t* __restrict
       o.y = pack2bf(acc[j][2], acc[j][3]);
       if (MODE != 1) *reinterpret_cast<uint2*>(tile + fr * OSTR + (j * 16 + fq * 4) * 2) = o;
       if (MODE == 2) {  // z = PReLU(BN(y)) of the ROUNDED y, as fr_bn_apply computes it from the stored tensor
-        float uq[4] = {__uint_as_float(o.x << 16), __uint_as_float(o.x & 0xFFFF0000u), __uint_as_float(o.y << 16),
-                       __uint_as_float(o.y & 0xFFFF0000u)};
+        float uq[4];
+        fr_cell_unpack(o, uq);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           uq[r] = fmaf(uq[r], asc[j][r], ash[j][r]);
           uq[r] = uq[r] > 0.f ? uq[r] : uq[r] * asl[j][r];
         }
-        o.x = pack2bf(uq[0], uq[1]);
-        o.y = pack2bf(uq[2], uq[3]);
+        o = fr_cell_pack(uq);
         *reinterpret_cast<uint2*>(ztile + fr * OSTR + (j * 16 + fq * 4) * 2) = o;
       }
       if (ok) {  // statistics of what the next layer will actually read
-        const float q0 = __uint_as_float(o.x << 16), q1 = __uint_as_float(o.x & 0xFFFF0000u);
-        const float q2 = __uint_as_float(o.y << 16), q3 = __uint_as_float(o.y & 0xFFFF0000u);
-        s0[j][0] += q0;
-        s0[j][1] += q1;
-        s0[j][2] += q2;
-        s0[j][3] += q3;
-        s1[j][0] = fmaf(q0, q0, s1[j][0]);
-        s1[j][1] = fmaf(q1, q1, s1[j][1]);
-        s1[j][2] = fmaf(q2, q2, s1[j][2]);
-        s1[j][3] = fmaf(q3, q3, s1[j][3]);
+        float q[4];
+        fr_cell_unpack(o, q);
+        fr_epi_cell<FR_EPI_STATS>(q, nullptr, nullptr, nullptr, s0[j], s1[j]);
       }
     }
     if (MODE == 1) continue;  // statistics only: no tile, no barrier
@@ -150,18 +143,7 @@ __global__ __launch_bounds__(256) void stem_gemm_kernel(const bf16_t* __restrict
 #pragma unroll
   for (int j = 0; j < 4; ++j)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float a = s0[j][r], c = s1[j][r];
-#pragma unroll
-      for (int o = 1; o < 16; o <<= 1) {
-        a += __shfl_xor(a, o, 64);
-        c += __shfl_xor(c, o, 64);
-      }
-      if (fr == 0) {
-        red[(wave * NV + 0) * SN + j * 16 + fq * 4 + r] = a;
-        red[(wave * NV + 1) * SN + j * 16 + fq * 4 + r] = c;
-      }
-    }
+    for (int r = 0; r < 4; ++r) fr_fold16_park<NV>(red, SN, wave, j * 16 + fq * 4 + r, fr, s0[j][r], s1[j][r]);
   __syncthreads();
   if (tid < NV * SN) {
     const int k = tid / SN, n = tid - k * SN;
