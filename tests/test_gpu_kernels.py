@@ -618,6 +618,20 @@ def _part_rows(nparts, B, sel):
     return rows
 
 
+def _assert_all_part_rows_match_the_stored_output(part, out, what):
+    """Device-side check over ALL part rows and ALL images: the sum of the rows' first vector (taken from the fp32 accumulators,
+    before the bf16 store) against the per-channel sum of the kernel's own stored output.  The bar is derived, not measured:
+    the two differ by ONE bf16 rounding per element (2^-9 relative, round to nearest) plus the fp32 summation error of the
+    n elements one part row adds (n * 2^-24 relative; the rows themselves are added in float64):
+    |difference| <= (2^-9 + n * 2^-24) * sum |out| per channel."""
+    o = out.double().reshape(-1, out.shape[-1])
+    n = -(-o.shape[0] // part.shape[0])
+    bound = (2.0 ** -9 + n * 2.0 ** -24) * o.abs().sum(0)
+    diff = (part.double().sum(0)[0] - o.sum(0)).abs()
+    assert bool((diff <= bound).all()), "%s: all part rows vs the stored output: worst %.3g of the bound" % (
+        what, float((diff / bound.clamp_min(1e-30)).max()))
+
+
 @pytest.mark.parametrize("cin,cout,W,B", STRIP_CASES, ids=["%d_%d_%d_b%d" % s for s in STRIP_CASES])
 def test_conv3x3_strip(K, cin, cout, W, B):
     """LDS-resident-strip 3x3 s1 conv (bf16): forward with BN prologue + statistics, and the mirrored-tap data
@@ -649,6 +663,7 @@ def test_conv3x3_strip(K, cin, cout, W, B):
         s = part[_part_rows(nparts, B, sel)].sum(0).cpu()
         np.testing.assert_allclose(s[0], ref.sum((0, 2, 3)), rtol=1e-2, atol=1e-2 * float(ref.abs().sum() / cout))
         np.testing.assert_allclose(s[1], (ref * ref).sum((0, 2, 3)), rtol=1e-2)
+        _assert_all_part_rows_match_the_stored_output(part, out, "forward")
     # data gradient: g [B, cout, W, W] -> gx [B, cin, W, W] with weights given as [cin][tap][cout]
     gs_, gd = _operand(B, sel, 31, "sg", (B, cout, W, W), dtype)
     xg = synth.normal(31, "sxx", (len(sel), cin, W, W)).requires_grad_(True)
@@ -684,6 +699,7 @@ def test_conv3x3_strip(K, cin, cout, W, B):
                                        atol=1e-2 * float(gx.abs().sum() / cin))
             np.testing.assert_allclose(ps[1].cpu(), (gx * xh).sum((0, 2, 3)), rtol=1e-2,
                                        atol=1e-2 * float((gx * xh).abs().sum() / cin))
+            _assert_all_part_rows_match_the_stored_output(part, o, "data gradient (BNBWD)")
 
 
 
@@ -1019,6 +1035,7 @@ def test_conv3x3_s2_strip_forward(K, s2_walk, C, WL, B, walk, pro):
     ps = part[_part_rows(n, B, sel)].sum(0)  # forward rows are image-major, the same number per image
     np.testing.assert_allclose(ps[0].cpu(), y.sum((0, 2, 3)), rtol=tol, atol=tol * float(y.abs().sum() / C))
     np.testing.assert_allclose(ps[1].cpu(), (y * y).sum((0, 2, 3)), rtol=tol)
+    _assert_all_part_rows_match_the_stored_output(part, out, "stride-2 forward")
 
 
 @pytest.mark.parametrize("C,WL,B,walk", S2_CASES, ids=["%d_%d_b%d%s" % s for s in S2_CASES])
