@@ -598,6 +598,21 @@ int fr_resize_bilinear(const float* in, float* out, int planes, int Hin, int Win
  * F.interpolate(..., mode='bilinear') in pSp.forward (backbone/restyle_psp.py:440-443). */
 int fr_resize_bilinear_bwd(const float* gout, float* gin, int planes, int Hin, int Win, int Hout, int Wout, void* stream);
 
+/* ---- RB-WebFace pair tallies (rb-webface/scripts/test_RB_Webface.py:153-233: calc_FNMR, calc_FMR), fp32.  E [M][ldE] holds
+ *      M L2-normalised rows of D floats (fr_row_normalize), thr [T] the thresholds on the device, T <= 32:
+ *   mode 0: counts[t] = #{ i < j                         : E_i . E_j > thr[t] }   (all pairs; `group` ignored)
+ *   mode 1: counts[t] = #{ i < j, i / group == j / group : E_i . E_j < thr[t] }   (group consecutive rows = one person,
+ *                                                                                  2 <= group <= 16; a short last group counts the pairs it has)
+ * Both comparisons are strict and a NaN score is in no tally.  The M x M scores are never stored: one workgroup per
+ * 128 x 128 tile of the upper triangle (mode 1: the diagonal tiles and the right neighbour wherever a tile edge cuts a group)
+ * forms its scores with the f32-input MFMA, tallies them and writes one row of partials [fr_pair_counts_parts()][T] uint32;
+ * a second kernel of the same call sums the rows into counts [T] int64.  Integer sums: bit-identical from run to run.
+ * M >= 2, D % 4 == 0, 4 <= D <= 2048, ldE % 4 == 0, E 16-byte aligned.  Allocates nothing. */
+int fr_pair_counts(const float* E, int ldE, int M, int D, const float* thr, int T, int mode, int group, uint32_t* partials,
+                   int64_t* counts, void* stream);
+/* rows of `partials` a call with (M, mode, group) writes (host arithmetic only); < 0: unsupported argument */
+int fr_pair_counts_parts(int M, int mode, int group);
+
 /* ---- multi-tensor SGD with momentum (torch.optim.SGD defaults; train.py:196)
  *   d = g + wd*p ; buf = momentum*buf + d ; p -= lr*buf      (buf starts at 0, so the first step gives buf = d)
  * table_dev: device array of tensor records; chunks_dev: device array of (tensor index, chunk index) pairs,
