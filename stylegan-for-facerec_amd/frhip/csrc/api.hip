@@ -73,6 +73,11 @@ extern "C" int fr_set_option(const char* name, int value) {
 
 extern "C" int fr_get_option(const char* name, int dflt) { return *fr_option_slot(name, dflt); }
 
+int fr_xcd_order() {
+  static const int* v = fr_option_slot("FRHIP_XCD_ORDER", 1);
+  return *v != 0;
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // Completion event of the next kernel (common.h, FR_LAUNCH_KERNEL)
 // ---------------------------------------------------------------------------------------------------------

@@ -86,6 +86,17 @@ inline void fr_attr_done(unsigned long long& done_mask) {
   (void)hipGetDevice(&dev);
   if (dev < 64) __atomic_fetch_or(&done_mask, 1ull << dev, __ATOMIC_RELEASE);
 }
+// launch of kernel instance Kern with `lds` bytes of dynamic LDS: attribute (once per device), launch, error check
+template <auto Kern, typename... A>
+int fr_launch_lds(int grid, int threads, int lds, hipStream_t st, A&&... args) {
+  static unsigned long long attr_done = 0;  // one bit per device
+  if (fr_attr_needed(attr_done)) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    fr_attr_done(attr_done);
+  }
+  FR_LAUNCH_KERNEL(Kern, dim3(grid), dim3(threads), lds, st, std::forward<A>(args)...);
+  FR_LAUNCH_CHECK();
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // bf16 <-> f32

@@ -562,24 +562,11 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_s2_kernel(const FrConvArgs
   }
 }
 
-static int s2_xcd_order() {  // bit 0: FRHIP_XCD_ORDER=0: strips in dispatch order
-  static const int* v = fr_option_slot("FRHIP_XCD_ORDER", 1);
-  return *v != 0 ? 1 : 0;
-}
-
 template <int CIN, int COUT, int WL, int ROWS, int WN, int NW, int KIND, int PRO, int NSPL, int NIMG>
 int launch(const FrConvArgs& a, hipStream_t st) {
   using C = S2<CIN, COUT, WL, ROWS, WN, NW, KIND, NIMG>;
-  static unsigned long long attr_done = 0;  // one bit per device
-  if (fr_attr_needed(attr_done)) {
-    (void)hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&conv3x3_s2_kernel<CIN, COUT, WL, ROWS, WN, NW, KIND, PRO, NSPL, NIMG>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-    fr_attr_done(attr_done);
-  }
-  FR_LAUNCH_KERNEL((conv3x3_s2_kernel<CIN, COUT, WL, ROWS, WN, NW, KIND, PRO, NSPL, NIMG>),
-                     dim3(a.B * C::NS / NIMG * NSPL), dim3(C::NTH), C::LDS, st, a, s2_xcd_order());
-  FR_LAUNCH_CHECK();
+  return fr_launch_lds<&conv3x3_s2_kernel<CIN, COUT, WL, ROWS, WN, NW, KIND, PRO, NSPL, NIMG>>(
+      fr_strips_of<C, NIMG>(a.B) * NSPL, C::NTH, C::LDS, st, a, fr_xcd_order());
 }
 
 template <int CIN, int COUT, int WL, int ROWS, int WN, int NW, int KIND, int NSPL = 1, int NIMG = 1>
@@ -592,22 +579,48 @@ int by_pro(const FrConvArgs& a, hipStream_t st) {
   FR_UNSUPPORTED("fr_conv3x3_s2_strip: unknown prologue");
 }
 
-// The table (round 3; its round-2 predecessor behind FRHIP_S2_VARIANT=0 was removed in round 4): instances in which ONE
-// weight fragment feeds as many M tiles as the registers allow -- a wave's cost per MFMA is its private weight stream from L2
-// (conv3x3_strip.hip):
+// One line of the table: an LDS-strip instance of one KIND (0: forward, one partial-sum row per strip; 1: data gradient,
+// 4 parity classes x strips, ordered [class][strip]).  Fragment-order weights but at 64 channels.
+template <int KIND, int CIN, int COUT, int WL, int ROWS, int WN, int NW, int NSPL = 1, int NIMG = 1>
+FrConvInstance s2(int B) {
+  return {(KIND ? 4 : 1) * fr_strips_of<S2<CIN, COUT, WL, ROWS, WN, NW, KIND, NIMG>, NIMG>(B), CIN != 64, false,
+          &by_pro<CIN, COUT, WL, ROWS, WN, NW, KIND, NSPL, NIMG>};
+}
+// ... of both kinds
+template <int CIN, int COUT, int WL, int ROWS, int WN, int NW, int NSPL = 1, int NIMG = 1>
+FrConvInstance s2(int B, int mode) {
+  return mode == 0 ? s2<0, CIN, COUT, WL, ROWS, WN, NW, NSPL, NIMG>(B) : s2<1, CIN, COUT, WL, ROWS, WN, NW, NSPL, NIMG>(B);
+}
+
+// The shape table of the stride-2 family (the four IR stage transitions, C -> C): the instance that serves (batch, channels,
+// low-res width, mode) under the current switches, parts == 0 when none does.  fr_conv3x3_s2_strip_parts / _takes_frag
+// report it, fr_conv3x3_s2_strip launches it -- nothing else decides.  `a`: the launch's arguments; nullptr for the queries,
+// which have no epilogue argument and answer with the kernel that serves the training step's epilogues.
+// The LDS-strip lines (round 3; their round-2 predecessors behind FRHIP_S2_VARIANT=0 were removed in round 4): instances in
+// which ONE weight fragment feeds as many M tiles as the registers allow -- a wave's cost per MFMA is its private weight
+// stream from L2 (conv3x3_strip.hip):
 //   128 @28: 8 waves x (13 tiles x 1 column) instead of 4 x 2 waves x (7 x 2): 0.139 -> 0.116 ms forward, 0.193 -> 0.168 gradient
 //   256 @14 forward: the whole image (13 tiles) x 1 column, output channels over two workgroups (123 KB plane);
 //            the gradient keeps 7-row strips: its g strip stays resident beside the output tile (178 KB otherwise)
 //   512 @7:  two images per workgroup (7 tiles x 1 column), output channels over four workgroups; odd batches keep the
 //            one-image instance
-
-// strips (= partial-sum rows per output class) of a served shape, 0 = not served: the four IR stage transitions
-int s2_strips(int B, int C, int WL, int mode) {
-  if (C == 64 && WL == 56) return B * 28;   // 2 low-res rows per workgroup
-  if (C == 128 && WL == 28) return B * 4;   // 7 rows
-  if (C == 256 && WL == 14) return mode == 0 ? B : B * 2;
-  if (C == 512 && WL == 7) return B % 2 == 0 ? B / 2 : B;
-  return 0;
+FrConvInstance select_s2(int B, int C, int WL, int mode, const FrConvArgs* a) {
+  const auto is = [&](int c, int wl) { return C == c && WL == wl; };
+  // 64 channels: the rolling-window kernel (conv3x3_s2_roll64.hip; one row per work item in either mode, weights resident:
+  // plain layout), for the epilogues it serves -- forward STORE / STATS, gradient PReLU backward
+  if (is(64, 56) && fr_s2roll_enabled() && (!a || fr_s2roll_serves(*a))) return {fr_s2roll_parts(B), false, false, &fr_s2roll_launch};
+  // forward at 128 / 256 / 512 channels: the warp-specialised kernel (conv3x3_s2_ws.hip, round 6), which has its own strip
+  // count at 7x7 (four images per workgroup)
+  if (const int ws = mode == 0 ? fr_s2ws_strips(B, C, WL) : 0; ws && (!a || fr_s2ws_serves(*a))) return {ws, true, false, &fr_s2ws_launch};
+  if (is(64, 56)) return s2<64, 64, 56, 2, 2, 4>(B, mode);  // 2 low-res rows per workgroup
+  // 128 -> 128: 7-row strips (196 pixels per weight pass) although only one workgroup then fits a CU: 0.166 -> 0.140 ms
+  // forward, 0.221 -> 0.206 ms gradient against the 4-row strips (the kernel is bound by the weight stream)
+  if (is(128, 28)) return s2<128, 128, 28, 7, 8, 8>(B, mode);
+  if (is(256, 14) && mode == 0) return s2<0, 256, 128, 14, 14, 8, 8, 2, 1>(B);
+  if (is(512, 7) && B % 2 == 0) return s2<512, 128, 7, 7, 8, 8, 4, 2>(B, mode);
+  if (is(256, 14)) return s2<256, 256, 14, 7, 8, 8>(B, mode);  // (reached by the gradient only)
+  if (is(512, 7)) return s2<512, 512, 7, 7, 8, 8>(B, mode);
+  return {};
 }
 
 }  // namespace
@@ -615,24 +628,11 @@ int s2_strips(int B, int C, int WL, int mode) {
 // Partial-sum rows the kernel writes for a supported (B, C -> C, low-res width) problem; 0 when not served.
 // mode 0: forward (one row per workgroup); mode 2: data gradient (4 classes x workgroups, ordered [class][workgroup]).
 extern "C" int fr_conv3x3_s2_strip_parts(int B, int Cin, int Cout, int WL, int mode) {
-  if (Cin != Cout) return 0;
-  // 64 channels: one row per work item of the rolling-window kernel.  NOTE: the caller's epilogue decides whether that kernel
-  // serves the launch (forward STORE / STATS, gradient PReLU backward); the combinations it does not serve write no sums.
-  if (Cin == 64 && WL == 56 && fr_s2roll_enabled()) return fr_s2roll_parts(B);
-  if (mode == 0) {  // the warp-specialised forward kernel has its own strip count at 7x7 (four images per workgroup)
-    const int ws = fr_s2ws_strips(B, Cin, WL);
-    if (ws) return ws;
-  }
-  const int strips = s2_strips(B, Cin, WL, mode);
-  return mode == 2 ? 4 * strips : strips;
+  return Cin == Cout ? select_s2(B, Cin, WL, mode, nullptr).parts : 0;
 }
 
-// 1 when the launch reads fragment-order weights (FrConvArgs.w_frag): every served shape but the 64-channel layer, whose
-// rolling-window kernel keeps its weights resident
-extern "C" int fr_conv3x3_s2_strip_takes_frag(int B, int C, int WL, int mode) {
-  if (C == 64) return 0;
-  return fr_conv3x3_s2_strip_parts(B, C, C, WL, mode) > 0 ? 1 : 0;
-}
+// 1 when the launch reads fragment-order weights (FrConvArgs.w_frag): every served shape but the 64-channel layer
+extern "C" int fr_conv3x3_s2_strip_takes_frag(int B, int C, int WL, int mode) { return select_s2(B, C, WL, mode, nullptr).frag; }
 
 extern "C" int fr_conv3x3_s2_strip(const FrConvArgs* args, void* stream) {
   const FrConvArgs& a = *args;
@@ -648,35 +648,17 @@ extern "C" int fr_conv3x3_s2_strip(const FrConvArgs* args, void* stream) {
   const int WHi = a.mode == 0 ? a.SW : a.RW, HHi = a.mode == 0 ? a.SH : a.RH;
   if (WLo != HLo || WHi != 2 * WLo || HHi != 2 * HLo || a.SC != a.N)
     FR_UNSUPPORTED("fr_conv3x3_s2_strip: square images, high-res side = 2 x low-res side, Cin == Cout");
-  if (fr_s2roll_serves(a)) {
-    if (a.w_frag) FR_UNSUPPORTED("fr_conv3x3_s2_strip: the 64-channel rolling-window kernel takes the plain weight layout (w_frag)");
-    return fr_s2roll_launch(a, st);
-  }
-  if (fr_s2ws_serves(a)) return fr_s2ws_launch(a, st);  // forward, 128 / 256 / 512 channels (round 6)
-  // fr_conv3x3_s2_strip_parts() has no epilogue argument: for the 64-channel layer it answers with the row count of the
-  // rolling-window kernel.  A summing epilogue that kernel does not serve would make the strip kernel below write a
-  // DIFFERENT number of partial rows into a buffer sized from that answer -- refuse instead of overrunning it.
-  if (a.SC == 64 && WLo == 56 && fr_s2roll_enabled() && a.part &&
-      (a.epi == FR_EPI_STATS || a.epi == FR_EPI_PRELU_BWD || a.epi == FR_EPI_BNBWD))
-    FR_UNSUPPORTED("fr_conv3x3_s2_strip: this prologue / epilogue combination of the 64-channel layer writes partial rows "
-                   "in the strip kernel's layout, not the one fr_conv3x3_s2_strip_parts() reports (set FRHIP_S2ROLL=0 or "
-                   "use fr_conv_igemm)");
-#define SHAPE(c, wl, rows, wn, nw)                                   \
-  if (a.SC == c && WLo == wl) {                                      \
-    if (a.mode == 0) return by_pro<c, c, wl, rows, wn, nw, 0>(a, st); \
-    return by_pro<c, c, wl, rows, wn, nw, 1>(a, st);                  \
-  }
-  SHAPE(64, 56, 2, 2, 4)
-  // 128 -> 128: 7-row strips (196 pixels per weight pass) although only one workgroup then fits a CU: 0.166 -> 0.140 ms
-  // forward, 0.221 -> 0.206 ms gradient against the 4-row strips (the kernel is bound by the weight stream)
-  SHAPE(128, 28, 7, 8, 8)
-  if (a.SC == 256 && WLo == 14 && a.mode == 0) return by_pro<256, 128, 14, 14, 8, 8, 0, 2, 1>(a, st);
-  if (a.SC == 512 && WLo == 7 && a.B % 2 == 0) {
-    if (a.mode == 0) return by_pro<512, 128, 7, 7, 8, 8, 0, 4, 2>(a, st);
-    return by_pro<512, 128, 7, 7, 8, 8, 1, 4, 2>(a, st);
-  }
-  SHAPE(256, 14, 7, 8, 8)
-  SHAPE(512, 7, 7, 8, 8)
-#undef SHAPE
-  FR_UNSUPPORTED("fr_conv3x3_s2_strip: shape not in the table");
+  const FrConvInstance inst = select_s2(a.B, a.SC, WLo, a.mode, &a);
+  if (!inst.parts) FR_UNSUPPORTED("fr_conv3x3_s2_strip: shape not in the table");
+  if (a.w_frag && inst.launch == &fr_s2roll_launch)
+    FR_UNSUPPORTED("fr_conv3x3_s2_strip: the 64-channel rolling-window kernel takes the plain weight layout (w_frag)");
+  // fr_conv3x3_s2_strip_parts() has no epilogue argument: `part` was sized for the instance it selected.  If this launch's
+  // prologue / epilogue needs another one, its summing epilogue would write that instance's rows (a DIFFERENT number, in
+  // general) into the buffer -- refuse instead of overrunning it.
+  if (a.part && (a.epi == FR_EPI_STATS || a.epi == FR_EPI_PRELU_BWD || a.epi == FR_EPI_BNBWD) &&
+      inst.launch != select_s2(a.B, a.SC, WLo, a.mode, nullptr).launch)
+    FR_UNSUPPORTED("fr_conv3x3_s2_strip: this prologue / epilogue combination writes the partial rows of another instance "
+                   "than the one fr_conv3x3_s2_strip_parts() reports (switch that kernel off -- FRHIP_ROLL64=0, "
+                   "FRHIP_S2_WS=0 -- or use fr_conv_igemm)");
+  return inst.launch(a, st);
 }

@@ -387,16 +387,8 @@ int* ws_switch() {
 template <int CIN, int WL, int ROWS, int NIMG, int PRO>
 int launch(const FrConvArgs& a, hipStream_t st) {
   using C = WS<WL, ROWS, NIMG>;
-  static unsigned long long attr_done = 0;  // one bit per device
-  if (fr_attr_needed(attr_done)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_s2_ws_kernel<CIN, WL, ROWS, NIMG, PRO>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-    fr_attr_done(attr_done);
-  }
-  static const int* order = fr_option_slot("FRHIP_XCD_ORDER", 1);
-  FR_LAUNCH_KERNEL((conv3x3_s2_ws_kernel<CIN, WL, ROWS, NIMG, PRO>), dim3(a.B * C::NS / NIMG * (CIN / CW)), dim3(512), C::LDS,
-                   st, a, *order != 0);
-  FR_LAUNCH_CHECK();
+  return fr_launch_lds<&conv3x3_s2_ws_kernel<CIN, WL, ROWS, NIMG, PRO>>(a.B * C::NS / NIMG * (CIN / CW), 512, C::LDS, st, a,
+                                                                        fr_xcd_order());
 }
 
 template <int CIN, int WL, int ROWS, int NIMG>

@@ -474,28 +474,13 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_strip_kernel(const FrConvA
   }
 }
 
-// FRHIP_XCD_ORDER=0: workgroups take strips in dispatch order (A/B switch for tools/kbench.py)
-static int xcd_order() {
-  static const int* v = fr_option_slot("FRHIP_XCD_ORDER", 1);
-  return *v != 0;
-}
-
 template <int CIN, int COUT, int W, int ROWS, int WN, int NW, int NSPL, int PRO, int NIMG = 1, int KSPL = 1>
 int launch(const FrConvArgs& a, hipStream_t st) {
   using C = SC<CIN, COUT, W, ROWS, WN, NW, NIMG, KSPL>;
-  static unsigned long long attr_done = 0;  // one bit per device
-  if (fr_attr_needed(attr_done)) {
-    (void)hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&conv3x3_strip_kernel<CIN, COUT, W, ROWS, WN, NW, NSPL, PRO, NIMG, KSPL>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-    fr_attr_done(attr_done);
-  }
-  const int strips = a.B * C::NS / NIMG;
   if (a.epi == FR_EPI_STATS_X && (!a.part || !a.aux))
     FR_UNSUPPORTED("fr_conv3x3_strip: FR_EPI_STATS_X needs part and aux (its rows go to fr_bn_finalize_res)");
-  FR_LAUNCH_KERNEL((conv3x3_strip_kernel<CIN, COUT, W, ROWS, WN, NW, NSPL, PRO, NIMG, KSPL>),
-                     dim3(strips * NSPL), dim3(C::NTH), C::LDS, st, a, xcd_order());
-  FR_LAUNCH_CHECK();
+  return fr_launch_lds<&conv3x3_strip_kernel<CIN, COUT, W, ROWS, WN, NW, NSPL, PRO, NIMG, KSPL>>(
+      fr_strips_of<C, NIMG>(a.B) * NSPL, C::NTH, C::LDS, st, a, fr_xcd_order());
 }
 
 template <int CIN, int COUT, int W, int ROWS, int WN, int NW = 8, int NSPL = 1, int NIMG = 1, int KSPL = 1>
@@ -520,85 +505,46 @@ int by_pro(const FrConvArgs& a, hipStream_t st) {
   FR_UNSUPPORTED("fr_conv3x3_strip: unknown prologue");
 }
 
-}  // namespace
+// One line of the shape table: an LDS-strip instance.  It reads fragment-order weights and serves the two-source prologues
+// (FR_PRO_RESBN[_SE]) and the cross-moment epilogue (FR_EPI_STATS_X).
+template <int CIN, int COUT, int W, int ROWS, int WN, int NW = 8, int NSPL = 1, int NIMG = 1, int KSPL = 1>
+FrConvInstance strip(int B) {
+  return {fr_strips_of<SC<CIN, COUT, W, ROWS, WN, NW, NIMG, KSPL>, NIMG>(B), true, true,
+          &by_pro<CIN, COUT, W, ROWS, WN, NW, NSPL, NIMG, KSPL>};
+}
 
-// Shape table.  (Rounds 1-3 carried five generations of it behind FRHIP_STRIP_VARIANT=0..4 for same-box A/B runs: the
+// fewer whole-image workgroups than ~3/4 of the CUs: prefer the instances that split an image over two workgroups
+// FRHIP_SPLIT_STRIPS=1 forces them at any batch: 2 x B workgroups of half the output channels instead of B whole-image
+// ones, so that CUs taken by another resident kernel (RCCL's all-reduce under data parallelism) cost a proportional
+// share instead of a whole second round of workgroups (A/B switch for multi-GPU runs; slower stand-alone).
+bool small_batch(int B) {
+  static const int* force = fr_option_slot("FRHIP_SPLIT_STRIPS", 0);
+  return B <= 160 || *force == 1;
+}
+
+int two_pass_256_512(const FrConvArgs& a, hipStream_t st);
+
+// The shape table of the stride-1 family: the instance that serves (batch, channels, width, epilogue) under the current
+// switches, parts == 0 when none does.  fr_conv3x3_strip_parts / _takes_frag / _serves_resbn report it, fr_conv3x3_strip
+// launches it -- nothing else decides.
+// (Rounds 1-3 carried five generations of it behind FRHIP_STRIP_VARIANT=0..4 for same-box A/B runs: the
 // one-workgroup-per-CU instances of the 64- and 128-channel layers, the 7 x 2 tile instances of the stage-entry shapes and
 // the one- / two-image 7x7 instances as the DEFAULT.  Table 4 -- 4-wave workgroups, two resident per CU, at 64 / 128
 // channels; one tile column per wave at the stage entries; 2 - 4 images per workgroup at 7x7 -- ran 0.8 ms per step faster
 // than table 0 and has a round of green tests behind it; the older generations were removed in round 4, their measurements
 // stay in the comments below and in DESIGN.md section 3.)
-// fewer whole-image workgroups than ~3/4 of the CUs: prefer the instances that split an image over two workgroups
-// FRHIP_SPLIT_STRIPS=1 forces them at any batch: 2 x B workgroups of half the output channels instead of B whole-image
-// ones, so that CUs taken by another resident kernel (RCCL's all-reduce under data parallelism) cost a proportional
-// share instead of a whole second round of workgroups (A/B switch for multi-GPU runs; slower stand-alone).
-static bool small_batch(int B) {
-  static const int* force = fr_option_slot("FRHIP_SPLIT_STRIPS", 0);
-  return B <= 160 || *force == 1;
-}
-
-// rows per strip for a shape (0 = not served)
-static int strip_rows(int Cin, int Cout, int W) {
-#define SHAPE(ci, co, w, rows) \
-  if (Cin == ci && Cout == co && W == w) return rows;
-  SHAPE(64, 64, 112, 2)
-  SHAPE(64, 64, 56, 7)
-  SHAPE(64, 128, 56, 4)
-  SHAPE(128, 64, 56, 7)
-  SHAPE(128, 128, 28, 7)
-  SHAPE(128, 256, 28, 7)
-  SHAPE(256, 128, 28, 7)
-  SHAPE(256, 256, 14, 14)
-  SHAPE(256, 512, 14, 14)
-  SHAPE(512, 256, 14, 14)
-  SHAPE(512, 512, 7, 7)
-#undef SHAPE
-  return 0;
-}
-
-// The two-source prologues (FR_PRO_RESBN[_SE]) and the cross-moment epilogue (FR_EPI_STATS_X) exist on the LDS-strip instances
-// of the square layers; the 64-channel layers run on the rolling-window kernel, which takes neither.
-extern "C" int fr_conv3x3_strip_serves_resbn(int B, int C, int W) {
-  if (C == 64 && (W == 112 || W == 56) && fr_roll64_enabled()) return 0;
-  return fr_conv3x3_strip_parts(B, C, C, W, FR_EPI_PRELU_BWD) > 0 ? 1 : 0;
-}
-
-extern "C" int fr_conv3x3_strip_takes_frag(int B, int Cin, int Cout, int W) {
-  if (Cin == 64 && Cout == 64 && (W == 112 || W == 56) && fr_roll64_enabled()) return 0;
-  return fr_conv3x3_strip_parts(B, Cin, Cout, W, FR_EPI_STORE) > 0 ? 1 : 0;
-}
-
-// Number of partial rows the kernel writes into `part` (= workgroups) for a supported shape, 0 if unsupported.
-extern "C" int fr_conv3x3_strip_parts(int B, int Cin, int Cout, int W, int epi) {
-  if (Cin == 256 && Cout == 512 && W == 14 && epi != FR_EPI_STORE) return 0;
-  if (Cin == 64 && Cout == 64 && (W == 112 || W == 56) && fr_roll64_enabled()) return fr_roll64_parts(B, W);
-  const int rows = strip_rows(Cin, Cout, W);
-  if (Cin == 512 && Cout == 512 && W == 7 && B % 2 == 0 && small_batch(B)) return B / 2;
-  if (Cin == 512 && Cout == 512 && W == 7 && B % 4 == 0) return B / 4;  // four images per strip
-  if (Cin == 512 && Cout == 512 && W == 7 && B % 2 == 0) return B / 2;  // two images per strip
-  return rows ? B * (W / rows) : 0;
-}
-
-extern "C" int fr_conv3x3_strip(const FrConvArgs* args, void* stream) {
-  const FrConvArgs& a = *args;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.RH != a.SH || a.RW != a.SW || a.SH != a.SW ||
-      a.out_f32 || a.splitk > 1 || a.bias || a.epi == FR_EPI_MARGIN || a.epi == FR_EPI_ATOMIC)
-    FR_UNSUPPORTED("fr_conv3x3_strip: only square stride-1 3x3 bf16 convolutions");
-  if (a.lda % 8 || a.ldc % 8 || (a.aux && a.ldaux % 8)) FR_UNSUPPORTED("fr_conv3x3_strip: strides must be 16-byte multiples");
-  if (a.SC == 64 && a.N == 64 && (a.SW == 112 || a.SW == 56) && fr_roll64_enabled()) {
-    if (a.w_frag) FR_UNSUPPORTED("fr_conv3x3_strip: the 64-channel rolling-window kernel takes the plain weight layout (w_frag)");
-    return fr_roll64_launch(a, st);
-  }
-#define SHAPE(ci, co, w, rows, wn, nw) \
-  if (a.SC == ci && a.N == co && a.SW == w) return by_pro<ci, co, w, rows, wn, nw>(a, st);
+FrConvInstance select_strip(int B, int Cin, int Cout, int W, int epi) {
+  const auto is = [&](int ci, int co, int w) { return Cin == ci && Cout == co && W == w; };
+  // 64 -> 64 at 112 / 56: the rolling-window kernel (conv3x3_roll64.hip; plain weight layout, one-source prologues);
+  // FRHIP_ROLL64=0 leaves them to the two strip instances below
+  if ((is(64, 64, 112) || is(64, 64, 56)) && fr_roll64_enabled()) return {fr_roll64_parts(B, W), false, false, &fr_roll64_launch};
   // (round 3: 128 -> 128 @28 as 8 waves x (25 tiles x 1 column) on half images, one workgroup per CU, half the weight stream:
   // 0.143 / 0.151 ms forward / data gradient against 0.068 / 0.070 for the two resident 4-wave workgroups below)
   // 4-wave workgroups, two resident per CU -- measured (tools/kbench.py, B=256) 1.1-1.45x over the 8-wave one-per-CU
   // instances <64,64,112,4,2,8>, <64,64,56,7,2,8>, <128,128,28,14,4,8> of round 1 (removed in round 4)
-  SHAPE(64, 64, 112, 2, 2, 4)
-  SHAPE(64, 64, 56, 7, 2, 4)
-  SHAPE(128, 128, 28, 7, 4, 4)
+  if (is(64, 64, 112)) return strip<64, 64, 112, 2, 2, 4>(B);
+  if (is(64, 64, 56)) return strip<64, 64, 56, 7, 2, 4>(B);
+  if (is(128, 128, 28)) return strip<128, 128, 28, 7, 4, 4>(B);
   // 256 -> 256 @14 (half of all FLOPs): 8 waves x (13 x 2) accumulator tiles on the whole image.  Measured and rejected
   // at B=256 (tools/kbench.py): 4-wave half-height strips 0.101 ms, the same with the channels split over two
   // workgroups (NSPL = 2, no spills) 0.093 ms, 8 waves x (7 x 4) tiles 0.114 ms (spills) -- against 0.062 ms here.
@@ -616,21 +562,21 @@ extern "C" int fr_conv3x3_strip(const FrConvArgs* args, void* stream) {
   // Not instantiated.
   // small batches (fewer whole-image workgroups than CUs): split the output channels over two workgroups per image
   // (measured at B = 128: 0.034 instead of 0.049 ms per launch -- IR-SE-101 trains at 128 images per GPU)
-  if (a.SC == 256 && a.N == 256 && a.SW == 14 && small_batch(a.B)) return by_pro<256, 128, 14, 14, 8, 8, 2>(a, st);
-  SHAPE(256, 256, 14, 14, 8, 8)
+  if (is(256, 256, 14) && small_batch(B)) return strip<256, 128, 14, 14, 8, 8, 2>(B);
+  if (is(256, 256, 14)) return strip<256, 256, 14, 14, 8, 8>(B);
   // 64 -> 128 @56 (one forward launch per step): 4-row strips, two resident 4-wave workgroups per CU: 0.170-0.174 -> 0.159-0.160 ms
   // against the 7-row 8-wave instance <64,128,56,7,4,8> (removed)
-  SHAPE(64, 128, 56, 4, 4, 4)
+  if (is(64, 128, 56)) return strip<64, 128, 56, 4, 4, 4>(B);
   // Round 3: what a wave pays per MFMA is its private weight stream (16 B per lane from L2 for every (tap, 32 channels,
   // 16 output channels)): an instance is fast when one weight fragment feeds ~13 M tiles.  The data gradients of the three
   // stage-entry convolutions ran 7 tiles x 2 columns per wave (<128,64,56,7,2,8>, <256,128,28,7,4,8>, <512,256,14,7,8,8>:
   // removed in round 4); with ONE 16-channel column per wave and 13 tiles (128 -> 64: 4 x 2 waves; 256 -> 128: 8 x 1;
   // 512 -> 256: the whole image in two channel stages, output channels over two workgroups) the same launches take
   // 0.254 -> 0.202, 0.202 -> 0.150 and 0.177 -> 0.132 ms (same box), the step 0.2 ms less.
-  SHAPE(128, 64, 56, 7, 4, 8)
-  SHAPE(256, 128, 28, 7, 8, 8)
-  if (a.SC == 512 && a.N == 256 && a.SW == 14) return by_pro<512, 128, 14, 14, 8, 8, 2, 1, 2>(a, st);
-  SHAPE(128, 256, 28, 7, 8, 8)
+  if (is(128, 64, 56)) return strip<128, 64, 56, 7, 4, 8>(B);
+  if (is(256, 128, 28)) return strip<256, 128, 28, 7, 8, 8>(B);
+  if (is(512, 256, 14)) return strip<512, 128, 14, 14, 8, 8, 2, 1, 2>(B);
+  if (is(128, 256, 28)) return strip<128, 256, 28, 7, 8, 8>(B);
   // 512 -> 512 @7: two images per workgroup, 256 resident input channels at a time, output channels split over two
   // workgroups: every weight fragment now feeds 98 pixels instead of 49 and the M tiles are 12 % instead of 23 % padding
   // Round 3: FOUR images per workgroup, 128 resident input channels at a time (four stages of the strip), output channels
@@ -639,30 +585,57 @@ extern "C" int fr_conv3x3_strip(const FrConvArgs* args, void* stream) {
   // data gradient at B = 256 (tools/kbench.py, same box), no scratch, 100 KB of LDS.
   // ... at small batches (IR-SE-101 trains at 128 images per GPU: 32 four-image strips x 4 = 128 workgroups would leave half
   // the CUs idle) two images per workgroup with the same split: B / 2 x 4 workgroups
-  if (a.SC == 512 && a.N == 512 && a.SW == 7 && a.B % 2 == 0 && small_batch(a.B))
-    return by_pro<512, 128, 7, 7, 8, 8, 4, 2, 2>(a, st);
-  if (a.SC == 512 && a.N == 512 && a.SW == 7 && a.B % 4 == 0) return by_pro<512, 128, 7, 7, 8, 8, 4, 4, 4>(a, st);
-  if (a.SC == 512 && a.N == 512 && a.SW == 7 && a.B % 2 == 0) return by_pro<512, 256, 7, 7, 8, 8, 2, 2, 2>(a, st);
-  SHAPE(512, 512, 7, 7, 8, 8)
-#undef SHAPE
-  if (a.SC == 256 && a.N == 512 && a.SW == 14 && a.epi == FR_EPI_STORE) {
-    // 256 -> 512 @14 (one layer per network): two passes over 256 output channels each reuse the 256x256 instance
-    // (a 512-wide accumulator tile would spill); the strip is simply loaded twice
-    FrConvArgs h = a;
-    h.N = 256;
-    for (int half = 0; half < 2; ++half) {
-      h.w = reinterpret_cast<const bf16_t*>(a.w) + (size_t)half * 256 * 9 * 256;
-      h.out = reinterpret_cast<bf16_t*>(a.out) + half * 256;
-      if ((a.pro == FR_PRO_RESBN || a.pro == FR_PRO_RESBN_SE) && half == 1) {  // the first pass has materialised the residual sum: plain BN1 on it
-        h.pro = FR_PRO_BN;
-        h.src = a.pro_out;
-        h.pro_a = a.pro_c;
-        h.pro_b = a.pro_d;
-      }
-      const int rc = small_batch(a.B) ? by_pro<256, 128, 14, 14, 8, 8, 2>(h, st) : by_pro<256, 256, 14, 14, 8, 8>(h, st);
-      if (rc) return rc;
-    }
-    return 0;
+  if (is(512, 512, 7) && B % 2 == 0 && small_batch(B)) return strip<512, 128, 7, 7, 8, 8, 4, 2, 2>(B);
+  if (is(512, 512, 7) && B % 4 == 0) return strip<512, 128, 7, 7, 8, 8, 4, 4, 4>(B);
+  if (is(512, 512, 7) && B % 2 == 0) return strip<512, 256, 7, 7, 8, 8, 2, 2, 2>(B);
+  if (is(512, 512, 7)) return strip<512, 512, 7, 7, 8, 8>(B);
+  // 256 -> 512 @14 (one layer per network), plain store only: two passes of the 256 -> 256 @14 line above
+  if (is(256, 512, 14) && epi == FR_EPI_STORE) {
+    FrConvInstance half = select_strip(B, 256, 256, 14, epi);
+    half.launch = &two_pass_256_512;
+    return half;
   }
-  FR_UNSUPPORTED("fr_conv3x3_strip: shape not in the strip table");
+  return {};
+}
+
+// 256 -> 512 @14: two passes over 256 output channels each reuse the 256x256 instance (a 512-wide accumulator tile would
+// spill); the strip is simply loaded twice
+int two_pass_256_512(const FrConvArgs& a, hipStream_t st) {
+  FrConvArgs h = a;
+  h.N = 256;
+  for (int half = 0; half < 2; ++half) {
+    h.w = reinterpret_cast<const bf16_t*>(a.w) + (size_t)half * 256 * 9 * 256;
+    h.out = reinterpret_cast<bf16_t*>(a.out) + half * 256;
+    if ((a.pro == FR_PRO_RESBN || a.pro == FR_PRO_RESBN_SE) && half == 1) {  // the first pass has materialised the residual sum: plain BN1 on it
+      h.pro = FR_PRO_BN;
+      h.src = a.pro_out;
+      h.pro_a = a.pro_c;
+      h.pro_b = a.pro_d;
+    }
+    const int rc = select_strip(a.B, 256, 256, 14, a.epi).launch(h, st);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int fr_conv3x3_strip_serves_resbn(int B, int C, int W) { return select_strip(B, C, C, W, FR_EPI_PRELU_BWD).resbn; }
+
+extern "C" int fr_conv3x3_strip_takes_frag(int B, int Cin, int Cout, int W) { return select_strip(B, Cin, Cout, W, FR_EPI_STORE).frag; }
+
+// Number of partial rows the kernel writes into `part` (= strips) for a supported shape, 0 if unsupported.
+extern "C" int fr_conv3x3_strip_parts(int B, int Cin, int Cout, int W, int epi) { return select_strip(B, Cin, Cout, W, epi).parts; }
+
+extern "C" int fr_conv3x3_strip(const FrConvArgs* args, void* stream) {
+  const FrConvArgs& a = *args;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.RH != a.SH || a.RW != a.SW || a.SH != a.SW ||
+      a.out_f32 || a.splitk > 1 || a.bias || a.epi == FR_EPI_MARGIN || a.epi == FR_EPI_ATOMIC)
+    FR_UNSUPPORTED("fr_conv3x3_strip: only square stride-1 3x3 bf16 convolutions");
+  if (a.lda % 8 || a.ldc % 8 || (a.aux && a.ldaux % 8)) FR_UNSUPPORTED("fr_conv3x3_strip: strides must be 16-byte multiples");
+  const FrConvInstance inst = select_strip(a.B, a.SC, a.N, a.SW, a.epi);
+  if (!inst.parts) FR_UNSUPPORTED("fr_conv3x3_strip: shape not in the strip table");
+  if (a.w_frag && !inst.frag) FR_UNSUPPORTED("fr_conv3x3_strip: the 64-channel rolling-window kernel takes the plain weight layout (w_frag)");
+  return inst.launch(a, st);
 }

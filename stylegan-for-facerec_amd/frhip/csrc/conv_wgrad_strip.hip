@@ -417,9 +417,6 @@ int by_pro(const FrWgradArgs& a, hipStream_t st) {
   FR_UNSUPPORTED("fr_conv_wgrad_strip: unknown prologue");
 }
 
-// the 28x28 / 14x14 instances use the row-aligned K layout (round 2; its A/B switch left in round 5)
-bool row_k() { return true; }
-
 }  // namespace
 
 // 1 when (W) is in the strip table and the channel counts are multiples of 64
@@ -471,8 +468,9 @@ extern "C" int fr_conv_wgrad_strip(const FrWgradArgs* args, void* stream) {
   switch (a.SW) {
     case 112: return by_pro<112, 2, 1, 8>(a, st);
     case 56: return by_pro<56, 4, 1, 8>(a, st);
-    case 28: return row_k() ? by_pro<28, 7, 1, 8, false, true>(a, st) : by_pro<28, 7, 1, 8>(a, st);
-    case 14: return row_k() ? by_pro<14, 14, 1, 8, false, true>(a, st) : by_pro<14, 14, 1, 8>(a, st);
+    // 28x28 / 14x14: the row-aligned K layout (round 2; its A/B switch left in round 5)
+    case 28: return by_pro<28, 7, 1, 8, false, true>(a, st);
+    case 14: return by_pro<14, 14, 1, 8, false, true>(a, st);
     case 7: return by_pro<7, 7, 4, 8>(a, st);
   }
   FR_UNSUPPORTED("fr_conv_wgrad_strip: width not in the strip table");

@@ -6,17 +6,34 @@
 
 // run-time switch `name` (api.hip): pointer to its cached value (environment variable of that name, else dflt)
 int* fr_option_slot(const char* name, int dflt);
+// FRHIP_XCD_ORDER=0: the strip kernels' workgroups take strips in dispatch order (A/B switch for tools/kbench.py); else 1
+int fr_xcd_order();
+
+// What a convolution family's shape table (select_strip, conv3x3_strip.hip; select_s2, conv3x3_s2_strip.hip) answers for a
+// problem: the host queries report these fields and the entry point calls `launch`, so the two cannot disagree.
+struct FrConvInstance {
+  int parts;   // partial-sum rows the launch writes into FrConvArgs.part; 0: the family does not serve the problem
+  bool frag;   // reads fragment-order weights (FrConvArgs.w_frag)
+  bool resbn;  // serves the two-source prologues (FR_PRO_RESBN[_SE]) and FR_EPI_STATS_X
+  int (*launch)(const FrConvArgs&, hipStream_t);
+};
+// strips of a batch for a strip geometry C (SC / S2) with NIMG images per workgroup: the partial-sum rows of a forward
+// launch.  A table line computes `parts` from it and the launch its grid (x NSPL), so the two cannot differ.
+template <class C, int NIMG>
+constexpr int fr_strips_of(int B) {
+  return B * C::NS / NIMG;
+}
 
 // out[i] = sum_g slab[g][i] in the fixed order g = 0, 1, ... (n elements, n % 4 == 0); conv_wgrad_strip.hip
 int fr_launch_reduce_slabs(const float* slab, int groups, long long n, float* out, hipStream_t st);
 
-// 64 -> 64 stride-1 3x3 layers on the rolling-window kernel (conv3x3_roll64.hip); dispatched from fr_conv3x3_strip
+// 64 -> 64 stride-1 3x3 layers on the rolling-window kernel (conv3x3_roll64.hip); a line of select_strip
 bool fr_roll64_enabled();
 int fr_roll64_parts(int B, int W);
 int fr_roll64_launch(const FrConvArgs& a, hipStream_t st);
 
 // 64-channel stride-2 3x3 layer (112 -> 56) and its data gradient on the rolling-window kernel (conv3x3_s2_roll64.hip);
-// dispatched from fr_conv3x3_s2_strip
+// a line of select_s2
 bool fr_s2roll_serves(const FrConvArgs& a);
 int fr_s2roll_parts(int B);
 int fr_s2roll_launch(const FrConvArgs& a, hipStream_t st);
@@ -31,8 +48,8 @@ int fr_wgrad_roll_launch(const FrWgradArgs& a, hipStream_t st);
 bool fr_wgrad_s2roll_serves(const FrWgradArgs& a);
 int fr_wgrad_s2roll_launch(const FrWgradArgs& a, hipStream_t st);
 
-// stride-2 3x3 forward at 128 / 256 / 512 channels on the warp-specialised kernel (conv3x3_s2_ws.hip); dispatched from
-// fr_conv3x3_s2_strip.  fr_s2ws_strips: partial-sum rows of a served (B, C, low-res width), 0 = not served.
+// stride-2 3x3 forward at 128 / 256 / 512 channels on the warp-specialised kernel (conv3x3_s2_ws.hip); a line of
+// select_s2.  fr_s2ws_strips: partial-sum rows of a served (B, C, low-res width), 0 = not served.
 bool fr_s2ws_serves(const FrConvArgs& a);
 int fr_s2ws_strips(int B, int C, int WL);
 int fr_s2ws_launch(const FrConvArgs& a, hipStream_t st);

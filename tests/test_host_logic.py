@@ -477,6 +477,34 @@ def test_dispatch_geometry_of_the_strip_tables():
     assert ws(96, 64, 56) == 0 and ws(64, 64, 20) == 0
 
 
+def test_dispatch_queries_answer_as_recorded(golden_dir):
+    """The five queries behind the strip-convolution dispatch, swept over every batch 1 .. 520, the channel counts and
+    widths of tests/dispatch_sweep.py (served and unserved), all nine epilogues, both modes and every setting of
+    FRHIP_ROLL64 / FRHIP_S2_WS / FRHIP_SPLIT_STRIPS, with the row-segment hooks at their default and forced: the answers
+    equal, exactly, the ones recorded from the library BEFORE the shape tables were folded into one selector per family
+    (tests/golden/make_golden_dispatch.py).  A different answer is a different instance -- and a partial-sum buffer
+    of the wrong size."""
+    import dispatch_sweep as S
+    from frhip import _lib
+    with np.load(os.path.join(golden_dir, "g17_dispatch.npz")) as z:
+        gold = {k: z[k] for k in z.files}
+    index = json.loads(gold["index"].tobytes().decode())
+    assert len(index) == 16 * len(S.QUERIES)
+    with S.Switches(_lib.lib) as sw:
+        for setting in S.settings():
+            sw.set(setting)
+            for query in S.QUERIES:
+                name = index[S.setting_key(setting, query)]
+                want = np.repeat(gold["v_" + name], gold["c_" + name])
+                got = S.answers(_lib.lib, query)
+                assert got.shape == want.shape, (query, got.shape, want.shape)
+                bad = np.flatnonzero(got != want)
+                if len(bad):
+                    k = int(bad[0])
+                    pytest.fail("%s%r under %r answers %d, recorded %d (first of %d differences)"
+                                % (query, S.arguments(query, k), setting, int(got[k]), int(want[k]), len(bad)))
+
+
 def test_configs_select_the_compute_dtype():
     """COMPUTE_DTYPE is the config key that selects the numerics of the backbone (reference configs: train.py:41-90 have
     none, so train.py reads it with cfg.get): the two BUPT configs run the bf16 path bench.py times, the synthetic smoke
