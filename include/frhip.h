@@ -613,6 +613,24 @@ int fr_pair_counts(const float* E, int ldE, int M, int D, const float* thr, int 
 /* rows of `partials` a call with (M, mode, group) writes (host arithmetic only); < 0: unsupported argument */
 int fr_pair_counts_parts(int M, int mode, int group);
 
+/* ---- Histogram of the same pair scores over a window of their integer keys: one pass of the radix select that finds the
+ *      exact threshold at a chosen FPR (the np.interp lines of rb-webface/scripts/test_RB_Webface.py:153-233 interpolate
+ *      between twenty hand-placed thresholds instead).  E, ldE, M, D, mode and group as for fr_pair_counts, and the scores
+ *      are bit for bit the ones fr_pair_counts compares (one main loop, csrc/pair_tile.h).  The key of a score s keeps
+ *      the order of the scores and has no NaN:
+ *   u = bits(s == 0 ? +0.0f : s);   key = (u & 0x80000000) ? ~u : (u | 0x80000000)
+ *   hist[0]      = #{ pairs : key <  key_lo }
+ *   hist[1 + b]  = #{ pairs : key_lo + (b << shift) <= key < key_lo + ((b + 1) << shift) },   0 <= b < NB
+ *   hist[NB + 1] = #{ pairs : key >= key_lo + (NB << shift) }
+ * A NaN score (a zero row) is in no slot.  1 <= NB <= 2048, 0 <= shift <= 21, key_lo + (NB << shift) <= 2^32.  Persistent
+ * workgroups bin into LDS and write one row each of partials [fr_pair_hist_parts()][NB + 2] uint32; a second kernel of the
+ * same call sums the rows into hist [NB + 2] int64.  No global atomics: bit-identical from run to run.  Allocates nothing. */
+int fr_pair_hist(const float* E, int ldE, int M, int D, uint32_t key_lo, int shift, int NB, int mode, int group,
+                 uint32_t* partials, int64_t* hist, void* stream);
+/* rows of `partials` a call with (M, mode, group) writes (host arithmetic only); < 0: unsupported argument, among them an
+ * M so large that one workgroup would see 2^32 pairs */
+int fr_pair_hist_parts(int M, int mode, int group);
+
 /* ---- multi-tensor SGD with momentum (torch.optim.SGD defaults; train.py:196)
  *   d = g + wd*p ; buf = momentum*buf + d ; p -= lr*buf      (buf starts at 0, so the first step gives buf = d)
  * table_dev: device array of tensor records; chunks_dev: device array of (tensor index, chunk index) pairs,
