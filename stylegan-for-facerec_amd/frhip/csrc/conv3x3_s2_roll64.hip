@@ -205,10 +205,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_s2_roll64_kernel(const FrConvA
             const unsigned keep = ((okmask >> u) & 1u) ? 0xFFFFFFFFu : 0u;
             U128 x = st[u];
             if (PRO != FR_PRO_NONE) {  // pro2 (frhip_internal.h): 5 / 7 vector instructions per dword instead of 11-12
-              x.x = pro2<PRO>(x.x, pa[0], pb[0], pa[1], pb[1]);
-              x.y = pro2<PRO>(x.y, pa[2], pb[2], pa[3], pb[3]);
-              x.z = pro2<PRO>(x.z, pa[4], pb[4], pa[5], pb[5]);
-              x.w = pro2<PRO>(x.w, pa[6], pb[6], pa[7], pb[7]);
+              x = pro8<PRO>(x, pa, pb);
             }
             x.x &= keep;
             x.y &= keep;

@@ -33,7 +33,7 @@
 
 namespace {
 
-constexpr int CT = 64;             // co and ci tile
+constexpr int CT = FR_WGRAD_CT;    // co and ci tile
 constexpr int TSTR = CT * 2 + 32;  // LDS row stride (bytes): conflict-free transposing reads (see conv_wgrad_strip.hip)
 constexpr int NLT = 256;           // data-moving threads (waves 4-7)
 
@@ -85,27 +85,102 @@ struct RL {  // LDS layout: buffer 0 holds the even phases of the schedule, buff
   static_assert(LDS <= 160 * 1024, "LDS budget");
 };
 
-// pro2<PRO>: the BN / PReLU prologue on one dword (two bf16), written as instructions -- frhip_internal.h
+// pro8<PRO>: the BN / PReLU prologue on one 16-byte chunk, written as instructions -- frhip_internal.h
 
-#define LDS_FENCE_BARRIER_RAW() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
+// ---------------------------------------------------------------------------------------------------------------------
+// What the three kernels of this file share: the hand-over barrier and its diagnostic stamps, the workgroup's tile and
+// run, the LDS zero fill, the deferred slab sum, the lane geometry of the computing
+// waves and the slab store.  The loader state, the data-moving schedules, the accumulator zeroing and the item loop
+// (run_phase) stay in each kernel: written once they changed the compiled kernels (profiles/wgrad_ws_refactor.txt).
 
+__device__ __forceinline__ void lds_fence_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// No stamps: the product build (conv_wgrad_s2roll_kernel carries none in any build and calls the fence directly).
+struct NoStamps {
+  __device__ __forceinline__ static unsigned long long now() { return 0; }
+  __device__ __forceinline__ unsigned long long since_start(unsigned long long) const { return 0; }
+  __device__ __forceinline__ void put(int, unsigned long long) const {}
+  __device__ __forceinline__ void barrier() { lds_fence_barrier(); }
+  __device__ __forceinline__ unsigned long long loop_begin() { return 0; }
+  __device__ __forceinline__ void loop_end(int, int) const {}
+  __device__ __forceinline__ void kernel_end() const {}
+};
 // Diagnostic build (make stamps; never loaded by the product): per workgroup, cycles (s_memtime) of the whole kernel and
-// of the image loop, and the cycles wave 0 (computing) / wave 4 (data-moving) spend inside the hand-over barriers.
+// of the image loop, and the cycles wave 0 (computing) / wave 4 (data-moving) spend inside the hand-over barriers.  Qword
+// slots of a workgroup: 0 kernel cycles, 1 / 2 loop cycles / barrier wait of wave 0, 3 / 4 barrier wait / loop cycles of
+// wave 4, 5 kernel time (s_memrealtime), 6 images or phases of the run, 8 LDS zero fill, 9 slab sum of the previous
+// launch, 10 wait for the first tiles.  One thread of a wave calls put / loop_end / kernel_end.
 #ifdef FRHIP_STAMPS
 __device__ unsigned long long* fr_stamp_buf_wgr = nullptr;
-#define TSTAMP() __builtin_amdgcn_s_memtime()
-// one region of 4096 workgroups x 16 qwords per width (14, 28, 56, 112), so that a whole training step leaves the stamps
-// of the LAST launch of every width
-#define STAMP_SLOT(W) ((size_t)((W) == 14 ? 0 : (W) == 28 ? 1 : (W) == 56 ? 2 : 3) * 4096 * 16 + (size_t)blockIdx.x * 16)
-#define LDS_FENCE_BARRIER()                         \
-  do {                                              \
-    const unsigned long long t0__ = TSTAMP();       \
-    LDS_FENCE_BARRIER_RAW();                        \
-    bar_wait += TSTAMP() - t0__;                    \
-  } while (0)
+template <int W>
+struct Stamps {
+  unsigned long long bar_wait = 0, t_loop = 0;
+  const unsigned long long t_start = now(), rt_start = __builtin_amdgcn_s_memrealtime();
+  __device__ __forceinline__ static unsigned long long now() { return __builtin_amdgcn_s_memtime(); }
+  __device__ __forceinline__ unsigned long long since_start(unsigned long long t) const { return t - t_start; }
+  // one region of 4096 workgroups x 16 qwords per width (14, 28, 56, 112), so that a whole training step leaves the stamps
+  // of the LAST launch of every width
+  __device__ __forceinline__ void put(int slot, unsigned long long v) const {
+    if (fr_stamp_buf_wgr)
+      fr_stamp_buf_wgr[(size_t)(W == 14 ? 0 : W == 28 ? 1 : W == 56 ? 2 : 3) * 4096 * 16 + (size_t)blockIdx.x * 16 + slot] = v;
+  }
+  __device__ __forceinline__ void barrier() {
+    const unsigned long long t0 = now();
+    lds_fence_barrier();
+    bar_wait += now() - t0;
+  }
+  __device__ __forceinline__ unsigned long long loop_begin() {  // behind B0: the loop's cycles and barrier waits count from here
+    bar_wait = 0;
+    return t_loop = now();
+  }
+  __device__ __forceinline__ void loop_end(int slot_cycles, int slot_wait) const {
+    put(slot_wait, bar_wait);
+    put(slot_cycles, now() - t_loop);
+  }
+  __device__ __forceinline__ void kernel_end() const {
+    put(0, now() - t_start);
+    put(5, __builtin_amdgcn_s_memrealtime() - rt_start);
+  }
+};
 #else
-#define LDS_FENCE_BARRIER() LDS_FENCE_BARRIER_RAW()
+template <int W>
+using Stamps = NoStamps;
 #endif
+
+// block -> (group, tile): consecutive logical ids (= all tiles of a group) share an XCD
+struct WgTile {
+  int group, cot, cit;
+};
+__device__ __forceinline__ WgTile wg_tile(const FrWgradArgs& p) {
+  const int nblk = gridDim.x;
+  int bid = blockIdx.x;
+  {
+    const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;
+    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+  }
+  const int cit_n = p.SC / CT, tiles = (p.Cout / CT) * cit_n;
+  const int group = bid / tiles, tile = bid - group * tiles;
+  const int cot = tile / cit_n, cit = tile - cot * cit_n;
+  return {group, cot, cit};
+}
+// the group's share [begin, end) of the launch's `units` (images, phases or virtual rows), n of them
+struct WgRun {
+  int begin, end, n;
+};
+__device__ __forceinline__ WgRun wg_run(const FrWgradArgs& p, int group, int units) {
+  const int per = (units + p.nsplit - 1) / p.nsplit;
+  const int begin = group * per;
+  int end = begin + per;
+  if (end > units) end = units;
+  return {begin, end, end > begin ? end - begin : 0};
+}
+
+// zero the whole tile memory once: halo rows / columns, surplus K slots and tails stay zero for the whole launch
+template <int LDS>
+__device__ __forceinline__ void zero_lds(char* smem, int tid) {
+  for (int idx = tid; idx < LDS / 16; idx += 512) st16(smem + idx * 16, zero16());
+  __syncthreads();
+}
 
 // This workgroup's share of the deferred slab sum of the PREVIOUS weight-gradient launch (FrWgradArgs.prev_*), split between
 // the wave roles of the three kernels below: [e0, cut) by the computing waves (tid < 256, two elements per thread and
@@ -122,6 +197,24 @@ __device__ __forceinline__ void fold_prev_share(const FrWgradArgs& p, bool mover
   else if (cut < e1) slab_sum_range<256, 1>(p.prev_slab, p.prev_groups, n4, cut, e1, p.prev_dw, tid - 256);
 }
 
+// A computing lane (waves 0-3) inside the 16 x 16 MFMA tiles
+struct Lane {
+  int li, lq;
+  int colb;  // byte offset of this lane's 4-channel group inside a 16-channel tile
+  int lrow;  // byte offset of its tile row
+  __device__ __forceinline__ explicit Lane(int lane)
+      : li(lane & 15), lq(lane >> 4), colb((4 * (li & 3)) * 2), lrow((4 * lq + (li >> 2)) * TSTR) {}
+};
+// slab[co][tap][ci] of this workgroup's group: lane (li, lq) of the wave holds rows co0 + 16 t + r of column ci
+__device__ __forceinline__ void store_slab(float* __restrict__ slab, const f32x4 (&acc)[4][9], int SC, int co0, int ci) {
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) slab[((size_t)(co0 + t * 16 + r) * 9 + tap) * (size_t)SC + ci] = acc[t][tap][r];
+}
+
 template <int W, int PRO>
 __global__ __launch_bounds__(512, 2) void conv_wgrad_roll_kernel(const FrWgradArgs p) {
   using C = RC<W>;
@@ -130,32 +223,14 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_roll_kernel(const FrWgradAr
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-
-  // block -> (group, tile): consecutive logical ids (= all tiles of a group) share an XCD
-  const int nblk = gridDim.x;
-  int bid = blockIdx.x;
-  {
-    const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  const int cit_n = p.SC / CT, tiles = (p.Cout / CT) * cit_n;
-  const int group = bid / tiles, tile = bid - group * tiles;
-  const int cot = tile / cit_n, cit = tile - cot * cit_n;
+  const WgTile wt = wg_tile(p);
+  const int group = wt.group, cot = wt.cot, cit = wt.cit;
   // work of a group: whole images (two-phase schedule) or a run of phases that may start inside an image (uniform)
-  const int units = NPH == 2 ? p.B : p.B * NPH;
-  const int per = (units + p.nsplit - 1) / p.nsplit;
-  const int b_begin = group * per;
-  int b_end = b_begin + per;
-  if (b_end > units) b_end = units;
-  const int nimg = b_end > b_begin ? b_end - b_begin : 0;  // images / phases of this workgroup
+  const WgRun run = wg_run(p, group, NPH == 2 ? p.B : p.B * NPH);
+  const int b_begin = run.begin, b_end = run.end, nimg = run.n;  // images / phases of this workgroup
 
-#ifdef FRHIP_STAMPS
-  unsigned long long bar_wait = 0;
-  const unsigned long long t_start = TSTAMP(), rt_start = __builtin_amdgcn_s_memrealtime();
-#endif
-  // zero both buffers once: halo rows / columns, surplus K slots and tails stay zero for the whole launch
-  for (int idx = tid; idx < L::LDS / 16; idx += 512) st16(smem + idx * 16, zero16());
-  __syncthreads();
+  Stamps<W> st;
+  zero_lds<L::LDS>(smem, tid);
 
   // Deferred slab sum of the PREVIOUS weight-gradient launch of this stream (FrWgradArgs.prev_*): every workgroup adds its
   // share of that launch's slabs in the fixed order g = 0, 1, ... while its own first tiles are in flight -- the sum no
@@ -164,16 +239,12 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_roll_kernel(const FrWgradAr
   // share with two elements per thread and pass, the data-moving waves one third with one element, squeezed in between
   // their first two tile requests -- one memory round trip for the whole sum at every shape of the step (three sequential
   // ones cost 8.5-9.9 us per launch in situ, tools/stamps_step.py).
-  auto fold_prev = [&](bool movers) { fold_prev_share(p, movers, tid); };
+  auto fold_prev = [&](bool movers) {
+    if (p.prev_n) fold_prev_share(p, movers, tid);
+  };
 
-#ifdef ROLL_ALL_PRIO  // experiment: the weight-gradient waves win every issue arbitration against co-resident channel-wise kernels
-  __builtin_amdgcn_s_setprio(ROLL_ALL_PRIO);
-#endif
   if (wave >= 4) {
     // ------------------------------------------------------------------------------------------- data-moving waves
-#ifdef ROLL_LOADER_PRIO
-    __builtin_amdgcn_s_setprio(ROLL_LOADER_PRIO);
-#endif
     const int lt = tid - 256;
     const int ch = lt & 7;  // the 8-channel chunk of a pixel this thread always handles
     // uniform base (scalar registers) + 32-bit per-lane byte offset: the loads take the saddr form, no 64-bit vector
@@ -239,13 +310,7 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_roll_kernel(const FrWgradAr
           if ((u - NGS) * NLT >= a_chunks(ph)) continue;
           q = q < a_chunks(ph) ? q : a_chunks(ph) - 1;
           const int px = q >> 3, r = px / W, c = px - r * W;
-          U128 x = s.v[u];
-          if (PRO != FR_PRO_NONE) {
-            x.x = pro2<PRO>(x.x, pa[0], pb[0], pa[1], pb[1]);
-            x.y = pro2<PRO>(x.y, pa[2], pb[2], pa[3], pb[3]);
-            x.z = pro2<PRO>(x.z, pa[4], pb[4], pa[5], pb[5]);
-            x.w = pro2<PRO>(x.w, pa[6], pb[6], pa[7], pb[7]);
-          }
+          const U128 x = PRO != FR_PRO_NONE ? pro8<PRO>(s.v[u], pa, pb) : s.v[u];
           // tile row of image row h in this phase: h - (row0 - 1); column c + 1 (column 0 / W + 1 = zero halo)
           const int tr = a_r0(ph) + r - (C::row0(ph) - 1);
           st16(As + (tr * RW + c + 1) * TSTR + ch * 16, x);
@@ -256,14 +321,14 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_roll_kernel(const FrWgradAr
     char* const buf0 = smem;
     char* const buf1 = smem + L::BUF0;
     if (nimg == 0) {  // (never with the group counts the host computes; both roles then skip every barrier)
-      if (p.prev_n) fold_prev(true);
+      fold_prev(true);
       return;
     }
     if constexpr (NPH == 2) {
       // 14x14: phase kind == buffer.  set0 <-> (phase 0, buf0), set1 <-> (phase 1, buf1)
       Set s0, s1;
       issue(s0, b_begin, std::integral_constant<int, 0>{});
-      if (p.prev_n) fold_prev(true);
+      fold_prev(true);
       __builtin_amdgcn_sched_barrier(0);
       issue(s1, b_begin, std::integral_constant<int, 1>{});
       commit(s0, buf0, std::integral_constant<int, 0>{});
@@ -271,11 +336,8 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_roll_kernel(const FrWgradAr
         const int bn = b_begin + 1 < b_end ? b_begin + 1 : b_end - 1;
         issue(s0, bn, std::integral_constant<int, 0>{});
       }
-      LDS_FENCE_BARRIER();  // B0: phase 0 of the first image is in buf0
-#ifdef FRHIP_STAMPS
-      const unsigned long long t_loop = TSTAMP();
-      bar_wait = 0;
-#endif
+      st.barrier();  // B0: phase 0 of the first image is in buf0
+      st.loop_begin();
 #pragma unroll 1
       for (int i = 0; i < nimg; ++i) {
         const int b = b_begin + i;
@@ -286,19 +348,13 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_roll_kernel(const FrWgradAr
         __builtin_amdgcn_sched_barrier(0);
         issue(s1, b1, std::integral_constant<int, 1>{});
         __builtin_amdgcn_sched_barrier(0);
-        LDS_FENCE_BARRIER();  // phase 1 of image i is in buf1; buf0 is free
+        st.barrier();  // phase 1 of image i is in buf1; buf0 is free
         commit(s0, buf0, std::integral_constant<int, 0>{});  // phase 0 of image i + 1 (past the end: a repeat nobody reads)
         __builtin_amdgcn_sched_barrier(0);
         issue(s0, b2, std::integral_constant<int, 0>{});
         __builtin_amdgcn_sched_barrier(0);
-        LDS_FENCE_BARRIER();  // phase 0 of image i + 1 is in buf0; buf1 is free
+        st.barrier();  // phase 0 of image i + 1 is in buf0; buf1 is free
       }
-#ifdef FRHIP_STAMPS
-      if (tid == 256 && fr_stamp_buf_wgr) {
-        fr_stamp_buf_wgr[STAMP_SLOT(W) + 3] = bar_wait;
-        fr_stamp_buf_wgr[STAMP_SLOT(W) + 4] = TSTAMP() - t_loop;
-      }
-#endif
     } else {
       // Uniform schedule (28x28: 7 phases of 4 rows per image).  Phase k of the workgroup lives in buffer k & 1 and in
       // register set k & 1; a phase moves g rows [r0, r0+4) and input rows [r0-1, r0+5) -- the two halo rows are data of
@@ -342,20 +398,14 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_roll_kernel(const FrWgradAr
           s.a[u] = ld16(xi + (unsigned)(row * W * p.lda * 2 + aoff_c[u]));
         }
       };
-      auto commit = [&](Set& s, char* buf) {
-        char* Gs = buf;
-        char* As = buf + L::g_bytes(0);
+      auto commit = [&](Set& s, int b) {
+        char* Gs = b ? buf1 : buf0;
+        char* As = Gs + L::g_bytes(0);
 #pragma unroll
         for (int u = 0; u < NGS; ++u) st16(Gs + gdst[u], s.g[u]);
 #pragma unroll
         for (int u = 0; u < NAS; ++u) {
-          U128 x = s.a[u];
-          if (PRO != FR_PRO_NONE) {
-            x.x = pro2<PRO>(x.x, pa[0], pb[0], pa[1], pb[1]);
-            x.y = pro2<PRO>(x.y, pa[2], pb[2], pa[3], pb[3]);
-            x.z = pro2<PRO>(x.z, pa[4], pb[4], pa[5], pb[5]);
-            x.w = pro2<PRO>(x.w, pa[6], pb[6], pa[7], pb[7]);
-          }
+          U128 x = PRO != FR_PRO_NONE ? pro8<PRO>(s.a[u], pa, pb) : s.a[u];
           // slots that can hold a row outside the image (tile row 0 of the first phase, row PR+1 of the last)
           if (u * NLT < W * 8 || (u + 1) * NLT > (PR + 1) * W * 8) {
             const int row = s.img_row0 - 1 + atr[u];
@@ -369,72 +419,58 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_roll_kernel(const FrWgradAr
         }
       };
       Set s0, s1;
-      const int fl = b_end - 1;  // requests past the run are clamped to its last phase and never read
-      issue(s0, b_begin);
-      if (p.prev_n) fold_prev(true);
+      const int fl = run.end - 1;  // requests past the run are clamped to its last phase and never read
+      issue(s0, run.begin);
+      fold_prev(true);
       __builtin_amdgcn_sched_barrier(0);
-      issue(s1, b_begin + 1 < b_end ? b_begin + 1 : fl);
-      commit(s0, buf0);
+      issue(s1, run.begin + 1 < run.end ? run.begin + 1 : fl);
+      commit(s0, 0);
       __builtin_amdgcn_sched_barrier(0);
-      issue(s0, b_begin + 2 < b_end ? b_begin + 2 : fl);
+      issue(s0, run.begin + 2 < run.end ? run.begin + 2 : fl);
       __builtin_amdgcn_sched_barrier(0);
-      LDS_FENCE_BARRIER();  // B0: phase 0 is in buffer 0
-#ifdef FRHIP_STAMPS
-      const unsigned long long t_loop = TSTAMP();
-      bar_wait = 0;
-#endif
+      st.barrier();  // B0: phase 0 is in buffer 0
+      st.loop_begin();
 #pragma unroll 1
-      for (int k = 0; k < nimg; k += 2) {
-        const int f = b_begin + k;
-        // computing waves: phase k (buffer 0); buffer 1 is free
-        commit(s1, buf1);
+      for (int k = 0; k < run.n; k += 2) {
+        const int f = run.begin + k;
+        // computing waves: phase k (buffer 0); buffer 1 is free (commit -> issue order: see the two-phase loop above)
+        commit(s1, 1);
         __builtin_amdgcn_sched_barrier(0);
-        issue(s1, f + 3 < b_end ? f + 3 : fl);
+        issue(s1, f + 3 < run.end ? f + 3 : fl);
         __builtin_amdgcn_sched_barrier(0);
-        LDS_FENCE_BARRIER();  // phase k + 1 is in buffer 1; buffer 0 is free
-        commit(s0, buf0);
+        st.barrier();  // phase k + 1 is in buffer 1; buffer 0 is free
+        commit(s0, 0);
         __builtin_amdgcn_sched_barrier(0);
-        issue(s0, f + 4 < b_end ? f + 4 : fl);
+        issue(s0, f + 4 < run.end ? f + 4 : fl);
         __builtin_amdgcn_sched_barrier(0);
-        LDS_FENCE_BARRIER();  // phase k + 2 is in buffer 0; buffer 1 is free
+        st.barrier();  // phase k + 2 is in buffer 0; buffer 1 is free
       }
-#ifdef FRHIP_STAMPS
-      if (tid == 256 && fr_stamp_buf_wgr) {
-        fr_stamp_buf_wgr[STAMP_SLOT(W) + 3] = bar_wait;
-        fr_stamp_buf_wgr[STAMP_SLOT(W) + 4] = TSTAMP() - t_loop;
-      }
-#endif
     }
+    if (tid == 256) st.loop_end(4, 3);
     return;
   }
 
   // ------------------------------------------------------------------------------------------------ computing waves
   const int wci = wave;  // ci tile of this wave
-  const int li = lane & 15, lq = lane >> 4;
-  const int colb = (4 * (li & 3)) * 2;  // byte offset of this lane's 4-channel group inside a 16-channel tile
-  const int lrow = (4 * lq + (li >> 2)) * TSTR;
-#ifdef FRHIP_STAMPS
-  const unsigned long long t_zero = TSTAMP();
-#endif
-  if (p.prev_n) fold_prev(false);  // before the accumulators exist: the sum may use their registers
+  const Lane ln(lane);
+  const unsigned long long t_zero = st.now();
+  fold_prev(false);  // before the accumulators exist: the sum may use their registers
   __builtin_amdgcn_sched_barrier(0);
   f32x4 acc[4][9];
 #pragma unroll
   for (int t = 0; t < 4; ++t)
 #pragma unroll
     for (int k = 0; k < 9; ++k) acc[t][k] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#ifdef FRHIP_STAMPS
-  const unsigned long long t_fold = TSTAMP();
-  if (tid == 0 && fr_stamp_buf_wgr) {
-    fr_stamp_buf_wgr[STAMP_SLOT(W) + 8] = t_zero - t_start;   // LDS zero fill
-    fr_stamp_buf_wgr[STAMP_SLOT(W) + 9] = t_fold - t_zero;    // slab sum of the previous launch
+  const unsigned long long t_fold = st.now();
+  if (tid == 0) {
+    st.put(8, st.since_start(t_zero));  // LDS zero fill
+    st.put(9, t_fold - t_zero);      // slab sum of the previous launch
   }
-#endif
   if (nimg > 0) {
-    const char* const gb0 = smem + lrow + colb;
-    const char* const ab0 = smem + L::g_bytes(0) + lrow + (wci * 16) * 2 + colb;
-    const char* const gb1 = smem + L::BUF0 + lrow + colb;
-    const char* const ab1 = smem + L::BUF0 + L::g_bytes(1) + lrow + (wci * 16) * 2 + colb;
+    const char* const gb0 = smem + ln.lrow + ln.colb;
+    const char* const ab0 = smem + L::g_bytes(0) + ln.lrow + (wci * 16) * 2 + ln.colb;
+    const char* const gb1 = smem + L::BUF0 + ln.lrow + ln.colb;
+    const char* const ab1 = smem + L::BUF0 + L::g_bytes(1) + ln.lrow + (wci * 16) * 2 + ln.colb;
     // One "item" = one tap of one K step: an input fragment (2 reads) and 4 MFMAs (one per co tile).  Flat software
     // pipeline over the items of a phase: the fragment of item it + LA is requested behind the MFMAs of item it into a ring
     // of RS = LA + 1 = 3 (the slot of an item is its index mod 3 in every phase: 36 and 27 items); the g fragments of the
@@ -445,10 +481,8 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_roll_kernel(const FrWgradAr
     // instructions: 1.35 per MFMA by PMC, a quarter of the wave cycles in LDS-issue stalls).
     // The barrier that hands the buffers over sits at the last item of a phase: its fragment was requested two items
     // earlier; the first fragments of the next phase are requested right behind the barrier, under that item's MFMAs.
-#ifndef ROLL_LA
-#define ROLL_LA 2
-#endif
-    constexpr int LA = ROLL_LA, RS = LA + 1;  // ring slots
+    // (Other look-aheads and raised wave priorities were compile-time experiments once; none paid.)
+    constexpr int LA = 2, RS = LA + 1;  // ring slots
     auto a_frag = [&](const char* ab, int item) -> s16x8 {
       const int ks = item / 9, tap = item % 9;
       const int off = 32 * ks + RW * (tap / 3) + tap % 3;
@@ -469,7 +503,7 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_roll_kernel(const FrWgradAr
       for (int it = 0; it < NI; ++it) {
         const int ks = it / 9, tap = it % 9;
         if (it == IB) {
-          LDS_FENCE_BARRIER();  // every fragment of this phase is in registers; the next buffer is complete
+          st.barrier();  // every fragment of this phase is in registers; the next buffer is complete
 #pragma unroll
           for (int t = 0; t < 4; ++t) gn[t] = g_frag(gb_next, 0, t);
 #pragma unroll
@@ -491,13 +525,9 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_roll_kernel(const FrWgradAr
       }
     };
     constexpr int NS0 = C::krows(0) * RW / 32, NS1 = C::krows(NPH == 2 ? 1 : 0) * RW / 32;
-    LDS_FENCE_BARRIER();  // B0: phase 0 of the first image is in buffer 0
-#ifdef FRHIP_STAMPS
-    const unsigned long long t_loop = TSTAMP();
-    bar_wait = 0;
-    if (tid == 0 && fr_stamp_buf_wgr)
-      fr_stamp_buf_wgr[STAMP_SLOT(W) + 10] = t_loop - t_fold;  // wait for the first tiles
-#endif
+    st.barrier();  // B0: phase 0 of the first image is in buffer 0
+    const unsigned long long t_loop = st.loop_begin();
+    if (tid == 0) st.put(10, t_loop - t_fold);  // wait for the first tiles
 #pragma unroll
     for (int t = 0; t < 4; ++t) gf[t] = g_frag(gb0, 0, t);
 #pragma unroll
@@ -515,36 +545,19 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_roll_kernel(const FrWgradAr
       for (int k = 0; k < nimg; k += 2) {
         run_phase(gb0, ab0, gb1, ab1, std::integral_constant<int, NS0>{});
         if (k + 1 < nimg) run_phase(gb1, ab1, gb0, ab0, std::integral_constant<int, NS0>{});
-        else LDS_FENCE_BARRIER();
+        else st.barrier();
       }
     }
-#ifdef FRHIP_STAMPS
-    if (tid == 0 && fr_stamp_buf_wgr) {
-      fr_stamp_buf_wgr[STAMP_SLOT(W) + 1] = TSTAMP() - t_loop;
-      fr_stamp_buf_wgr[STAMP_SLOT(W) + 2] = bar_wait;
-      fr_stamp_buf_wgr[STAMP_SLOT(W) + 6] = nimg;
+    if (tid == 0) {
+      st.loop_end(1, 2);
+      st.put(6, nimg);
     }
-#endif
   }
 
   // slab[group][co][tap][ci]
-  float* __restrict__ slab = p.slab + (size_t)group * (size_t)p.Cout * 9 * (size_t)p.SC;
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int co = cot * CT + t * 16 + lq * 4 + r;
-        const int ci = cit * CT + wci * 16 + li;
-        slab[((size_t)co * 9 + tap) * (size_t)p.SC + ci] = acc[t][tap][r];
-      }
-#ifdef FRHIP_STAMPS
-  if (tid == 0 && fr_stamp_buf_wgr) {
-    fr_stamp_buf_wgr[STAMP_SLOT(W) + 0] = TSTAMP() - t_start;
-    fr_stamp_buf_wgr[STAMP_SLOT(W) + 5] = __builtin_amdgcn_s_memrealtime() - rt_start;
-  }
-#endif
+  store_slab(p.slab + (size_t)group * (size_t)p.Cout * 9 * (size_t)p.SC, acc, p.SC, cot * CT + ln.lq * 4,
+             cit * CT + wci * 16 + ln.li);
+  if (tid == 0) st.kernel_end();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -574,42 +587,24 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_vr_kernel(const FrWgradArgs
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nblk = gridDim.x;
-  int bid = blockIdx.x;
-  {
-    const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  const int cit_n = p.SC / CT, tiles = (p.Cout / CT) * cit_n;
-  const int group = bid / tiles, tile = bid - group * tiles;
-  const int cot = tile / cit_n, cit = tile - cot * cit_n;
+  const WgTile wt = wg_tile(p);
+  const int group = wt.group, cot = wt.cot, cit = wt.cit;
   const int total = p.B * VH;  // virtual rows of the launch
-  const int per = (total + p.nsplit - 1) / p.nsplit;
-  const int v_begin = group * per;
-  int v_end = v_begin + per;
-  if (v_end > total) v_end = total;
-  const int nph = v_end > v_begin ? v_end - v_begin : 0;  // phases of this workgroup
+  const WgRun run = wg_run(p, group, total);
+  const int v_begin = run.begin, nph = run.n;  // phases of this workgroup
 
-#ifdef FRHIP_STAMPS
-  unsigned long long bar_wait = 0;
-  const unsigned long long t_start = TSTAMP(), rt_start = __builtin_amdgcn_s_memrealtime();
-#endif
-  for (int idx = tid; idx < C::LDS / 16; idx += 512) st16(smem + idx * 16, zero16());
-  __syncthreads();
+  Stamps<W> st;
+  zero_lds<C::LDS>(smem, tid);
 
   // deferred slab sum of the previous launch, split between the wave roles (see conv_wgrad_roll_kernel)
-  auto fold_prev = [&](bool movers) { fold_prev_share(p, movers, tid); };
+  auto fold_prev = [&](bool movers) {
+    if (p.prev_n) fold_prev_share(p, movers, tid);
+  };
 
-#ifdef ROLL_ALL_PRIO  // experiment: the weight-gradient waves win every issue arbitration against co-resident channel-wise kernels
-  __builtin_amdgcn_s_setprio(ROLL_ALL_PRIO);
-#endif
   if (wave >= 4) {
     // ------------------------------------------------------------------------------------------- data-moving waves
-#ifdef ROLL_LOADER_PRIO
-    __builtin_amdgcn_s_setprio(ROLL_LOADER_PRIO);
-#endif
     if (nph == 0) {
-      if (p.prev_n) fold_prev(true);
+      fold_prev(true);
       return;
     }
     const int lt = tid - 256;
@@ -666,13 +661,7 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_vr_kernel(const FrWgradArgs
       char* As = smem + C::A_OFF + slot * C::AROW;
 #pragma unroll
       for (int u = 0; u < NRS; ++u) {
-        U128 x = s.v[u];
-        if (PRO != FR_PRO_NONE) {
-          x.x = pro2<PRO>(x.x, pa[0], pb[0], pa[1], pb[1]);
-          x.y = pro2<PRO>(x.y, pa[2], pb[2], pa[3], pb[3]);
-          x.z = pro2<PRO>(x.z, pa[4], pb[4], pa[5], pb[5]);
-          x.w = pro2<PRO>(x.w, pa[6], pb[6], pa[7], pb[7]);
-        }
+        U128 x = PRO != FR_PRO_NONE ? pro8<PRO>(s.v[u], pa, pb) : s.v[u];
         if (s.zero) x = zero16();
         st16(As + adst[u], x);
       }
@@ -690,7 +679,7 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_vr_kernel(const FrWgradArgs
       issue_a(t1, v_begin);
       issue_a(t2, v_begin + 1);
       issue_g(tg, v_begin);
-      if (p.prev_n) fold_prev(true);
+      fold_prev(true);
       __builtin_amdgcn_sched_barrier(0);
       commit_a(t0, 0);
       commit_a(t1, 1);
@@ -702,11 +691,8 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_vr_kernel(const FrWgradArgs
     issue_g(g0, v_begin + 1);
     issue_a(a1, v_begin + 3);
     issue_g(g1, v_begin + 2);
-    LDS_FENCE_BARRIER();  // B0: phase 0 is resident
-#ifdef FRHIP_STAMPS
-    const unsigned long long t_loop = TSTAMP();
-    bar_wait = 0;
-#endif
+    st.barrier();  // B0: phase 0 is resident
+    st.loop_begin();
 #pragma unroll 1
     for (int j = 0; j < nph; j += 4) {
       const int V = v_begin + j;
@@ -722,25 +708,17 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_vr_kernel(const FrWgradArgs
         issue_a(ra, V + s + 4);
         issue_g(rg, V + s + 3);
         __builtin_amdgcn_sched_barrier(0);
-        LDS_FENCE_BARRIER();
+        st.barrier();
       }
     }
-#ifdef FRHIP_STAMPS
-    if (tid == 256 && fr_stamp_buf_wgr) {
-      fr_stamp_buf_wgr[STAMP_SLOT(W) + 3] = bar_wait;
-      fr_stamp_buf_wgr[STAMP_SLOT(W) + 4] = TSTAMP() - t_loop;
-    }
-#endif
+    if (tid == 256) st.loop_end(4, 3);
     return;
   }
 
   // ------------------------------------------------------------------------------------------------ computing waves
   const int wci = wave;
-  const int li = lane & 15, lq = lane >> 4;
-  const int colb = (4 * (li & 3)) * 2;
-  const int lrow = (4 * lq + (li >> 2)) * TSTR;
-
-  if (p.prev_n) fold_prev(false);
+  const Lane ln(lane);
+  fold_prev(false);
   __builtin_amdgcn_sched_barrier(0);
   f32x4 acc[4][9];
 #pragma unroll
@@ -748,8 +726,8 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_vr_kernel(const FrWgradArgs
 #pragma unroll
     for (int k = 0; k < 9; ++k) acc[t][k] = (f32x4){0.f, 0.f, 0.f, 0.f};
   if (nph > 0) {
-    const char* const gbase = smem + lrow + colb;
-    const char* const abase = smem + C::A_OFF + lrow + (wci * 16) * 2 + colb;
+    const char* const gbase = smem + ln.lrow + ln.colb;
+    const char* const abase = smem + C::A_OFF + ln.lrow + (wci * 16) * 2 + ln.colb;
     constexpr int LA = 2, RS = 3;  // tap-major items, ring of 3: see the kernel above
     constexpr int NI = NSTEP * 9, IB = NI - LA + 1;
     static_assert(NI % RS == 0 && IB / 9 == NSTEP - 1 && IB % 9 >= 4, "item pipeline");
@@ -770,14 +748,14 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_vr_kernel(const FrWgradArgs
     auto run_phase = [&](auto sc, bool live) {
       constexpr int s = decltype(sc)::value;
       if (!live) {
-        LDS_FENCE_BARRIER();
+        st.barrier();
         return;
       }
 #pragma unroll
       for (int it = 0; it < NI; ++it) {
         const int ks = it / 9, tap = it % 9;
         if (it == IB) {
-          LDS_FENCE_BARRIER();
+          st.barrier();
 #pragma unroll
           for (int t = 0; t < 4; ++t) gn[t] = g_frag((s + 1) & 1, 0, t);
 #pragma unroll
@@ -798,11 +776,8 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_vr_kernel(const FrWgradArgs
         __builtin_amdgcn_sched_barrier(0);
       }
     };
-    LDS_FENCE_BARRIER();  // B0
-#ifdef FRHIP_STAMPS
-    const unsigned long long t_loop = TSTAMP();
-    bar_wait = 0;
-#endif
+    st.barrier();  // B0
+    st.loop_begin();
 #pragma unroll
     for (int t = 0; t < 4; ++t) gf[t] = g_frag(0, 0, t);
 #pragma unroll
@@ -814,32 +789,15 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_vr_kernel(const FrWgradArgs
       run_phase(std::integral_constant<int, 2>{}, j + 2 < nph);
       run_phase(std::integral_constant<int, 3>{}, j + 3 < nph);
     }
-#ifdef FRHIP_STAMPS
-    if (tid == 0 && fr_stamp_buf_wgr) {
-      fr_stamp_buf_wgr[STAMP_SLOT(W) + 1] = TSTAMP() - t_loop;
-      fr_stamp_buf_wgr[STAMP_SLOT(W) + 2] = bar_wait;
-      fr_stamp_buf_wgr[STAMP_SLOT(W) + 6] = nph;
+    if (tid == 0) {
+      st.loop_end(1, 2);
+      st.put(6, nph);
     }
-#endif
   }
 
-  float* __restrict__ slab = p.slab + (size_t)group * (size_t)p.Cout * 9 * (size_t)p.SC;
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int co = cot * CT + t * 16 + lq * 4 + r;
-        const int ci = cit * CT + wci * 16 + li;
-        slab[((size_t)co * 9 + tap) * (size_t)p.SC + ci] = acc[t][tap][r];
-      }
-#ifdef FRHIP_STAMPS
-  if (tid == 0 && fr_stamp_buf_wgr) {
-    fr_stamp_buf_wgr[STAMP_SLOT(W) + 0] = TSTAMP() - t_start;
-    fr_stamp_buf_wgr[STAMP_SLOT(W) + 5] = __builtin_amdgcn_s_memrealtime() - rt_start;
-  }
-#endif
+  store_slab(p.slab + (size_t)group * (size_t)p.Cout * 9 * (size_t)p.SC, acc, p.SC, cot * CT + ln.lq * 4,
+             cit * CT + wci * 16 + ln.li);
+  if (tid == 0) st.kernel_end();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -900,34 +858,21 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_s2roll_kernel(const FrWgrad
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nblk = gridDim.x;
-  int bid = blockIdx.x;
-  {
-    const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  const int cit_n = p.SC / CT, tiles = (p.Cout / CT) * cit_n;
-  const int group = bid / tiles, tile = bid - group * tiles;
-  const int cot = tile / cit_n, cit = tile - cot * cit_n;
-  const int units = p.B * NPH;  // phases of the launch
-  const int per = (units + p.nsplit - 1) / p.nsplit;
-  const int b_begin = group * per;
-  int b_end = b_begin + per;
-  if (b_end > units) b_end = units;
-  const int nph = b_end > b_begin ? b_end - b_begin : 0;  // phases of this workgroup
+  const WgTile wt = wg_tile(p);
+  const int group = wt.group, cot = wt.cot, cit = wt.cit;
+  const WgRun run = wg_run(p, group, p.B * NPH);  // phases of the launch
+  const int nph = run.n;                          // phases of this workgroup
 
-  for (int idx = tid; idx < L::LDS / 16; idx += 512) st16(smem + idx * 16, zero16());
-  __syncthreads();
+  zero_lds<L::LDS>(smem, tid);
 
-  auto fold_prev = [&](bool movers) { fold_prev_share(p, movers, tid); };
+  auto fold_prev = [&](bool movers) {
+    if (p.prev_n) fold_prev_share(p, movers, tid);
+  };
 
-#ifdef ROLL_ALL_PRIO  // experiment: the weight-gradient waves win every issue arbitration against co-resident channel-wise kernels
-  __builtin_amdgcn_s_setprio(ROLL_ALL_PRIO);
-#endif
   if (wave >= 4) {
     // ------------------------------------------------------------------------------------------- data-moving waves
     if (nph == 0) {
-      if (p.prev_n) fold_prev(true);
+      fold_prev(true);
       return;
     }
     const int lt = tid - 256;
@@ -987,7 +932,8 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_s2roll_kernel(const FrWgrad
         s.a[u] = ld16(xi + (unsigned)(row * WH * p.lda * 2 + acol[u]));
       }
     };
-    auto commit = [&](Set& s, char* buf) {
+    auto commit = [&](Set& s, int b) {
+      char* buf = smem + b * L::BUF;
 #pragma unroll
       for (int u = 0; u < NGS; ++u) {
         U128 x = s.g[u];
@@ -1002,13 +948,7 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_s2roll_kernel(const FrWgrad
       }
 #pragma unroll
       for (int u = 0; u < NAS; ++u) {
-        U128 x = s.a[u];
-        if (PRO != FR_PRO_NONE) {
-          x.x = pro2<PRO>(x.x, pa[0], pb[0], pa[1], pb[1]);
-          x.y = pro2<PRO>(x.y, pa[2], pb[2], pa[3], pb[3]);
-          x.z = pro2<PRO>(x.z, pa[4], pb[4], pa[5], pb[5]);
-          x.w = pro2<PRO>(x.w, pa[6], pb[6], pa[7], pb[7]);
-        }
+        U128 x = PRO != FR_PRO_NONE ? pro8<PRO>(s.a[u], pa, pb) : s.a[u];
         {
           const int row = 2 * s.r0 - 1 + ae[u];
           const bool out = row < 0 || row > WH - 1;
@@ -1020,42 +960,41 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_s2roll_kernel(const FrWgrad
         st16(buf + adst[u], x);
       }
     };
-    char* const buf0 = smem;
-    char* const buf1 = smem + L::BUF;
+    // the double-buffered schedule of the uniform branch of conv_wgrad_roll_kernel, statement for statement (kept per kernel:
+    // shared as one helper it changed the compiled code of both kernels, profiles/wgrad_ws_refactor.txt)
     Set s0, s1;
-    const int fl = b_end - 1;  // requests past the run are clamped to its last phase and never read
-    issue(s0, b_begin);
-    if (p.prev_n) fold_prev(true);
+    const int fl = run.end - 1;  // requests past the run are clamped to its last phase and never read
+    issue(s0, run.begin);
+    fold_prev(true);
     __builtin_amdgcn_sched_barrier(0);
-    issue(s1, b_begin + 1 < b_end ? b_begin + 1 : fl);
-    commit(s0, buf0);
+    issue(s1, run.begin + 1 < run.end ? run.begin + 1 : fl);
+    commit(s0, 0);
     __builtin_amdgcn_sched_barrier(0);
-    issue(s0, b_begin + 2 < b_end ? b_begin + 2 : fl);
+    issue(s0, run.begin + 2 < run.end ? run.begin + 2 : fl);
     __builtin_amdgcn_sched_barrier(0);
-    LDS_FENCE_BARRIER_RAW();  // B0: phase 0 is in buffer 0
+    lds_fence_barrier();  // B0: phase 0 is in buffer 0
 #pragma unroll 1
-    for (int k = 0; k < nph; k += 2) {
-      const int f = b_begin + k;
-      commit(s1, buf1);
+    for (int k = 0; k < run.n; k += 2) {
+      const int f = run.begin + k;
+      // computing waves: phase k (buffer 0); buffer 1 is free
+      commit(s1, 1);
       __builtin_amdgcn_sched_barrier(0);
-      issue(s1, f + 3 < b_end ? f + 3 : fl);
+      issue(s1, f + 3 < run.end ? f + 3 : fl);
       __builtin_amdgcn_sched_barrier(0);
-      LDS_FENCE_BARRIER_RAW();  // phase k + 1 is in buffer 1; buffer 0 is free
-      commit(s0, buf0);
+      lds_fence_barrier();  // phase k + 1 is in buffer 1; buffer 0 is free
+      commit(s0, 0);
       __builtin_amdgcn_sched_barrier(0);
-      issue(s0, f + 4 < b_end ? f + 4 : fl);
+      issue(s0, f + 4 < run.end ? f + 4 : fl);
       __builtin_amdgcn_sched_barrier(0);
-      LDS_FENCE_BARRIER_RAW();  // phase k + 2 is in buffer 0; buffer 1 is free
+      lds_fence_barrier();  // phase k + 2 is in buffer 0; buffer 1 is free
     }
     return;
   }
 
   // ------------------------------------------------------------------------------------------------ computing waves
   const int wci = wave;
-  const int li = lane & 15, lq = lane >> 4;
-  const int colb = (4 * (li & 3)) * 2;
-  const int lrow = (4 * lq + (li >> 2)) * TSTR;
-  if (p.prev_n) fold_prev(false);
+  const Lane ln(lane);
+  fold_prev(false);
   __builtin_amdgcn_sched_barrier(0);
   f32x4 acc[4][9];
 #pragma unroll
@@ -1063,8 +1002,8 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_s2roll_kernel(const FrWgrad
 #pragma unroll
     for (int k = 0; k < 9; ++k) acc[t][k] = (f32x4){0.f, 0.f, 0.f, 0.f};
   if (nph > 0) {
-    const char* const gb0 = smem + lrow + colb;
-    const char* const ab0 = smem + lrow + (wci * 16) * 2 + colb;  // + tap_off (which includes the g tile and the plane)
+    const char* const gb0 = smem + ln.lrow + ln.colb;
+    const char* const ab0 = smem + ln.lrow + (wci * 16) * 2 + ln.colb;  // + tap_off (which includes the g tile and the plane)
     const char* const gb1 = gb0 + L::BUF;
     const char* const ab1 = ab0 + L::BUF;
     constexpr int LA = 2, RS = 3, NSTEP = PRK * RW / 32, NI = NSTEP * 9, IB = NI - LA + 1;
@@ -1084,7 +1023,7 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_s2roll_kernel(const FrWgrad
       for (int it = 0; it < NI; ++it) {
         const int ks = it / 9, tap = it % 9;
         if (it == IB) {
-          LDS_FENCE_BARRIER_RAW();  // every fragment of this phase is in registers; the next buffer is complete
+          lds_fence_barrier();  // every fragment of this phase is in registers; the next buffer is complete
 #pragma unroll
           for (int t = 0; t < 4; ++t) gn[t] = g_frag(gb_next, 0, t);
 #pragma unroll
@@ -1105,7 +1044,7 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_s2roll_kernel(const FrWgrad
         __builtin_amdgcn_sched_barrier(0);
       }
     };
-    LDS_FENCE_BARRIER_RAW();  // B0
+    lds_fence_barrier();  // B0
 #pragma unroll
     for (int t = 0; t < 4; ++t) gf[t] = g_frag(gb0, 0, t);
 #pragma unroll
@@ -1114,111 +1053,31 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_s2roll_kernel(const FrWgrad
     for (int k = 0; k < nph; k += 2) {
       run_phase(gb0, ab0, gb1, ab1);
       if (k + 1 < nph) run_phase(gb1, ab1, gb0, ab0);
-      else LDS_FENCE_BARRIER_RAW();
+      else lds_fence_barrier();
     }
   }
 
-  float* __restrict__ slab = p.slab + (size_t)group * (size_t)p.Cout * 9 * (size_t)p.SC;
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int co = cot * CT + t * 16 + lq * 4 + r;
-        const int ci = cit * CT + wci * 16 + li;
-        slab[((size_t)co * 9 + tap) * (size_t)p.SC + ci] = acc[t][tap][r];
-      }
+  store_slab(p.slab + (size_t)group * (size_t)p.Cout * 9 * (size_t)p.SC, acc, p.SC, cot * CT + ln.lq * 4,
+             cit * CT + wci * 16 + ln.li);
 }
 
-template <int WL, int PRO>
-int launch_s2(const FrWgradArgs& a, hipStream_t st) {
-  using L = SL2<WL>;
-  static unsigned long long attr_done = 0;  // one bit per device
-  if (fr_attr_needed(attr_done)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_s2roll_kernel<WL, PRO>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, L::LDS);
-    fr_attr_done(attr_done);
-  }
-  const int tiles = (a.Cout / CT) * (a.SC / CT);
-  hipLaunchKernelGGL((conv_wgrad_s2roll_kernel<WL, PRO>), dim3(tiles * a.nsplit), dim3(512), L::LDS, st, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    fr_set_error(hipGetErrorString(e));
-    return (int)e;
-  }
-  if (a.defer) return 0;
-  return fr_launch_reduce_slabs(a.slab, a.nsplit, (long long)a.Cout * 9 * a.SC, a.dw, st);
+template <int W>
+int launch_roll(const FrWgradArgs& a, hipStream_t st) {
+  return fr_by_pro(a.pro, [&](auto pro) {
+    return fr_launch_slab_kernel<conv_wgrad_roll_kernel<W, decltype(pro)::value>>(a, st, 512, RL<W>::LDS);
+  });
 }
-
-template <int WL>
-int by_pro_s2(const FrWgradArgs& a, hipStream_t st) {
-  switch (a.pro) {
-    case FR_PRO_NONE: return launch_s2<WL, FR_PRO_NONE>(a, st);
-    case FR_PRO_BN: return launch_s2<WL, FR_PRO_BN>(a, st);
-    case FR_PRO_PRELU: return launch_s2<WL, FR_PRO_PRELU>(a, st);
-  }
-  FR_UNSUPPORTED("fr_conv_wgrad_strip: unknown prologue");
-}
-
-template <int W, int PRO>
+template <int W>
 int launch_vr(const FrWgradArgs& a, hipStream_t st) {
-  using C = VC<W>;
-  static unsigned long long attr_done = 0;  // one bit per device
-  if (fr_attr_needed(attr_done)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_vr_kernel<W, PRO>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-    fr_attr_done(attr_done);
-  }
-  const int tiles = (a.Cout / CT) * (a.SC / CT);
-  hipLaunchKernelGGL((conv_wgrad_vr_kernel<W, PRO>), dim3(tiles * a.nsplit), dim3(512), C::LDS, st, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    fr_set_error(hipGetErrorString(e));
-    return (int)e;
-  }
-  if (a.defer) return 0;
-  return fr_launch_reduce_slabs(a.slab, a.nsplit, (long long)a.Cout * 9 * a.SC, a.dw, st);
+  return fr_by_pro(a.pro, [&](auto pro) {
+    return fr_launch_slab_kernel<conv_wgrad_vr_kernel<W, decltype(pro)::value>>(a, st, 512, VC<W>::LDS);
+  });
 }
-
-template <int W>
-int by_pro_vr(const FrWgradArgs& a, hipStream_t st) {
-  switch (a.pro) {
-    case FR_PRO_NONE: return launch_vr<W, FR_PRO_NONE>(a, st);
-    case FR_PRO_BN: return launch_vr<W, FR_PRO_BN>(a, st);
-    case FR_PRO_PRELU: return launch_vr<W, FR_PRO_PRELU>(a, st);
-  }
-  FR_UNSUPPORTED("fr_conv_wgrad_strip: unknown prologue");
-}
-
-template <int W, int PRO>
-int launch(const FrWgradArgs& a, hipStream_t st) {
-  using L = RL<W>;
-  static unsigned long long attr_done = 0;  // one bit per device
-  if (fr_attr_needed(attr_done)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_roll_kernel<W, PRO>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, L::LDS);
-    fr_attr_done(attr_done);
-  }
-  const int tiles = (a.Cout / CT) * (a.SC / CT);
-  hipLaunchKernelGGL((conv_wgrad_roll_kernel<W, PRO>), dim3(tiles * a.nsplit), dim3(512), L::LDS, st, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    fr_set_error(hipGetErrorString(e));
-    return (int)e;
-  }
-  if (a.defer) return 0;  // the caller sums the slabs (prev_* of a later launch, or fr_reduce_slabs)
-  return fr_launch_reduce_slabs(a.slab, a.nsplit, (long long)a.Cout * 9 * a.SC, a.dw, st);
-}
-
-template <int W>
-int by_pro(const FrWgradArgs& a, hipStream_t st) {
-  switch (a.pro) {
-    case FR_PRO_NONE: return launch<W, FR_PRO_NONE>(a, st);
-    case FR_PRO_BN: return launch<W, FR_PRO_BN>(a, st);
-    case FR_PRO_PRELU: return launch<W, FR_PRO_PRELU>(a, st);
-  }
-  FR_UNSUPPORTED("fr_conv_wgrad_strip: unknown prologue");
+template <int WL>
+int launch_s2(const FrWgradArgs& a, hipStream_t st) {
+  return fr_by_pro(a.pro, [&](auto pro) {
+    return fr_launch_slab_kernel<conv_wgrad_s2roll_kernel<WL, decltype(pro)::value>>(a, st, 512, SL2<WL>::LDS);
+  });
 }
 
 }  // namespace
@@ -1262,21 +1121,21 @@ bool fr_wgrad_s2roll_serves(const FrWgradArgs& a) {
 
 int fr_wgrad_s2roll_launch(const FrWgradArgs& a, hipStream_t st) {
   switch (a.GW) {
-    case 56: return by_pro_s2<56>(a, st);
-    case 28: return by_pro_s2<28>(a, st);
-    case 14: return by_pro_s2<14>(a, st);
-    case 7: return by_pro_s2<7>(a, st);
+    case 56: return launch_s2<56>(a, st);
+    case 28: return launch_s2<28>(a, st);
+    case 14: return launch_s2<14>(a, st);
+    case 7: return launch_s2<7>(a, st);
   }
   FR_UNSUPPORTED("fr_conv_wgrad_strip: stride-2 width not served by the warp-specialised kernel");
 }
 
 int fr_wgrad_roll_launch(const FrWgradArgs& a, hipStream_t st) {
   switch (a.SW) {
-    case 7: return by_pro<7>(a, st);
-    case 14: return by_pro<14>(a, st);
-    case 28: return by_pro<28>(a, st);
-    case 56: return by_pro_vr<56>(a, st);
-    case 112: return by_pro_vr<112>(a, st);
+    case 7: return launch_roll<7>(a, st);
+    case 14: return launch_roll<14>(a, st);
+    case 28: return launch_roll<28>(a, st);
+    case 56: return launch_vr<56>(a, st);
+    case 112: return launch_vr<112>(a, st);
   }
   FR_UNSUPPORTED("fr_conv_wgrad_strip: width not served by the warp-specialised kernel");
 }

@@ -21,7 +21,7 @@
 
 namespace {
 
-constexpr int CT = 64;               // co and ci tile
+constexpr int CT = FR_WGRAD_CT;               // co and ci tile
 constexpr int TSTR = CT * 2 + 32;    // LDS row stride (bytes) of both tiles: conflict-free transposed reads
 
 // S2: the stride-2 convolution of a stage transition (model_irse.py:59).  W / ROWS then describe the LOW-resolution
@@ -386,35 +386,12 @@ int fr_launch_reduce_slabs(const float* slab, int groups, long long n, float* ou
 
 namespace {
 
-template <int W, int ROWS, int NIMG, int NW, int PRO, bool S2 = false, bool RK = false>
-int launch(const FrWgradArgs& a, hipStream_t st) {
-  using C = WC<W, ROWS, NIMG, NW, S2, RK>;
-  static unsigned long long attr_done = 0;  // one bit per device
-  if (fr_attr_needed(attr_done)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_strip_kernel<W, ROWS, NIMG, NW, PRO, S2, RK>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-    fr_attr_done(attr_done);
-  }
-  const int tiles = (a.Cout / CT) * (a.SC / CT);
-  hipLaunchKernelGGL((conv_wgrad_strip_kernel<W, ROWS, NIMG, NW, PRO, S2, RK>), dim3(tiles * a.nsplit), dim3(C::NTH), C::LDS,
-                     st, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    fr_set_error(hipGetErrorString(e));
-    return (int)e;
-  }
-  if (a.defer) return 0;  // the caller sums the slabs (prev_* of a later launch, or fr_reduce_slabs)
-  return fr_launch_reduce_slabs(a.slab, a.nsplit, (long long)a.Cout * 9 * a.SC, a.dw, st);
-}
-
 template <int W, int ROWS, int NIMG, int NW, bool S2 = false, bool RK = false>
 int by_pro(const FrWgradArgs& a, hipStream_t st) {
-  switch (a.pro) {
-    case FR_PRO_NONE: return launch<W, ROWS, NIMG, NW, FR_PRO_NONE, S2, RK>(a, st);
-    case FR_PRO_BN: return launch<W, ROWS, NIMG, NW, FR_PRO_BN, S2, RK>(a, st);
-    case FR_PRO_PRELU: return launch<W, ROWS, NIMG, NW, FR_PRO_PRELU, S2, RK>(a, st);
-  }
-  FR_UNSUPPORTED("fr_conv_wgrad_strip: unknown prologue");
+  using C = WC<W, ROWS, NIMG, NW, S2, RK>;
+  return fr_by_pro(a.pro, [&](auto pro) {
+    return fr_launch_slab_kernel<conv_wgrad_strip_kernel<W, ROWS, NIMG, NW, decltype(pro)::value, S2, RK>>(a, st, C::NTH, C::LDS);
+  });
 }
 
 }  // namespace

@@ -4,6 +4,10 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
+#include "common.h"  // U128 (pro8), FR_UNSUPPORTED (fr_by_pro)
+
 // run-time switch `name` (api.hip): pointer to its cached value (environment variable of that name, else dflt)
 int* fr_option_slot(const char* name, int dflt);
 // FRHIP_XCD_ORDER=0: the strip kernels' workgroups take strips in dispatch order (A/B switch for tools/kbench.py); else 1
@@ -39,12 +43,12 @@ int fr_s2roll_parts(int B);
 int fr_s2roll_launch(const FrConvArgs& a, hipStream_t st);
 bool fr_s2roll_enabled();
 
-// 3x3 stride-1 weight gradients at 14x14 on the warp-specialised kernel (conv_wgrad_roll.hip); dispatched from
+// 3x3 stride-1 weight gradients at 7x7 ... 112x112 on the warp-specialised kernels (conv_wgrad_roll.hip); dispatched from
 // fr_conv_wgrad_strip
 bool fr_wgrad_roll_enabled();
 bool fr_wgrad_roll_serves(const FrWgradArgs& a);
 int fr_wgrad_roll_launch(const FrWgradArgs& a, hipStream_t st);
-// ... and the stride-2 ones with a 28 / 14 / 7 wide gradient (conv_wgrad_s2roll_kernel, same file)
+// ... and the stride-2 ones with a 56 / 28 / 14 / 7 wide gradient (conv_wgrad_s2roll_kernel, same file)
 bool fr_wgrad_s2roll_serves(const FrWgradArgs& a);
 int fr_wgrad_s2roll_launch(const FrWgradArgs& a, hipStream_t st);
 
@@ -85,5 +89,48 @@ __device__ __forceinline__ uint32_t pro2(uint32_t u, float a0, float b0, float a
       : "=&v"(lo), "=&v"(hi), "=&v"(m), "=v"(r)
       : "v"(u), "v"(a0), "v"(a1));
   return r;
+}
+// ... on one 16-byte chunk: eight channels with their coefficients a[j] (scale / slope) and b[j] (BN shift)
+template <int PRO>
+__device__ __forceinline__ U128 pro8(U128 x, const float (&a)[8], const float (&b)[8]) {
+  x.x = pro2<PRO>(x.x, a[0], b[0], a[1], b[1]);
+  x.y = pro2<PRO>(x.y, a[2], b[2], a[3], b[3]);
+  x.z = pro2<PRO>(x.z, a[4], b[4], a[5], b[5]);
+  x.w = pro2<PRO>(x.w, a[6], b[6], a[7], b[7]);
+  return x;
+}
+
+constexpr int FR_WGRAD_CT = 64;  // co and ci tile of every weight-gradient slab kernel
+
+// Launch of one weight-gradient slab kernel instance (CT co x CT ci dW tiles x nsplit groups, `lds` bytes of dynamic LDS):
+// attribute once per device, launch, error check, then the slab sum unless the caller defers it (prev_* of a later launch,
+// or fr_reduce_slabs).  A plain launch on purpose, not FR_LAUNCH_KERNEL: an armed stop event (fr_arm_stop_event) must
+// not attach to this kernel and complete before the slab sum behind it.
+template <auto Kern>
+int fr_launch_slab_kernel(const FrWgradArgs& a, hipStream_t st, int threads, int lds) {
+  static unsigned long long attr_done = 0;  // one bit per device
+  if (fr_attr_needed(attr_done)) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    fr_attr_done(attr_done);
+  }
+  const int tiles = (a.Cout / FR_WGRAD_CT) * (a.SC / FR_WGRAD_CT);
+  hipLaunchKernelGGL(Kern, dim3(tiles * a.nsplit), dim3(threads), lds, st, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    fr_set_error(hipGetErrorString(e));
+    return (int)e;
+  }
+  if (a.defer) return 0;
+  return fr_launch_reduce_slabs(a.slab, a.nsplit, (long long)a.Cout * 9 * a.SC, a.dw, st);
+}
+// f(std::integral_constant<int, PRO>) for the prologue of a weight-gradient launch
+template <class F>
+int fr_by_pro(int pro, F f) {
+  switch (pro) {
+    case FR_PRO_NONE: return f(std::integral_constant<int, FR_PRO_NONE>{});
+    case FR_PRO_BN: return f(std::integral_constant<int, FR_PRO_BN>{});
+    case FR_PRO_PRELU: return f(std::integral_constant<int, FR_PRO_PRELU>{});
+  }
+  FR_UNSUPPORTED("fr_conv_wgrad_strip: unknown prologue");
 }
 #endif
