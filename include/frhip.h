@@ -549,6 +549,28 @@ int fr_col_normalize(const float* K, float* kn, float* kt, float* inv, int D, in
  * gradient GEMM's rows), gK in K's [D][N] layout */
 int fr_col_normalize_bwd(const float* GW, const float* kn, const float* inv, float* gK, int D, int N, void* stream);
 
+/* ---- CurricularFace (head/metrics.py:475-510) on the raw cosines cos [rows][ld] of the FR_EPI_STORE GEMM between
+ *      fr_row_normalize'd embeddings and the fr_col_normalize'd [D][N] kernel; c = clamp(cos, -1, 1) (NaN passes).
+ *      t is a one-float DEVICE buffer (the module's EMA buffer): no entry point reads it on the host. */
+/* per-row values (:497-502), rowv [4][rows]: tl = c[label], ctm = tl*cos_m - sqrt(1 - tl^2)*sin_m,
+ * final = tl > th ? ctm : tl - mm, flag = tl > th (1.0 / 0.0).  A label outside [0, N) has no target: tl = 0.
+ * mean[0] = the batch mean of tl, added in a fixed order in double by one workgroup (bit-reproducible).  train = 1 also
+ * updates t[0] <- 0.01*mean + 0.99*t[0] (:505-506; the reference does so on every forward call); train = 0 leaves t alone,
+ * for a caller that averages mean over the ranks first and then calls fr_curricular_ema. */
+int fr_curricular_rows(const float* cos, const int64_t* label, float* rowv, float* mean, float* t, int rows, int N, int ld,
+                       float cos_m, float sin_m, float th, float mm, int train, void* stream);
+/* t[0] <- 0.01*(scale*mean[0]) + 0.99*t[0]: the update above from a mean summed over `1 / scale` ranks */
+int fr_curricular_ema(float* t, const float* mean, float scale, void* stream);
+/* out[m][n] = s * (n == label[m] ? final[m] : (c > ctm[m] ? c*(t + c) : c))  (:501-509); ld a multiple of 4, columns N..ld of
+ * out are written as 0.  A label outside [0, N) selects nothing. */
+int fr_curricular_apply(const float* cos, const int64_t* label, const float* rowv, const float* t, float* out, int rows,
+                        int N, int ld, float s, void* stream);
+/* gcos[m][n] = g[m][n] * d out / d cos with t, the hard mask and the branch flag constant: s*(t + 2c) on hard negatives, s on
+ * easy ones, on the label column s*(cos_m + sin_m*tl/sqrt(1 - tl^2)) where flag is set and s where it is not; 0 where the
+ * clamp saturated (the closed interval passes) and in the padding columns N..ldg.  g is [rows][N] contiguous. */
+int fr_curricular_bwd(const float* g, const float* cos, const int64_t* label, const float* rowv, const float* t, float* gcos,
+                      int rows, int N, int ld, int ldg, float cos_m, float sin_m, float s, void* stream);
+
 /* ---- focal loss on the batch-mean cross entropy (loss/focal.py:17-21) + top-k (util/utils.py:343-358) */
 /* per row: lse[m], ce[m] = lse - z[label], rank[m] = #{n: z[n] > z[label]} */
 int fr_ce_rows(const float* logits, const int64_t* label, float* lse, float* ce, int32_t* rank, int rows, int N,

@@ -5,6 +5,7 @@
 //   d phi / d cos of the ArcFace / CosFace margin, label select       head/metrics.py:115-138, :181-189
 //   SphereFace margin (clamp, k, Chebyshev phi, lambda blend, *||x||)  head/metrics.py:236-268
 //   Am_softmax l2_norm(kernel, axis=0), clamp, label margin, *s         head/metrics.py:280-284, :302-331
+//   CurricularFace per-row margin, EMA of t, hard-negative re-weighting head/metrics.py:494-509
 //   FocalLoss on mean CE                                              loss/focal.py:17-21
 //   accuracy top-1/5                                                  util/utils.py:343-358
 //   optim.SGD(momentum, coupled weight decay on group 0)              train.py:196, :313-316
@@ -264,6 +265,108 @@ __global__ __launch_bounds__(256) void col_normalize_bwd_kernel(const float* __r
       if (d < D && j < N) gK[(size_t)d * N + j] = tile[lane][dd];
     }
     __syncthreads();
+  }
+}
+
+// ------------------------------------------------------------------------------------------ CurricularFace
+// head/metrics.py:494-509 on the raw cosines of the FR_EPI_STORE GEMM.  rowv is [4][rows]: tl = clamp(cos[label]),
+// ctm = cos(theta_tl + m), final (the label column's value) and flag (1: the ctm branch, 0: tl - mm).  A row whose label
+// lies outside [0, N) has no target: tl counts as 0.
+constexpr float CURR_MOMENTUM = 0.01f;  // t <- 0.01 mean(tl) + (1 - 0.01) t  (:506)
+
+// one workgroup: the batch mean of tl is added in a fixed order in double (as focal_finalize_kernel), so t is reproducible
+__global__ __launch_bounds__(256) void curricular_rows_kernel(const float* __restrict__ cos,
+                                                              const long long* __restrict__ label,
+                                                              float* __restrict__ rowv, float* __restrict__ mean,
+                                                              float* __restrict__ t, int rows, int N, int ld, float cos_m,
+                                                              float sin_m, float th, float mm, int train) {
+  __shared__ double dred[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  double s = 0.0;
+  for (int i = tid; i < rows; i += 256) {
+    const long long lab = label[i];
+    const float tl = (lab >= 0 && lab < N) ? clamp1(cos[(size_t)i * ld + lab]) : 0.f;
+    const float ctm = tl * cos_m - sqrtf(1.0f - tl * tl) * sin_m;
+    const bool first = tl > th;
+    rowv[i] = tl;
+    rowv[rows + i] = ctm;
+    rowv[2 * rows + i] = first ? ctm : tl - mm;
+    rowv[3 * rows + i] = first ? 1.f : 0.f;
+    s += (double)tl;
+  }
+  s = wave_sum_d(s);
+  if (lane == 0) dred[wave] = s;
+  __syncthreads();
+  if (tid == 0) {
+    const float mu = (float)((dred[0] + dred[1] + dred[2] + dred[3]) / rows);
+    mean[0] = mu;
+    if (train) t[0] = __fadd_rn(__fmul_rn(mu, CURR_MOMENTUM), __fmul_rn(1.0f - CURR_MOMENTUM, t[0]));
+  }
+}
+
+// t <- 0.01 (scale * mean) + 0.99 t: the update of curricular_rows_kernel from a mean summed over the ranks
+__global__ void curricular_ema_kernel(float* __restrict__ t, const float* __restrict__ mean, float scale) {
+  if (threadIdx.x == 0)
+    t[0] = __fadd_rn(__fmul_rn(__fmul_rn(mean[0], scale), CURR_MOMENTUM), __fmul_rn(1.0f - CURR_MOMENTUM, t[0]));
+}
+
+// out = s * (label ? final : (c > ctm ? c (t + c) : c)), c = clamp(cos); the block layout of margin_apply_kernel
+__global__ __launch_bounds__(256) void curricular_apply_kernel(const float* __restrict__ cos,
+                                                               const long long* __restrict__ label,
+                                                               const float* __restrict__ rowv, const float* __restrict__ t,
+                                                               float* __restrict__ out, int rows, int N, int ld, float s) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const long long lab = label[row];
+  const float ctm = rowv[rows + row], fin = rowv[2 * rows + row], tt = t[0];
+  const int end = min(ld, (int)(blockIdx.x + 1) * MARGIN_COLS);
+  for (int n = blockIdx.x * MARGIN_COLS + lane * 4; n < end; n += 256) {
+    const f32x4 ch = *reinterpret_cast<const f32x4*>(cos + (size_t)row * ld + n);
+    f32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float c = clamp1(ch[j]);
+      float v = c > ctm ? c * (tt + c) : c;
+      if (n + j == lab) v = fin;
+      o[j] = n + j < N ? v * s : 0.f;
+    }
+    *reinterpret_cast<f32x4*>(out + (size_t)row * ld + n) = o;
+  }
+}
+
+// gcos = g * d out / d cos with t, the hard mask and the branch flags constant: s (t + 2c) on hard negatives, s on easy
+// ones, s (cos_m + sin_m tl / sqrt(1 - tl^2)) or s on the label column; 0 where the clamp saturated and in the padding
+// columns [N, ldg).  The block layout of margin_apply_bwd_kernel.
+__global__ __launch_bounds__(256) void curricular_bwd_kernel(const float* __restrict__ g, const float* __restrict__ cos,
+                                                             const long long* __restrict__ label,
+                                                             const float* __restrict__ rowv, const float* __restrict__ t,
+                                                             float* __restrict__ gcos, int rows, int N, int ld, int ldg,
+                                                             float cos_m, float sin_m, float s) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const long long lab = label[row];
+  const float tl = rowv[row], ctm = rowv[rows + row], tt = t[0];
+  const float dlab = rowv[3 * rows + row] != 0.f ? cos_m + sin_m * tl / sqrtf(1.0f - tl * tl) : 1.f;
+  const int end = min(ldg, (int)(blockIdx.x + 1) * MARGIN_COLS);
+  for (int n = blockIdx.x * MARGIN_COLS + lane * 4; n < end; n += 256) {
+    f32x4 ch = {0.f, 0.f, 0.f, 0.f};
+    if (n < ld) ch = *reinterpret_cast<const f32x4*>(cos + (size_t)row * ld + n);
+    f32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float v = 0.f;
+      if (n + j < N) {
+        const float c = clamp1(ch[j]);
+        const bool pass = ch[j] >= -1.f && ch[j] <= 1.f;
+        float d = c > ctm ? tt + 2.f * c : 1.f;
+        if (n + j == lab) d = dlab;
+        v = pass ? g[(size_t)row * N + n + j] * s * d : 0.f;
+      }
+      o[j] = v;
+    }
+    *reinterpret_cast<f32x4*>(gcos + (size_t)row * ldg + n) = o;
   }
 }
 
@@ -593,6 +696,39 @@ extern "C" int fr_col_normalize_bwd(const float* GW, const float* kn, const floa
   if (D <= 0 || N <= 0) FR_UNSUPPORTED("fr_col_normalize_bwd: empty");
   hipLaunchKernelGGL(col_normalize_bwd_kernel, dim3((N + 63) / 64), dim3(256), 0, (hipStream_t)stream, GW, kn, inv, gK,
                      D, N);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_curricular_rows(const float* cos, const int64_t* label, float* rowv, float* mean, float* t, int rows,
+                                  int N, int ld, float cos_m, float sin_m, float th, float mm, int train, void* stream) {
+  if (rows <= 0 || N <= 0 || ld < N) FR_UNSUPPORTED("fr_curricular_rows: shape (rows > 0, ld >= N > 0)");
+  if (train != 0 && train != 1) FR_UNSUPPORTED("fr_curricular_rows: train is 0 or 1");
+  hipLaunchKernelGGL(curricular_rows_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, cos, (const long long*)label,
+                     rowv, mean, t, rows, N, ld, cos_m, sin_m, th, mm, train);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_curricular_ema(float* t, const float* mean, float scale, void* stream) {
+  if (!(scale > 0.f)) FR_UNSUPPORTED("fr_curricular_ema: scale > 0 (1 / world size)");
+  hipLaunchKernelGGL(curricular_ema_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, t, mean, scale);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_curricular_apply(const float* cos, const int64_t* label, const float* rowv, const float* t, float* out,
+                                   int rows, int N, int ld, float s, void* stream) {
+  if (rows <= 0 || N <= 0 || ld < N || ld % 4) FR_UNSUPPORTED("fr_curricular_apply: shape (ld >= N, multiple of 4)");
+  hipLaunchKernelGGL(curricular_apply_kernel, dim3(fr_margin_apply_parts(ld), (rows + 3) / 4), dim3(256), 0,
+                     (hipStream_t)stream, cos, (const long long*)label, rowv, t, out, rows, N, ld, s);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_curricular_bwd(const float* g, const float* cos, const int64_t* label, const float* rowv, const float* t,
+                                 float* gcos, int rows, int N, int ld, int ldg, float cos_m, float sin_m, float s,
+                                 void* stream) {
+  if (rows <= 0 || N <= 0 || ld < N || ld % 4 || ldg < ld || ldg % 4)
+    FR_UNSUPPORTED("fr_curricular_bwd: shape (ldg >= ld >= N, multiples of 4)");
+  hipLaunchKernelGGL(curricular_bwd_kernel, dim3(fr_margin_apply_parts(ldg), (rows + 3) / 4), dim3(256), 0,
+                     (hipStream_t)stream, g, cos, (const long long*)label, rowv, t, gcos, rows, N, ld, ldg, cos_m, sin_m, s);
   FR_LAUNCH_CHECK();
 }
 

@@ -250,6 +250,114 @@ class MarginExtHeadFn(torch.autograd.Function):
         return gx, gw, None, None, None, None, None
 
 
+def curricular_forward(x, kernel, label, t, s, m, group=None):
+    """CurricularFace logits (head/metrics.py:490-510) for fp32 device tensors; ``kernel`` is [D, N], ``t`` the module's
+    one-float device buffer, updated in place before it is used (no host read).  ``group``: the batch mean of the target
+    cosines is averaged over that process group first (equal batch sizes on every rank), so every rank holds the ``t`` of one
+    head over the global batch.  Returns (logits, saved, cfg) for ``curricular_backward``."""
+    B, D = x.shape
+    N = kernel.shape[1]
+    dev = x.device
+    st = ops.current_stream_ptr()
+    x = x.contiguous().float()
+    w = kernel.contiguous().float()
+    label = label.contiguous().long()
+    Np = _pad(N, 32)
+    xn = torch.empty(B, D, device=dev)
+    inv_x = torch.empty(B, device=dev)
+    wn = torch.empty(Np, D, device=dev)  # GEMM B operand, rows >= N zero
+    wt = torch.empty(D, Np, device=dev)  # its transpose, the B operand of the data gradient
+    inv_w = torch.empty(N, device=dev)
+    ops.call("fr_row_normalize", x, xn, None, inv_x, B, B, D, 0, FR_F32, st)()
+    ops.call("fr_col_normalize", w, wn, wt, inv_w, D, N, Np, st)()
+    ld = _pad(N, 4)
+    cos = torch.empty(B, ld, device=dev)
+    ops.conv(st, FR_F32, src=xn, w=wn, out=cos, B=B, RH=1, RW=1, SH=1, SW=1, SC=D, N=N, KH=1, KW=1, stride=1, pad=0,
+             mode=0, lda=D, ldc=ld, pro=0, epi=ops.EPI_STORE, out_f32=1)()
+    cos_m, sin_m = math.cos(m), math.sin(m)
+    th, mm = math.cos(math.pi - m), math.sin(math.pi - m) * m
+    rowv = torch.empty(4, B, device=dev)  # tl, ctm, final, branch flag
+    mean = torch.empty(1, device=dev)
+    ops.call("fr_curricular_rows", cos, label, rowv, mean, t, B, N, ld, cos_m, sin_m, th, mm, int(group is None), st)()
+    if group is not None:
+        import torch.distributed as dist
+        dist.all_reduce(mean, group=group)  # one float, stays on the device
+        ops.call("fr_curricular_ema", t, mean, 1.0 / dist.get_world_size(group), st)()
+    store = torch.empty(B, ld, device=dev)
+    ops.call("fr_curricular_apply", cos, label, rowv, t, store, B, N, ld, float(s), st)()
+    logits = store if ld == N else store[:, :N]
+    # the backward pass needs the t this forward call used: the buffer moves on with the next call
+    saved = (x, w, label, xn, wn, wt, inv_x, inv_w, cos, rowv, t.clone())
+    cfg = (float(s), cos_m, sin_m, Np, ld)
+    return logits, saved, cfg
+
+
+def curricular_backward(saved, cfg, g, need_x, need_w):
+    """(gx, gkernel) of ``curricular_forward``; gkernel is [D, N].  The GEMMs of ``margin_ext_backward``, between
+    fr_curricular_bwd and the two normalisation backwards."""
+    x, w, label, xn, wn, wt, inv_x, inv_w, cos, rowv, t = saved
+    s, cos_m, sin_m, Np, ld = cfg
+    B, D = x.shape
+    N = w.shape[1]
+    dev = x.device
+    st = ops.current_stream_ptr()
+    g = g.contiguous().float()
+    gcos = torch.empty(B, Np, device=dev)
+    ops.call("fr_curricular_bwd", g, cos, label, rowv, t, gcos, B, N, ld, Np, cos_m, sin_m, s, st)()
+    N4 = _pad(N, 4)  # the weight-gradient GEMM wants 16-byte channel counts; gcos columns >= N are zero
+
+    def weight_grad(stream, GW):
+        ops.wgrad(stream, FR_F32, g=gcos, src=xn, dw=GW, B=B, GH=1, GW=1, Cout=N4, SH=1, SW=1, SC=D, KH=1, KW=1,
+                  stride=1, pad=0, ldg=Np, lda=D, pro=0, nsplit=1)()
+        gw = torch.empty_like(w)
+        ops.call("fr_col_normalize_bwd", GW, wn, inv_w, gw, D, N, stream)()
+        return gw
+
+    gx = gw = None
+    # the weight's half on the weight-gradient stream, as margin_backward does
+    side = _head_side_stream(dev) if (need_x and need_w) else None
+    if side is not None:
+        main = torch.cuda.current_stream(dev)
+        GW = torch.empty(N4, D, device=dev)
+        side.wait_stream(main)
+        sp = ops.stream_ptr(side)
+        ops.call("fr_fill_rows", GW, None, N4, D, sp)()
+        gw = weight_grad(sp, GW)
+        need_w = False
+    if need_x:
+        Gx = torch.empty(B, D, device=dev)
+        nk = Np // 32
+        splitk = max(1, min(nk, 64, nk // 8))
+        slab = torch.empty(splitk, B, D, device=dev)  # K slices to slabs, added in a fixed order (reproducible)
+        ops.conv(st, FR_F32, src=gcos, w=wt, out=slab, B=B, RH=1, RW=1, SH=1, SW=1, SC=Np, N=D, KH=1, KW=1,
+                 stride=1, pad=0, mode=0, lda=Np, ldc=D, pro=0, epi=ops.EPI_SLAB, out_f32=1, splitk=splitk)()
+        ops.call("fr_reduce_parts", slab, splitk, 1, B * D, Gx, None, None, st)()
+        gx = torch.empty(B, D, device=dev)
+        ops.call("fr_normalize_bwd", Gx, x, inv_x, gx, B, D, st)()
+    if need_w:
+        gw = weight_grad(st, torch.zeros(N4, D, device=dev))
+    if side is not None:
+        main.wait_stream(side)
+    return gx, gw
+
+
+class CurricularHeadFn(torch.autograd.Function):
+    """CurricularFace (head/metrics.py:475-510) on the HIP path; see ``curricular_forward``."""
+
+    @staticmethod
+    def forward(ctx, x, kernel, label, t, s, m, group):
+        logits, saved, cfg = curricular_forward(x, kernel, label, t, s, m, group)
+        ctx.save_for_backward(*saved)
+        ctx.cfg = cfg
+        ctx.mark_non_differentiable(label)
+        return logits
+
+    @staticmethod
+    def backward(ctx, g):
+        gx, gw = curricular_backward(ctx.saved_tensors, ctx.cfg, g, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return gx, gw, None, None, None, None, None
+
+
 CHECK_LABELS = True  # host-side range check of the labels (one device sync per call); loops with validated data clear it
 
 
@@ -274,6 +382,19 @@ def margin_ext_head(x, weight, label, kind, mi, p0, p1):
         return x.new_zeros((0, n), dtype=torch.float32) + 0.0 * (x.sum() + weight.sum())
     _check_labels(label, n)
     return MarginExtHeadFn.apply(x, weight, label, kind, mi, p0, p1)
+
+
+def curricular_head(x, kernel, label, t, s, m, group=None):
+    """CurricularFace logits; the empty batch and label check of ``margin_head``.  ``t`` (float32 [1] on x's device) is
+    updated in place; an empty batch leaves it as it is (the reference's mean over no rows turns it into NaN for good)."""
+    n = kernel.shape[1]
+    if x.shape[0] == 0:
+        ops.ptr(x)
+        return x.new_zeros((0, n), dtype=torch.float32) + 0.0 * (x.sum() + kernel.sum())
+    _check_labels(label, n)
+    if t.dtype != torch.float32 or t.numel() != 1 or t.device != x.device or not t.is_contiguous():
+        raise ValueError("curricular_head: t must be a contiguous float32 tensor of one element on %s" % (x.device,))
+    return CurricularHeadFn.apply(x, kernel, label, t, s, m, group)
 
 
 class FocalLossFn(torch.autograd.Function):

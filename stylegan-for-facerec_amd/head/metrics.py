@@ -1,18 +1,25 @@
 """Margin-softmax heads with the reference's import path, constructor signatures and state-dict keys.
 
     from head.metrics import ArcFace, CosFace, SphereFace, Am_softmax        (reference train.py:9)
+    from head.metrics import CurricularFace                                  (reference head/metrics.py:475)
 
-All four heads the reference driver can select (``HEAD_NAME``, train.py:56,178-182) run on the HIP kernels when their
-input is a device tensor:
+The four heads the reference driver can select (``HEAD_NAME``, train.py:56,178-182) and ``CurricularFace`` (one of the
+FaceX-Zoo heads of the reference's head/metrics.py that its driver never names; train.py here accepts it) run on the HIP
+kernels when their input is a device tensor:
   * ``ArcFace`` / ``CosFace`` (the two heads the shipped configs and BASELINE.json name): row normalise -> MFMA cosine
     GEMM with the margin / label-select / scale epilogue -> closed-form backward;
   * ``SphereFace`` / ``Am_softmax``: the same cosine GEMM stores the raw cosines, a row kernel applies the clamp and the
     margin (SphereFace: Chebyshev phi, lambda blend, times ||x||; Am_softmax: c - m on the label, times s), and the
     backward pass reads the raw cosines again for the clamp mask.  Am_softmax normalises the columns of its [in, out]
-    ``kernel`` (no eps) and not the embeddings.
-On host tensors ``SphereFace`` / ``Am_softmax`` run the reference's plain-PyTorch arithmetic (the restatement the tests
-compare with); ``ArcFace`` / ``CosFace`` refuse host tensors.  ``SphereFace.iter`` counts forward calls on either path, as
-in the reference; train.py carries it across a resume in the State_* file.
+    ``kernel`` (no eps) and not the embeddings;
+  * ``CurricularFace``: rows and ``kernel`` columns normalised, raw cosines from the same GEMM; one workgroup takes the
+    per-row target cosine, cos(theta + m), the label column's value and the batch mean, and moves the buffer ``t`` on the
+    device (no host read in the step); a row kernel re-weights the negatives above their row's cos(theta + m) by
+    ``t + c``; the backward pass treats ``t``, that mask and the branch choice as constants.
+On host tensors ``SphereFace`` / ``Am_softmax`` / ``CurricularFace`` run the reference's plain-PyTorch arithmetic (the
+restatement the tests compare with); ``ArcFace`` / ``CosFace`` refuse host tensors.  ``SphereFace.iter`` counts forward
+calls on either path, as in the reference; train.py carries it across a resume in the State_* file.  ``CurricularFace.t``
+is a buffer: the Head_* file carries it.
 
 Differences from the reference that a caller can observe:
   * ``device_id`` is accepted for signature compatibility but the class-dimension ``.cuda(i)`` split of
@@ -21,10 +28,15 @@ Differences from the reference that a caller can observe:
   * the reference's ArcFace allocates its one-hot on ``'cuda'`` unconditionally (metrics.py:133) and takes an
     optional ``onehot_vec``; here the label select happens inside the GEMM epilogue (bit-exact equivalent of
     the blend for finite values), ``onehot_vec`` is accepted and ignored.
+  * ``CurricularFace`` on the device path divides the kernel's columns by their norm without the eps = 1e-12 of the
+    reference's ``F.normalize(kernel, dim=0)``: a column of norm below 1e-12 is out of contract.  A target cosine of
+    exactly +-1 makes the reference's own gradient infinite (sin_m * tl / sqrt(1 - tl^2)); nothing is done about it here
+    either.  An empty batch leaves ``t`` as it is (the reference's mean over no rows makes it NaN for good).
 """
 import math
 
 import torch
+import torch.distributed as dist
 import torch.nn as nn
 import torch.nn.functional as F
 from torch.nn import Parameter
@@ -139,3 +151,48 @@ class Am_softmax(nn.Module):
         c = torch.mm(embbedings, kn / kn.norm(2, 0, True)).clamp(-1, 1)
         hot = torch.zeros_like(c).scatter_(1, label.view(-1, 1), 1).bool()
         return torch.where(hot, c - self.m, c) * self.s
+
+
+class CurricularFace(nn.Module):
+    """CurricularFace (reference head/metrics.py:475-510): HIP kernels on device tensors, plain PyTorch on the host.
+
+    ``t`` moves on every forward call, training or not, as in the reference, and the updated value is the one the call uses.
+    ``process_group``: the reference's nn.DataParallel shows one head the global batch; with one replica per rank, set this
+    to the ranks' group and the batch mean of the target cosines is averaged over it before it enters ``t`` (one float, a
+    device tensor on the device path), so every rank holds the ``t`` of a single head over the concatenated batch.  That
+    takes equal batch sizes on every rank (DROP_LAST).  Limits: see the module docstring (kernel columns of norm below
+    1e-12; target cosines of exactly +-1)."""
+
+    def __init__(self, feat_dim, num_class, m=0.5, s=64.):
+        super().__init__()
+        self.m, self.s = m, s
+        self.cos_m, self.sin_m = math.cos(m), math.sin(m)
+        self.threshold = math.cos(math.pi - m)
+        self.mm = math.sin(math.pi - m) * m
+        self.kernel = Parameter(torch.empty(feat_dim, num_class))
+        self.register_buffer('t', torch.zeros(1))
+        nn.init.normal_(self.kernel, std=0.01)
+        self.process_group = None
+
+    def forward(self, feats, labels):
+        if feats.is_cuda:
+            if self.kernel.device != feats.device:
+                self.to(feats.device)  # moved once, next to the features
+            return FRF.curricular_head(feats, self.kernel, labels.to(feats.device), self.t, self.s, self.m,
+                                       self.process_group)
+        kernel = self.kernel.to(feats.device)
+        c = torch.mm(F.normalize(feats), F.normalize(kernel, dim=0)).clamp(-1, 1)
+        at = labels.view(-1, 1).long()
+        tl = c.gather(1, at)
+        ctm = tl * self.cos_m - torch.sqrt(1.0 - torch.pow(tl, 2)) * self.sin_m  # cos(theta_target + m)
+        final = torch.where(tl > self.threshold, ctm, tl - self.mm)
+        if tl.numel():
+            with torch.no_grad():
+                mean = tl.mean()
+                if self.process_group is not None:
+                    dist.all_reduce(mean, group=self.process_group)
+                    mean = mean / dist.get_world_size(self.process_group)
+                self.t = mean * 0.01 + (1 - 0.01) * self.t
+        hard = (c > ctm).detach()
+        out = torch.where(hard, c * (self.t + c), c).scatter(1, at, final)
+        return out * self.s

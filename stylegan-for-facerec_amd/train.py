@@ -35,7 +35,7 @@ from frhip import functional as FRF
 from frhip import set_compute_dtype
 from frhip.optim import SGD, Adam
 from frhip.parallel import DataParallel
-from head.metrics import Am_softmax, ArcFace, CosFace, SphereFace
+from head.metrics import Am_softmax, ArcFace, CosFace, CurricularFace, SphereFace
 from loss.focal import FocalLoss
 from util.utils import (AverageMeter, accuracy, buffer_val, collate_fn_ignore_none, get_time, get_val_data, perform_val,
                         schedule_lr, separate_irse_bn_paras, warm_up_lr)
@@ -185,8 +185,13 @@ def main():
         print("Backbone compute dtype: {}".format(cdt if cdt is not None else "process default (FRHIP_COMPUTE_DTYPE)"))
     emb, s = cfg["EMBEDDING_SIZE"], cfg.get("ARCFACE_S", 64.0)
     heads = {"ArcFace": ArcFace(emb, num_class, None, s=s), "CosFace": CosFace(emb, num_class, None),
-             "SphereFace": SphereFace(emb, num_class, None), "Am_softmax": Am_softmax(emb, num_class, None)}
+             "SphereFace": SphereFace(emb, num_class, None), "Am_softmax": Am_softmax(emb, num_class, None),
+             "CurricularFace": CurricularFace(emb, num_class, s=s)}
     head = heads[cfg["HEAD_NAME"]]
+    if world > 1 and hasattr(head, "process_group"):
+        # CurricularFace: t follows the mean target cosine of the GLOBAL batch, as under the reference's nn.DataParallel
+        # (equal per-rank batch sizes: DROP_LAST)
+        head.process_group = dist.group.WORLD
     bn_params, other_params = separate_irse_bn_paras(backbone)
     _, head_params = separate_irse_bn_paras(head)
 

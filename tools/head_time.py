@@ -2,7 +2,13 @@
 calls (mode fwdbwd) after 3 warm-up calls, event-timed; run it under `rocprofv3 --kernel-trace --stats -- ...` for the
 kernel times (profiles/margin_heads_b256_n28000.txt).
 
-    python tools/head_time.py {ArcFace|CosFace|SphereFace|Am_softmax} {fwd|fwdbwd} ITERS
+    python tools/head_time.py {ArcFace|CosFace|SphereFace|Am_softmax|CurricularFace} {fwd|fwdbwd} ITERS
+
+Several heads, comma separated, are timed in ONE process in alternating rounds (ROUNDS rounds of ITERS calls per head, the
+median round of each head reported, and the ratio to the first head named), so clocks and allocator state are shared
+(profiles/curricular_head_b256_n28000.txt):
+
+    python tools/head_time.py Am_softmax,ArcFace,CurricularFace fwdbwd ITERS [ROUNDS]
 """
 import os
 import sys
@@ -13,31 +19,54 @@ import torch  # noqa: E402
 from frhip import synth, functional as FRF  # noqa: E402
 from head import metrics as H  # noqa: E402
 
-name, mode, iters = sys.argv[1], sys.argv[2], int(sys.argv[3])
+names, mode, iters = sys.argv[1].split(","), sys.argv[2], int(sys.argv[3])
+rounds = int(sys.argv[4]) if len(sys.argv) > 4 else 5
 B, D, N = 256, 512, 28000
 FRF.CHECK_LABELS = False
-head = getattr(H, name)(D, N, None).cuda()
 x = synth.normal(5, "t.x", (B, D)).cuda().requires_grad_(mode == "fwdbwd")
 label = synth.labels(5, "t.y", B, N).cuda()
 g = synth.normal(5, "t.g", (B, N)).cuda()
-p = list(head.parameters())[0]
 
 
-def step():
-    y = head(x, label)
-    if mode == "fwdbwd":
-        x.grad = None
-        p.grad = None
-        y.backward(g)
+def make(name):
+    cls = getattr(H, name)
+    head = (cls(D, N) if name == "CurricularFace" else cls(D, N, None)).cuda()  # FaceX-Zoo heads take no device_id
+    p = list(head.parameters())[0]
+
+    def step():
+        y = head(x, label)
+        if mode == "fwdbwd":
+            x.grad = None
+            p.grad = None
+            y.backward(g)
+
+    return step
 
 
-for _ in range(3):
-    step()
+def timed(step, n):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        step()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / n
+
+
+steps = {name: make(name) for name in names}
+for step in steps.values():
+    for _ in range(3):
+        step()
 torch.cuda.synchronize()
-e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-e0.record()
-for _ in range(iters):
-    step()
-e1.record()
-torch.cuda.synchronize()
-print("HEADTIME %s %s %.1f us/call (events, %d calls)" % (name, mode, e0.elapsed_time(e1) * 1e3 / iters, iters))
+if len(names) == 1:
+    print("HEADTIME %s %s %.1f us/call (events, %d calls)" % (names[0], mode, timed(steps[names[0]], iters), iters))
+else:
+    per = {name: [] for name in names}
+    for _ in range(rounds):
+        for name in names:
+            per[name].append(timed(steps[name], iters))
+    med = {name: sorted(v)[len(v) // 2] for name, v in per.items()}
+    for name in names:
+        print("HEADTIME %-14s %s median %.1f us/call, rounds %s, %.3f x %s (events, %d rounds of %d calls, alternating)"
+              % (name, mode, med[name], " ".join("%.1f" % t for t in per[name]), med[name] / med[names[0]], names[0],
+                 rounds, iters))
