@@ -127,70 +127,93 @@ __device__ __forceinline__ float sphere_label(float c, int mi, float div, float*
   return (phi - c) / div + c;
 }
 
-// kind 2: out = nrm * (label ? sphere : c), nrm = ||x_m|| (p0 = 1 + lambda);  kind 3: out = p1 * (label ? c - p0 : c)
-__global__ __launch_bounds__(256) void margin_apply_kernel(const float* __restrict__ cos, const long long* __restrict__ label,
-                                                           const float* __restrict__ inv_x, float* __restrict__ out,
-                                                           int rows, int N, int ld, int kind, int mi, float p0, float p1) {
+// Forward walker of one row: out[n] = body(n, raw cosine) for n < N, 0 in the padding columns [N, ld)
+template <typename Body>
+__device__ __forceinline__ void margin_cols_fwd(const float* __restrict__ cos, float* __restrict__ out, int row, int N,
+                                                int ld, Body body) {
   const int lane = threadIdx.x & 63;
-  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const long long lab = label[row];
-  const float scale = kind == 2 ? 1.f / inv_x[row] : p1;
   const int end = min(ld, (int)(blockIdx.x + 1) * MARGIN_COLS);
   for (int n = blockIdx.x * MARGIN_COLS + lane * 4; n < end; n += 256) {
     const f32x4 ch = *reinterpret_cast<const f32x4*>(cos + (size_t)row * ld + n);
     f32x4 o;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float c = clamp1(ch[j]);
-      float v = c;
-      if (n + j == lab) {
-        float unused;
-        v = kind == 2 ? sphere_label(c, mi, p0, &unused) : c - p0;
-      }
-      o[j] = n + j < N ? v * scale : 0.f;
+      const float v = body(n + j, ch[j]);
+      o[j] = n + j < N ? v : 0.f;
     }
     *reinterpret_cast<f32x4*>(out + (size_t)row * ld + n) = o;
   }
 }
 
-// gcos = g * d out / d cos, 0 where the clamp saturated (torch.clamp passes gradient on the closed interval) and in the
-// padding columns [N, ldg).  kind 2 also leaves r_part[row][blockIdx.x] = sum over the block's columns of g * out / nrm.
-__global__ __launch_bounds__(256) void margin_apply_bwd_kernel(const float* __restrict__ g, const float* __restrict__ cos,
-                                                               const long long* __restrict__ label,
-                                                               const float* __restrict__ inv_x, float* __restrict__ gcos,
-                                                               float* __restrict__ r_part, int rows, int N, int ld, int ldg,
-                                                               int kind, int mi, float p0, float p1) {
+// Backward walker of one row: gcos[n] = body(n, raw cosine, g[n]) where the clamp passes gradient (torch.clamp: the closed
+// interval), 0 where it saturated and in the padding columns [N, ldg).  cos has the pitch ld <= ldg.
+template <typename Body>
+__device__ __forceinline__ void margin_cols_bwd(const float* __restrict__ g, const float* __restrict__ cos,
+                                                float* __restrict__ gcos, int row, int N, int ld, int ldg, Body body) {
   const int lane = threadIdx.x & 63;
-  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const long long lab = label[row];
-  const float scale = kind == 2 ? 1.f / inv_x[row] : p1;
+  const float* crow = cos + (size_t)row * ld;
+  const float* grow = g + (size_t)row * N;
+  float* orow = gcos + (size_t)row * ldg;
   const int end = min(ldg, (int)(blockIdx.x + 1) * MARGIN_COLS);
-  float r = 0.f;
   for (int n = blockIdx.x * MARGIN_COLS + lane * 4; n < end; n += 256) {
     f32x4 ch = {0.f, 0.f, 0.f, 0.f};
-    if (n < ld) ch = *reinterpret_cast<const f32x4*>(cos + (size_t)row * ld + n);
+    if (n < ld) ch = *reinterpret_cast<const f32x4*>(crow + n);
     f32x4 o;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float v = 0.f;
       if (n + j < N) {
-        const float gg = g[(size_t)row * N + n + j];
-        const float c = clamp1(ch[j]);
+        const float gg = grow[n + j];
         const bool pass = ch[j] >= -1.f && ch[j] <= 1.f;
-        float a = c, d = 1.f;
-        if (kind == 2 && n + j == lab) a = sphere_label(c, mi, p0, &d);
-        if (kind == 2) r = fmaf(gg, a, r);
-        v = pass ? gg * scale * d : 0.f;
+        const float d = body(n + j, ch[j], gg);
+        v = pass ? d : 0.f;
       }
       o[j] = v;
     }
-    *reinterpret_cast<f32x4*>(gcos + (size_t)row * ldg + n) = o;
+    *reinterpret_cast<f32x4*>(orow + n) = o;
   }
+}
+
+// kind 2: out = nrm * (label ? sphere : c), nrm = ||x_m|| (p0 = 1 + lambda);  kind 3: out = p1 * (label ? c - p0 : c)
+__global__ __launch_bounds__(256) void margin_apply_kernel(const float* __restrict__ cos, const long long* __restrict__ label,
+                                                           const float* __restrict__ inv_x, float* __restrict__ out,
+                                                           int rows, int N, int ld, int kind, int mi, float p0, float p1) {
+  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const long long lab = label[row];
+  const float scale = kind == 2 ? 1.f / inv_x[row] : p1;
+  margin_cols_fwd(cos, out, row, N, ld, [&](int n, float raw) {
+    const float c = clamp1(raw);
+    float v = c;
+    if (n == lab) {
+      float unused;
+      v = kind == 2 ? sphere_label(c, mi, p0, &unused) : c - p0;
+    }
+    return v * scale;
+  });
+}
+
+// gcos = g * d out / d cos.  kind 2 also leaves r_part[row][blockIdx.x] = sum over the block's columns of g * out / nrm.
+__global__ __launch_bounds__(256) void margin_apply_bwd_kernel(const float* __restrict__ g, const float* __restrict__ cos,
+                                                               const long long* __restrict__ label,
+                                                               const float* __restrict__ inv_x, float* __restrict__ gcos,
+                                                               float* __restrict__ r_part, int rows, int N, int ld, int ldg,
+                                                               int kind, int mi, float p0, float p1) {
+  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const long long lab = label[row];
+  const float scale = kind == 2 ? 1.f / inv_x[row] : p1;
+  float r = 0.f;
+  margin_cols_bwd(g, cos, gcos, row, N, ld, ldg, [&](int n, float raw, float gg) {
+    const float c = clamp1(raw);
+    float a = c, d = 1.f;
+    if (kind == 2 && n == lab) a = sphere_label(c, mi, p0, &d);
+    if (kind == 2) r = fmaf(gg, a, r);
+    return gg * scale * d;
+  });
   if (kind == 2) {
     r = wave_sum(r);
-    if (lane == 0) r_part[(size_t)row * gridDim.x + blockIdx.x] = r;
+    if ((threadIdx.x & 63) == 0) r_part[(size_t)row * gridDim.x + blockIdx.x] = r;
   }
 }
 
@@ -310,64 +333,41 @@ __global__ void curricular_ema_kernel(float* __restrict__ t, const float* __rest
     t[0] = __fadd_rn(__fmul_rn(__fmul_rn(mean[0], scale), CURR_MOMENTUM), __fmul_rn(1.0f - CURR_MOMENTUM, t[0]));
 }
 
-// out = s * (label ? final : (c > ctm ? c (t + c) : c)), c = clamp(cos); the block layout of margin_apply_kernel
+// out = s * (label ? final : (c > ctm ? c (t + c) : c)), c = clamp(cos)
 __global__ __launch_bounds__(256) void curricular_apply_kernel(const float* __restrict__ cos,
                                                                const long long* __restrict__ label,
                                                                const float* __restrict__ rowv, const float* __restrict__ t,
                                                                float* __restrict__ out, int rows, int N, int ld, float s) {
-  const int lane = threadIdx.x & 63;
   const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const long long lab = label[row];
   const float ctm = rowv[rows + row], fin = rowv[2 * rows + row], tt = t[0];
-  const int end = min(ld, (int)(blockIdx.x + 1) * MARGIN_COLS);
-  for (int n = blockIdx.x * MARGIN_COLS + lane * 4; n < end; n += 256) {
-    const f32x4 ch = *reinterpret_cast<const f32x4*>(cos + (size_t)row * ld + n);
-    f32x4 o;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float c = clamp1(ch[j]);
-      float v = c > ctm ? c * (tt + c) : c;
-      if (n + j == lab) v = fin;
-      o[j] = n + j < N ? v * s : 0.f;
-    }
-    *reinterpret_cast<f32x4*>(out + (size_t)row * ld + n) = o;
-  }
+  margin_cols_fwd(cos, out, row, N, ld, [&](int n, float raw) {
+    const float c = clamp1(raw);
+    float v = c > ctm ? c * (tt + c) : c;
+    if (n == lab) v = fin;
+    return v * s;
+  });
 }
 
 // gcos = g * d out / d cos with t, the hard mask and the branch flags constant: s (t + 2c) on hard negatives, s on easy
-// ones, s (cos_m + sin_m tl / sqrt(1 - tl^2)) or s on the label column; 0 where the clamp saturated and in the padding
-// columns [N, ldg).  The block layout of margin_apply_bwd_kernel.
+// ones, s (cos_m + sin_m tl / sqrt(1 - tl^2)) or s on the label column
 __global__ __launch_bounds__(256) void curricular_bwd_kernel(const float* __restrict__ g, const float* __restrict__ cos,
                                                              const long long* __restrict__ label,
                                                              const float* __restrict__ rowv, const float* __restrict__ t,
                                                              float* __restrict__ gcos, int rows, int N, int ld, int ldg,
                                                              float cos_m, float sin_m, float s) {
-  const int lane = threadIdx.x & 63;
   const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const long long lab = label[row];
   const float tl = rowv[row], ctm = rowv[rows + row], tt = t[0];
   const float dlab = rowv[3 * rows + row] != 0.f ? cos_m + sin_m * tl / sqrtf(1.0f - tl * tl) : 1.f;
-  const int end = min(ldg, (int)(blockIdx.x + 1) * MARGIN_COLS);
-  for (int n = blockIdx.x * MARGIN_COLS + lane * 4; n < end; n += 256) {
-    f32x4 ch = {0.f, 0.f, 0.f, 0.f};
-    if (n < ld) ch = *reinterpret_cast<const f32x4*>(cos + (size_t)row * ld + n);
-    f32x4 o;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float v = 0.f;
-      if (n + j < N) {
-        const float c = clamp1(ch[j]);
-        const bool pass = ch[j] >= -1.f && ch[j] <= 1.f;
-        float d = c > ctm ? tt + 2.f * c : 1.f;
-        if (n + j == lab) d = dlab;
-        v = pass ? g[(size_t)row * N + n + j] * s * d : 0.f;
-      }
-      o[j] = v;
-    }
-    *reinterpret_cast<f32x4*>(gcos + (size_t)row * ldg + n) = o;
-  }
+  margin_cols_bwd(g, cos, gcos, row, N, ld, ldg, [&](int n, float raw, float gg) {
+    const float c = clamp1(raw);
+    float d = c > ctm ? tt + 2.f * c : 1.f;
+    if (n == lab) d = dlab;
+    return gg * s * d;
+  });
 }
 
 // ------------------------------------------------------------------------------------------ cross entropy rows

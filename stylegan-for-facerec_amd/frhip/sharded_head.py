@@ -182,7 +182,7 @@ class ShardedHeadLossFn(torch.autograd.Function):
         if G_all is not None:
             G = C.reduce_scatter_rows(G_all)
             lo, hi = ctx.rows_of_rank
-            inv_x = ctx.saved[5][lo:hi].contiguous()
+            inv_x = ctx.saved.inv_x[lo:hi].contiguous()
             gx = K.normalize_bwd(G, x_loc, inv_x)
             if head.grad_scale != 1.0:
                 gx = gx * head.grad_scale

@@ -44,6 +44,13 @@ from torch.nn import Parameter
 from frhip import functional as FRF
 
 
+def _beside(module, param, input):
+    """The reference keeps HEAD on the host and copies W every step (train.py never calls HEAD.to); here the module is
+    moved once, next to the features."""
+    if param.device != input.device:
+        module.to(input.device)
+
+
 class _MarginHead(nn.Module):
     _kind = 0
 
@@ -58,13 +65,8 @@ class _MarginHead(nn.Module):
         nn.init.xavier_uniform_(self.weight)  # metrics.py:87-88 / :163-164
 
     def _logits(self, input, label, easy_margin=False):
-        w = self.weight
-        if w.device != input.device:
-            # the reference keeps HEAD on the host and copies W every step (train.py never calls HEAD.to);
-            # here the parameter is moved once, next to the features
-            self.to(input.device)
-            w = self.weight
-        return FRF.margin_head(input, w, label.to(input.device), self._kind, self.s, self.m, easy_margin)
+        _beside(self, self.weight, input)
+        return FRF.margin_head(input, self.weight, label.to(input.device), self._kind, self.s, self.m, easy_margin)
 
     def __repr__(self):
         return "%s(in_features = %d, out_features = %d, s = %s, m = %s)" % (
@@ -118,8 +120,7 @@ class SphereFace(nn.Module):
         self.iter += 1
         self.lamb = max(self.LambdaMin, self.base * (1 + self.gamma * self.iter) ** (-1 * self.power))
         if input.is_cuda:
-            if self.weight.device != input.device:
-                self.to(input.device)  # moved once, next to the features (the reference copies W every step)
+            _beside(self, self.weight, input)
             return FRF.margin_ext_head(input, self.weight, label.to(input.device), FRF.SPHEREFACE, self.m,
                                        1 + self.lamb, 0.0)
         w = self.weight.to(input.device)
@@ -143,8 +144,7 @@ class Am_softmax(nn.Module):
 
     def forward(self, embbedings, label):
         if embbedings.is_cuda:
-            if self.kernel.device != embbedings.device:
-                self.to(embbedings.device)
+            _beside(self, self.kernel, embbedings)
             return FRF.margin_ext_head(embbedings, self.kernel, label.to(embbedings.device), FRF.AM_SOFTMAX, 0,
                                        self.m, self.s)
         kn = self.kernel.to(embbedings.device)
@@ -176,8 +176,7 @@ class CurricularFace(nn.Module):
 
     def forward(self, feats, labels):
         if feats.is_cuda:
-            if self.kernel.device != feats.device:
-                self.to(feats.device)  # moved once, next to the features
+            _beside(self, self.kernel, feats)
             return FRF.curricular_head(feats, self.kernel, labels.to(feats.device), self.t, self.s, self.m,
                                        self.process_group)
         kernel = self.kernel.to(feats.device)

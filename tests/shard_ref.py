@@ -9,6 +9,8 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 from oracle import irse_ref as O  # noqa: E402
+sys.path.insert(0, os.path.join(os.path.dirname(HERE), "stylegan-for-facerec_amd"))
+from frhip.functional import HeadSaved  # noqa: E402
 
 
 class OracleKernels(object):
@@ -24,8 +26,9 @@ class OracleKernels(object):
                 sel = O.cosface_forward(xl, wl, lab, s=s, m=m)
             plain = O.cosine_logits(xl, wl) * s
             logits = torch.where(own[:, None], sel, plain)
-        # saved[5] must be a per-row tensor (the HIP path keeps 1/|x| there); the stand-in's G is already d loss / d x
-        saved = (xl, wl, label_local, None, None, torch.ones(x_all.shape[0]), None, logits)
+        # inv_x must be a per-row tensor (the HIP path keeps 1/|x| there); the stand-in's G is already d loss / d x.  The
+        # graph of the logits rides in ``cos``
+        saved = HeadSaved(x=xl, w=wl, label=label_local, inv_x=torch.ones(x_all.shape[0]), cos=logits)
         return logits.detach(), saved, None
 
     def row_stats(self, logits, label_local):
@@ -64,7 +67,7 @@ class OracleKernels(object):
         return k * (torch.exp(logits - lse[:, None]) - hot.float())
 
     def head_bwd(self, saved, cfg, g, need_x, need_w):
-        xl, wl, logits = saved[0], saved[1], saved[7]
+        xl, wl, logits = saved.x, saved.w, saved.cos
         gx, gw = torch.autograd.grad(logits, [xl, wl], g)
         return (gx if need_x else None), (gw if need_w else None)
 
