@@ -559,6 +559,11 @@ int fr_col_normalize_bwd(const float* GW, const float* kn, const float* inv, flo
  * for a caller that averages mean over the ranks first and then calls fr_curricular_ema. */
 int fr_curricular_rows(const float* cos, const int64_t* label, float* rowv, float* mean, float* t, int rows, int N, int ld,
                        float cos_m, float sin_m, float th, float mm, int train, void* stream);
+/* fr_curricular_rows from given target cosines tl [rows] (:497-506 after the gather of :496): the same rowv, mean and
+ * update of t, bit for bit, for the same tl.  The class-sharded head passes the target cosines of the GLOBAL batch
+ * (fr_shard_target_cos summed over the ranks), so every rank holds the rowv and t of one head over that batch. */
+int fr_curricular_rows_from(const float* tl, float* rowv, float* mean, float* t, int rows, float cos_m, float sin_m,
+                            float th, float mm, int train, void* stream);
 /* t[0] <- 0.01*(scale*mean[0]) + 0.99*t[0]: the update above from a mean summed over `1 / scale` ranks */
 int fr_curricular_ema(float* t, const float* mean, float scale, void* stream);
 /* out[m][n] = s * (n == label[m] ? final[m] : (c > ctm[m] ? c*(t + c) : c))  (:501-509); ld a multiple of 4, columns N..ld of
@@ -600,6 +605,16 @@ int fr_shard_row_stats(const float* logits, const int64_t* label_local, float* s
                        void* stream);
 int fr_shard_combine(const float* stats_all, int world, int rows, float* lse, float* ce, float* tlogit, void* stream);
 int fr_shard_rank_rows(const float* logits, const float* tlogit, int32_t* rank, int rows, int N, int ld, void* stream);
+/* what the SphereFace and CurricularFace heads exchange besides the statistics, both [rows]-sized:
+ *   fr_shard_target_cos : tl[m] = clamp(cos[m][label_local], -1, 1) (head/metrics.py:494-496: the clamp, then the gather)
+ *                         where 0 <= label_local < N, else exactly +0: one rank owns each label, so the SUM of the ranks'
+ *                         tl is exact and independent of order; cos is [rows][ld], ld >= N
+ *   fr_shard_sum_parts  : r[m] = r_part[m][0] + ... + r_part[m][nparts-1] in that order (fr_normalize_bwd_radial's): the
+ *                         radial term of SphereFace's row scale (head/metrics.py:255, :268) is a sum over all classes,
+ *                         so over ranks; shards of different width have different nparts, the summed r goes through
+ *                         fr_normalize_bwd_radial with nparts = 1 */
+int fr_shard_target_cos(const float* cos, const int64_t* label_local, float* tl, int rows, int N, int ld, void* stream);
+int fr_shard_sum_parts(const float* r_part, int nparts, float* r, int rows, void* stream);
 
 /* ---- GPU-side training-input transform (replaces the per-sample host transform of train.py:108-116
  *      applied in dataset.py:85-88): Resize(Hr x Wr, Pillow 8-bit bilinear, bit-exact) -> crop S x S at crop[b] = (x0, y0)

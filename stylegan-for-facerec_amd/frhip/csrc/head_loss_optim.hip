@@ -237,6 +237,18 @@ __global__ void normalize_bwd_radial_kernel(const float* __restrict__ G, const f
   }
 }
 
+// r[row] = r_part[row][0] + ... + r_part[row][nparts - 1], in the order normalize_bwd_radial_kernel adds them.  The
+// class-sharded SphereFace head sums r over the ranks (shards of different width have different nparts) and then calls
+// that kernel with nparts = 1.
+__global__ __launch_bounds__(256) void sum_row_parts_kernel(const float* __restrict__ r_part, int nparts,
+                                                            float* __restrict__ r, int rows) {
+  const int row = blockIdx.x * 256 + threadIdx.x;
+  if (row >= rows) return;
+  float acc = 0.f;
+  for (int p = 0; p < nparts; ++p) acc += r_part[(size_t)row * nparts + p];
+  r[row] = acc;
+}
+
 // Am_softmax's l2_norm(kernel, axis=0) (head/metrics.py:280-284, no eps): kt[d][j] = K[d][j] / ||K[:, j]|| in the [D][Np]
 // layout of K (columns N..Np zero), inv[j] = 1 / ||K[:, j]||.  Block = 64 columns x 4 slices of D, slices added in order.
 __global__ __launch_bounds__(256) void col_normalize_kernel(const float* __restrict__ K, float* __restrict__ kt,
@@ -297,26 +309,21 @@ __global__ __launch_bounds__(256) void col_normalize_bwd_kernel(const float* __r
 // lies outside [0, N) has no target: tl counts as 0.
 constexpr float CURR_MOMENTUM = 0.01f;  // t <- 0.01 mean(tl) + (1 - 0.01) t  (:506)
 
-// one workgroup: the batch mean of tl is added in a fixed order in double (as focal_finalize_kernel), so t is reproducible
-__global__ __launch_bounds__(256) void curricular_rows_kernel(const float* __restrict__ cos,
-                                                              const long long* __restrict__ label,
-                                                              float* __restrict__ rowv, float* __restrict__ mean,
-                                                              float* __restrict__ t, int rows, int N, int ld, float cos_m,
-                                                              float sin_m, float th, float mm, int train) {
-  __shared__ double dred[4];
+// the row values of one target cosine, shared by the two row kernels below
+__device__ __forceinline__ void curricular_row_values(float tl, int i, int rows, float* __restrict__ rowv, float cos_m,
+                                                      float sin_m, float th, float mm) {
+  const float ctm = tl * cos_m - sqrtf(1.0f - tl * tl) * sin_m;
+  const bool first = tl > th;
+  rowv[i] = tl;
+  rowv[rows + i] = ctm;
+  rowv[2 * rows + i] = first ? ctm : tl - mm;
+  rowv[3 * rows + i] = first ? 1.f : 0.f;
+}
+
+// batch mean of tl from the threads' double sums (256 threads, fixed order) and the update of t; both row kernels end here
+__device__ __forceinline__ void curricular_mean_update(double s, double* dred, float* __restrict__ mean,
+                                                       float* __restrict__ t, int rows, int train) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  double s = 0.0;
-  for (int i = tid; i < rows; i += 256) {
-    const long long lab = label[i];
-    const float tl = (lab >= 0 && lab < N) ? clamp1(cos[(size_t)i * ld + lab]) : 0.f;
-    const float ctm = tl * cos_m - sqrtf(1.0f - tl * tl) * sin_m;
-    const bool first = tl > th;
-    rowv[i] = tl;
-    rowv[rows + i] = ctm;
-    rowv[2 * rows + i] = first ? ctm : tl - mm;
-    rowv[3 * rows + i] = first ? 1.f : 0.f;
-    s += (double)tl;
-  }
   s = wave_sum_d(s);
   if (lane == 0) dred[wave] = s;
   __syncthreads();
@@ -325,6 +332,50 @@ __global__ __launch_bounds__(256) void curricular_rows_kernel(const float* __res
     mean[0] = mu;
     if (train) t[0] = __fadd_rn(__fmul_rn(mu, CURR_MOMENTUM), __fmul_rn(1.0f - CURR_MOMENTUM, t[0]));
   }
+}
+
+// one workgroup: the batch mean of tl is added in a fixed order in double (as focal_finalize_kernel), so t is reproducible
+__global__ __launch_bounds__(256) void curricular_rows_kernel(const float* __restrict__ cos,
+                                                              const long long* __restrict__ label,
+                                                              float* __restrict__ rowv, float* __restrict__ mean,
+                                                              float* __restrict__ t, int rows, int N, int ld, float cos_m,
+                                                              float sin_m, float th, float mm, int train) {
+  __shared__ double dred[4];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < rows; i += 256) {
+    const long long lab = label[i];
+    const float tl = (lab >= 0 && lab < N) ? clamp1(cos[(size_t)i * ld + lab]) : 0.f;
+    curricular_row_values(tl, i, rows, rowv, cos_m, sin_m, th, mm);
+    s += (double)tl;
+  }
+  curricular_mean_update(s, dred, mean, t, rows, train);
+}
+
+// the same from given target cosines: the class-sharded head gathers them per shard (shard_target_cos_kernel) and sums
+// them over the ranks, so every rank runs this over the global batch and ends with the same rowv and t
+__global__ __launch_bounds__(256) void curricular_rows_from_kernel(const float* __restrict__ tlv, float* __restrict__ rowv,
+                                                                   float* __restrict__ mean, float* __restrict__ t,
+                                                                   int rows, float cos_m, float sin_m, float th, float mm,
+                                                                   int train) {
+  __shared__ double dred[4];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < rows; i += 256) {
+    const float tl = tlv[i];
+    curricular_row_values(tl, i, rows, rowv, cos_m, sin_m, th, mm);
+    s += (double)tl;
+  }
+  curricular_mean_update(s, dred, mean, t, rows, train);
+}
+
+// tl[i] = clamp(cos[i][label_local[i]]) where this shard owns the label, +0 elsewhere: one rank owns each label, so the sum
+// of the ranks' tl is exact in any order
+__global__ __launch_bounds__(256) void shard_target_cos_kernel(const float* __restrict__ cos,
+                                                               const long long* __restrict__ label,
+                                                               float* __restrict__ tl, int rows, int N, int ld) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= rows) return;
+  const long long lab = label[i];
+  tl[i] = (lab >= 0 && lab < N) ? clamp1(cos[(size_t)i * ld + lab]) : 0.f;
 }
 
 // t <- 0.01 (scale * mean) + 0.99 t: the update of curricular_rows_kernel from a mean summed over the ranks
@@ -708,6 +759,15 @@ extern "C" int fr_curricular_rows(const float* cos, const int64_t* label, float*
   FR_LAUNCH_CHECK();
 }
 
+extern "C" int fr_curricular_rows_from(const float* tl, float* rowv, float* mean, float* t, int rows, float cos_m,
+                                       float sin_m, float th, float mm, int train, void* stream) {
+  if (rows <= 0) FR_UNSUPPORTED("fr_curricular_rows_from: shape (rows > 0)");
+  if (train != 0 && train != 1) FR_UNSUPPORTED("fr_curricular_rows_from: train is 0 or 1");
+  hipLaunchKernelGGL(curricular_rows_from_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, tl, rowv, mean, t, rows,
+                     cos_m, sin_m, th, mm, train);
+  FR_LAUNCH_CHECK();
+}
+
 extern "C" int fr_curricular_ema(float* t, const float* mean, float scale, void* stream) {
   if (!(scale > 0.f)) FR_UNSUPPORTED("fr_curricular_ema: scale > 0 (1 / world size)");
   hipLaunchKernelGGL(curricular_ema_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, t, mean, scale);
@@ -790,6 +850,21 @@ extern "C" int fr_shard_rank_rows(const float* logits, const float* tlogit, int3
   if (rows <= 0 || N <= 0) FR_UNSUPPORTED("fr_shard_rank_rows: empty shard");
   hipLaunchKernelGGL(shard_rank_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, tlogit, rank, N,
                      ld);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_shard_target_cos(const float* cos, const int64_t* label_local, float* tl, int rows, int N, int ld,
+                                   void* stream) {
+  if (rows <= 0 || N <= 0 || ld < N) FR_UNSUPPORTED("fr_shard_target_cos: shape (rows > 0, ld >= N > 0)");
+  hipLaunchKernelGGL(shard_target_cos_kernel, dim3((rows + 255) / 256), dim3(256), 0, (hipStream_t)stream, cos,
+                     (const long long*)label_local, tl, rows, N, ld);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_shard_sum_parts(const float* r_part, int nparts, float* r, int rows, void* stream) {
+  if (rows <= 0 || nparts <= 0) FR_UNSUPPORTED("fr_shard_sum_parts: shape (rows > 0, nparts > 0)");
+  hipLaunchKernelGGL(sum_row_parts_kernel, dim3((rows + 255) / 256), dim3(256), 0, (hipStream_t)stream, r_part, nparts, r,
+                     rows);
   FR_LAUNCH_CHECK();
 }
 

@@ -184,8 +184,11 @@ def margin_ext_forward(x, weight, label, kind, mi, p0, p1):
     return logits, sv._replace(cos=cos), HeadCfg(kind, Np, ld, mi=int(mi), p0=float(p0), p1=float(p1))
 
 
-def margin_ext_backward(saved, cfg, g, need_x, need_w):
-    """(gx, gweight) of ``margin_ext_forward``; gweight has the weight's own layout ([D, N] for Am_softmax)."""
+def margin_ext_backward(saved, cfg, g, need_x, need_w, raw_x_grad=False):
+    """(gx, gweight) of ``margin_ext_forward``; gweight has the weight's own layout ([D, N] for Am_softmax).
+    ``raw_x_grad``: (G, gweight, r_part) instead, G = d loss / d xn before the normalisation backward and r_part
+    SphereFace's [B, parts] radial sums (None for Am_softmax): the class-sharded head sums both over the ranks first, as
+    with ``raw_x_grad`` of ``margin_backward``."""
     sphere = cfg.kind == SPHEREFACE
     B, N = saved.x.shape[0], saved.inv_w.shape[0]
     dev = saved.x.device
@@ -193,15 +196,20 @@ def margin_ext_backward(saved, cfg, g, need_x, need_w):
     r_part = torch.empty(B, int(ops.lib.fr_margin_apply_parts(cfg.Np)), device=dev) if sphere else None
     ops.call("fr_margin_apply_bwd", g.contiguous().float(), saved.cos, saved.label, saved.inv_x, gcos, r_part, B, N, cfg.ld,
              cfg.Np, cfg.kind, cfg.mi, cfg.p0, cfg.p1, ops.current_stream_ptr())()
+    if raw_x_grad:
+        return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, None, col_weight=not sphere) + (r_part,)
     return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, "radial" if sphere else None, col_weight=not sphere,
                             r_part=r_part)
 
 
-def curricular_forward(x, kernel, label, t, s, m, group=None):
+def curricular_forward(x, kernel, label, t, s, m, group=None, target_cos=None, train=True):
     """CurricularFace logits (head/metrics.py:490-510) for fp32 device tensors; ``kernel`` is [D, N], ``t`` the module's
     one-float device buffer, updated in place before it is used (no host read).  ``group``: the batch mean of the target
     cosines is averaged over that process group first (equal batch sizes on every rank), so every rank holds the ``t`` of one
-    head over the global batch.  Returns (logits, saved, cfg) for ``curricular_backward``."""
+    head over the global batch.  ``target_cos``: a hook ``(cos, label, N, ld) -> tl [B]`` called on the raw cosines in place
+    of the gather of the target cosines (the class-sharded head: a row's label may live on another rank; the hook exchanges
+    them); the row values and ``t`` (moved only if ``train``) then come from its result.  Returns (logits, saved, cfg) for
+    ``curricular_backward``."""
     sv, N, Np, ld = _cosine_operands(x, kernel, label, norm_x=True, col_weight=True)
     B = x.shape[0]
     st = ops.current_stream_ptr()
@@ -210,8 +218,12 @@ def curricular_forward(x, kernel, label, t, s, m, group=None):
     th, mm = math.cos(math.pi - m), math.sin(math.pi - m) * m
     rowv = torch.empty(4, B, device=x.device)  # tl, ctm, final, branch flag
     mean = torch.empty(1, device=x.device)
-    ops.call("fr_curricular_rows", cos, sv.label, rowv, mean, t, B, N, ld, cos_m, sin_m, th, mm, int(group is None), st)()
-    if group is not None:
+    if target_cos is not None:
+        tl = target_cos(cos, sv.label, N, ld)
+        ops.call("fr_curricular_rows_from", tl, rowv, mean, t, B, cos_m, sin_m, th, mm, int(bool(train)), st)()
+    else:
+        ops.call("fr_curricular_rows", cos, sv.label, rowv, mean, t, B, N, ld, cos_m, sin_m, th, mm, int(group is None), st)()
+    if group is not None and target_cos is None:
         import torch.distributed as dist
         dist.all_reduce(mean, group=group)  # one float, stays on the device
         ops.call("fr_curricular_ema", t, mean, 1.0 / dist.get_world_size(group), st)()
@@ -222,13 +234,13 @@ def curricular_forward(x, kernel, label, t, s, m, group=None):
     return logits, saved, HeadCfg(CURRICULAR, Np, ld, s=float(s), cos_m=cos_m, sin_m=sin_m)
 
 
-def curricular_backward(saved, cfg, g, need_x, need_w):
-    """(gx, gkernel) of ``curricular_forward``; gkernel is [D, N]."""
+def curricular_backward(saved, cfg, g, need_x, need_w, raw_x_grad=False):
+    """(gx, gkernel) of ``curricular_forward``; gkernel is [D, N].  ``raw_x_grad``: as in ``margin_backward``."""
     B, N = saved.x.shape[0], saved.inv_w.shape[0]
     gcos = torch.empty(B, cfg.Np, device=saved.x.device)
     ops.call("fr_curricular_bwd", g.contiguous().float(), saved.cos, saved.label, saved.rowv, saved.t, gcos, B, N, cfg.ld,
              cfg.Np, cfg.cos_m, cfg.sin_m, cfg.s, ops.current_stream_ptr())()
-    return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, "normalize", col_weight=True)
+    return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, None if raw_x_grad else "normalize", col_weight=True)
 
 
 def _head_fn(name, fwd, bwd, doc):

@@ -19,6 +19,17 @@ Against the replicated head this removes the largest gradient bucket from the al
 weight / momentum / logit memory and FLOPs per GPU, and makes the loss the global-batch focal loss (the replicated
 data-parallel step weights each rank's batch-mean separately).
 
+SphereFace, Am_softmax and CurricularFace run the same choreography with one difference each:
+  Am_softmax      a [D, N] kernel, sharded by COLUMNS (``class_dim`` 1); x is not normalised, so the reduce-scattered G is gx
+  SphereFace      every logit of a row carries ||x||: the radial part of gx is a sum over ALL classes, so its per-row
+                  scalar r is summed per shard (fr_shard_sum_parts) and reduce-scattered as [Bg, 1] next to G; lambda
+                  follows ``iter``, one per forward call, as in head/metrics.py
+  CurricularFace  [D, N] kernel by columns; the target cosine of a row decides which negatives of EVERY shard are hard, so
+                  the shards' target cosines (fr_shard_target_cos: 0 where the label lives elsewhere) are all-reduced
+                  ([Bg] floats, exact: one owner per label) before the row values; ``t`` then moves by the mean over the
+                  global batch, identically on every rank, in a device buffer
+Both extra exchanges are [Bg]-sized.
+
 The device arithmetic sits behind ``HipKernels`` (the only implementation in the package: HIP through the C ABI; no
 CPU fallback).  tests/ substitutes an oracle-backed stand-in to run the collective choreography at world_size 2 on
 ``gloo``.
@@ -31,7 +42,13 @@ from torch.nn import Parameter
 from . import functional as FRF
 from . import ops
 
-KINDS = {"ArcFace": 0, "CosFace": 1}
+KINDS = {"ArcFace": FRF.ARCFACE, "CosFace": FRF.COSFACE, "SphereFace": FRF.SPHEREFACE, "Am_softmax": FRF.AM_SOFTMAX,
+         "CurricularFace": FRF.CURRICULAR}
+# the dimension of the parameter that runs over the classes: ``weight`` [N, D] or ``kernel`` [D, N] (head/metrics.py)
+CLASS_DIM = {"ArcFace": 0, "CosFace": 0, "SphereFace": 0, "Am_softmax": 1, "CurricularFace": 1}
+# (s, m) of each head's own constructor (head/metrics.py); SphereFace has no s
+DEFAULTS = {"ArcFace": (64.0, 0.50), "CosFace": (64.0, 0.50), "SphereFace": (0.0, 4), "Am_softmax": (30.0, 0.35),
+            "CurricularFace": (64.0, 0.5)}
 
 
 def class_range(num_classes, world, rank):
@@ -146,6 +163,42 @@ class HipKernels(object):
         ops.call("fr_normalize_bwd", G, x, inv_x, gx, G.shape[0], G.shape[1], ops.current_stream_ptr())()
         return gx
 
+    # SphereFace / Am_softmax / CurricularFace
+    def ext_logits(self, x_all, w, label_local, kind, mi, p0, p1):
+        return FRF.margin_ext_forward(x_all, w, label_local, kind, mi, p0, p1)
+
+    def target_cos(self, cos, label_local, n, ld):
+        """This shard's target cosines [rows]: exactly 0 where another rank owns the label."""
+        rows = cos.shape[0]
+        tl = torch.empty(rows, device=cos.device)
+        ops.call("fr_shard_target_cos", cos, label_local, tl, rows, n, ld, ops.current_stream_ptr())()
+        return tl
+
+    def curricular_logits(self, x_all, w, label_local, t, s, m, exchange, train):
+        """``exchange``: the shard's target cosines -> those of the global batch (the sum over the ranks); the row values
+        and ``t`` (in place, on the device) follow from them by fr_curricular_rows_from inside ``curricular_forward``."""
+        return FRF.curricular_forward(x_all, w, label_local, t, s, m,
+                                      target_cos=lambda cos, lab, n, ld: exchange(self.target_cos(cos, lab, n, ld)),
+                                      train=train)
+
+    def ext_bwd(self, saved, cfg, g, need_x, need_w):
+        """(G, gradient of the shard, SphereFace's r_part [rows, parts] or None)."""
+        if cfg.kind == FRF.CURRICULAR:
+            return FRF.curricular_backward(saved, cfg, g, need_x, need_w, raw_x_grad=True) + (None,)
+        return FRF.margin_ext_backward(saved, cfg, g, need_x, need_w, raw_x_grad=True)
+
+    def sum_r(self, r_part):
+        """[rows, 1]: the row's parts added in the order fr_normalize_bwd_radial adds them."""
+        rows, nparts = r_part.shape
+        r = torch.empty(rows, 1, device=r_part.device)
+        ops.call("fr_shard_sum_parts", r_part, nparts, r, rows, ops.current_stream_ptr())()
+        return r
+
+    def normalize_bwd_radial(self, G, x, inv_x, r):
+        gx = torch.empty_like(G)
+        ops.call("fr_normalize_bwd_radial", G, x, inv_x, r, 1, gx, G.shape[0], G.shape[1], ops.current_stream_ptr())()
+        return gx
+
 
 class ShardedHeadLossFn(torch.autograd.Function):
     """(loss, prec@1, prec@5) of the global batch from this rank's features, labels and weight shard."""
@@ -159,7 +212,15 @@ class ShardedHeadLossFn(torch.autograd.Function):
         lab_all = C.all_gather(label.contiguous().long())
         rows = x_all.shape[0]
         lab_loc = localize_labels(lab_all, head.lo, head.hi)
-        logits, saved, cfg = K.logits(x_all, w.detach(), lab_loc, head.kind, head.s, head.m, head.easy_margin)
+        if head.kind in (FRF.ARCFACE, FRF.COSFACE):
+            logits, saved, cfg = K.logits(x_all, w.detach(), lab_loc, head.kind, head.s, head.m, head.easy_margin)
+        elif head.kind == FRF.SPHEREFACE:
+            logits, saved, cfg = K.ext_logits(x_all, w.detach(), lab_loc, head.kind, head.m, 1 + head.lamb, 0.0)
+        elif head.kind == FRF.AM_SOFTMAX:
+            logits, saved, cfg = K.ext_logits(x_all, w.detach(), lab_loc, head.kind, 0, head.m, head.s)
+        else:  # one [Bg] all-reduce: every rank gets every row's target cosine, and with them the same t
+            logits, saved, cfg = K.curricular_logits(x_all, w.detach(), lab_loc, head.t, head.s, head.m, C.all_reduce_sum,
+                                                     head.training)
         stats_all = C.all_gather(K.row_stats(logits, lab_loc).view(1, 3, rows))
         lse, ce, tlogit = K.combine(stats_all, C.world, rows)
         rank = C.all_reduce_sum(K.shard_rank(logits, tlogit))
@@ -177,28 +238,47 @@ class ShardedHeadLossFn(torch.autograd.Function):
         K, C = head.kernels, head.comm
         logits, lab_loc, lse, scalars, x_loc = ctx.saved_tensors
         grad = K.dlogits(logits, lab_loc, lse, scalars, gloss)
-        G_all, gw = K.head_bwd(ctx.saved, ctx.cfg, grad, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        r_part = None
+        if head.kind in (FRF.ARCFACE, FRF.COSFACE):
+            G_all, gw = K.head_bwd(ctx.saved, ctx.cfg, grad, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        else:
+            G_all, gw, r_part = K.ext_bwd(ctx.saved, ctx.cfg, grad, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         gx = None
         if G_all is not None:
             G = C.reduce_scatter_rows(G_all)
             lo, hi = ctx.rows_of_rank
-            inv_x = ctx.saved.inv_x[lo:hi].contiguous()
-            gx = K.normalize_bwd(G, x_loc, inv_x)
+            if head.kind == FRF.AM_SOFTMAX:  # x is not normalised: G is the gradient
+                gx = G
+            else:
+                inv_x = ctx.saved.inv_x[lo:hi].contiguous()
+                if head.kind == FRF.SPHEREFACE:  # the radial term sums over all classes: one more [Bg, 1] exchange
+                    r = C.reduce_scatter_rows(K.sum_r(r_part))
+                    gx = K.normalize_bwd_radial(G, x_loc, inv_x, r)
+                else:
+                    gx = K.normalize_bwd(G, x_loc, inv_x)
             if head.grad_scale != 1.0:
                 gx = gx * head.grad_scale
         return gx, gw, None, None
 
 
 class ShardedMarginLoss(nn.Module):
-    """ArcFace / CosFace + FocalLoss + accuracy with the class dimension sharded over the ranks of ``group``.
+    """A margin head + FocalLoss + accuracy with the class dimension sharded over the ranks of ``group``.
 
         crit = ShardedMarginLoss(512, 28000, "ArcFace", s=64.0, m=0.5, gamma=2)      # after init_process_group
         loss, prec1, prec5 = crit(features, labels)                                   # per-rank features / labels
         loss.backward()                        # crit.weight.grad is final (no all-reduce), features get their gradient
 
-    ``weight`` is this rank's [hi - lo, in_features] slice of the head weight: the slice of the tensor a replicated
-    ``ArcFace`` would have drawn from the same RNG state (``full_weight`` given: of that tensor), so the two are
-    interchangeable; ``gather_weight()`` returns the reference's ``weight`` ([N, 512], checkpoint key ``weight``).
+    ``head``: ArcFace, CosFace, SphereFace, Am_softmax or CurricularFace; ``s`` / ``m`` default to that head's own
+    (head/metrics.py; SphereFace takes ``m`` only, ``easy_margin`` is ArcFace's).
+
+    ``weight`` is this rank's slice of the head's parameter in the head's own layout, ``class_dim`` telling which dimension
+    runs over the classes: [hi - lo, in_features] of ``weight`` (ArcFace, CosFace, SphereFace: ``class_dim`` 0) or
+    [in_features, hi - lo] of ``kernel`` (Am_softmax, CurricularFace: ``class_dim`` 1).  It is the slice of the tensor the
+    replicated head would have drawn from the same RNG state (``full_weight`` given: of that tensor), so the two are
+    interchangeable; ``gather_weight()`` returns the reference's parameter (checkpoint key ``weight`` / ``kernel``), and
+    ``gather_full`` / ``slice_full`` do the same for any tensor of the parameter's shape (momentum buffers).
+    CurricularFace keeps the reference's ``t`` as a one-float buffer (identical on every rank), SphereFace its forward
+    counter ``iter``.
 
     The loss is the focal loss of the GLOBAL batch (head/metrics.py + loss/focal.py applied to the concatenated batch,
     what the reference's single head sees under nn.DataParallel).  ``average_over_ranks=True`` (default) scales the
@@ -206,44 +286,76 @@ class ShardedMarginLoss(nn.Module):
     (frhip.parallel.DataParallel) ends up with the gradient of that global loss.
     """
 
-    def __init__(self, in_features, out_features, head="ArcFace", s=64.0, m=0.50, easy_margin=False, gamma=2.0,
+    def __init__(self, in_features, out_features, head="ArcFace", s=None, m=None, easy_margin=False, gamma=2.0,
                  group=None, full_weight=None, average_over_ranks=True, kernels=None):
         super().__init__()
         if head not in KINDS:
-            raise ValueError("ShardedMarginLoss: head must be 'ArcFace' or 'CosFace', got %r" % (head,))
+            raise ValueError("ShardedMarginLoss: head must be one of %s, got %r" % (", ".join(KINDS), head))
         self.in_features, self.out_features = in_features, out_features
-        self.head_name, self.kind = head, KINDS[head]
-        self.s, self.m, self.easy_margin, self.gamma = float(s), float(m), bool(easy_margin), float(gamma)
+        self.head_name, self.kind, self.class_dim = head, KINDS[head], CLASS_DIM[head]
+        s = DEFAULTS[head][0] if s is None else s
+        m = DEFAULTS[head][1] if m is None else m
+        self.s, self.easy_margin, self.gamma = float(s), bool(easy_margin), float(gamma)
+        self.m = int(m) if self.kind == FRF.SPHEREFACE else float(m)
         self.comm = Comm(group)
         self.kernels = kernels if kernels is not None else HipKernels()
         self.lo, self.hi = class_range(out_features, self.comm.world, self.comm.rank)
         self.grad_scale = float(self.comm.world) if average_over_ranks else 1.0
-        if full_weight is None:
-            full_weight = torch.empty(out_features, in_features)
-            nn.init.xavier_uniform_(full_weight)  # head/metrics.py:87-88: same draw as the replicated head
-        if tuple(full_weight.shape) != (out_features, in_features):
-            raise ValueError("ShardedMarginLoss: full_weight must be [%d, %d]" % (out_features, in_features))
-        self.weight = Parameter(full_weight.detach()[self.lo:self.hi].clone().float())
+        self.full_shape = (out_features, in_features) if self.class_dim == 0 else (in_features, out_features)
+        if full_weight is None:  # the draw of the replicated head (head/metrics.py), from the same RNG state
+            full_weight = torch.empty(self.full_shape)
+            if self.kind == FRF.AM_SOFTMAX:
+                full_weight.uniform_(-1, 1).renorm_(2, 1, 1e-5).mul_(1e5)
+            elif self.kind == FRF.CURRICULAR:
+                nn.init.normal_(full_weight, std=0.01)
+            else:
+                nn.init.xavier_uniform_(full_weight)
+        if tuple(full_weight.shape) != self.full_shape:
+            raise ValueError("ShardedMarginLoss: full_weight must be [%d, %d]" % self.full_shape)
+        self.weight = Parameter(self.slice_full(full_weight.detach()).float())
+        if self.kind == FRF.CURRICULAR:
+            self.register_buffer("t", torch.zeros(1))
+        if self.kind == FRF.SPHEREFACE:  # the lambda schedule of head/metrics.py SphereFace
+            self.base, self.lambda_gamma, self.power, self.LambdaMin, self.iter = 1000.0, 0.12, 1, 5.0, 0
 
     @classmethod
     def from_head(cls, head, gamma=2.0, group=None, **kw):
-        """Shard an existing ``head.metrics.ArcFace`` / ``CosFace`` (same weights on every rank)."""
+        """Shard an existing head of head/metrics.py (same parameter on every rank); CurricularFace's ``t`` and
+        SphereFace's ``iter`` come along."""
         name = head.__class__.__name__
-        return cls(head.in_features, head.out_features, name, s=head.s, m=head.m,
+        full = head.kernel if hasattr(head, "kernel") else head.weight
+        dims = (full.shape[0], full.shape[1]) if CLASS_DIM.get(name, 0) == 1 else (full.shape[1], full.shape[0])
+        crit = cls(dims[0], dims[1], name, s=getattr(head, "s", None), m=head.m,
                    easy_margin=getattr(head, "easy_margin", False), gamma=gamma, group=group,
-                   full_weight=head.weight.detach().cpu(), **kw)
+                   full_weight=full.detach().cpu(), **kw)
+        if hasattr(crit, "t"):
+            crit.t.copy_(head.t.detach().cpu())
+        if hasattr(crit, "iter"):
+            crit.iter = head.iter
+        return crit
 
     def shard_sizes(self):
         return [hi - lo for lo, hi in (class_range(self.out_features, self.comm.world, r)
                                        for r in range(self.comm.world))]
 
+    def slice_full(self, full):
+        """This rank's class range of a tensor of the full parameter's shape (a copy)."""
+        return (full[self.lo:self.hi] if self.class_dim == 0 else full[:, self.lo:self.hi]).clone()
+
+    def gather_full(self, part):
+        """Inverse of ``slice_full`` on every rank (collective).  Column shards travel transposed: the ragged gather stacks
+        row blocks."""
+        if self.class_dim == 0:
+            return self.comm.gather_ragged_rows(part, self.shard_sizes())
+        return self.comm.gather_ragged_rows(part.t().contiguous(), self.shard_sizes()).t().contiguous()
+
     def gather_weight(self):
-        """The full [out_features, in_features] weight on every rank (checkpoints keep the reference's layout)."""
-        return self.comm.gather_ragged_rows(self.weight.detach(), self.shard_sizes())
+        """The full parameter on every rank (checkpoints keep the reference's layout)."""
+        return self.gather_full(self.weight.detach())
 
     def load_full_weight(self, full_weight):
         with torch.no_grad():
-            self.weight.copy_(full_weight[self.lo:self.hi])
+            self.weight.copy_(self.slice_full(full_weight))
 
     def forward(self, input, label):
         if self.weight.device != input.device:
@@ -252,6 +364,9 @@ class ShardedMarginLoss(nn.Module):
         if FRF.CHECK_LABELS and (label.min() < 0 or label.max() >= self.out_features):  # metrics.py:134 (scatter_)
             raise RuntimeError("index %d is out of bounds for dimension 1 with size %d"
                                % (int(label.max()), self.out_features))
+        if self.kind == FRF.SPHEREFACE:  # head/metrics.py:238-239: every forward call counts
+            self.iter += 1
+            self.lamb = max(self.LambdaMin, self.base * (1 + self.lambda_gamma * self.iter) ** (-1 * self.power))
         return ShardedHeadLossFn.apply(input, self.weight, label, self)
 
     def __repr__(self):

@@ -86,15 +86,15 @@ def _head_state_index(optimizer, crit):
 
 def optimizer_state_for_checkpoint(optimizer, crit):
     """``optimizer.state_dict()`` in the reference's layout.  With a class-sharded head the momentum buffer of the head
-    weight is gathered to [classes, 512] (collective: every rank calls this), so optimizer checkpoints are
-    interchangeable between replicated and sharded runs and between world sizes."""
+    parameter is gathered to the head's full shape, [classes, 512] or [512, classes] (collective: every rank calls this),
+    so optimizer checkpoints are interchangeable between replicated and sharded runs and between world sizes."""
     sd = optimizer.state_dict()
     if crit is None:
         return sd
     idx = _head_state_index(optimizer, crit)
     st = sd["state"].get(idx)
     if st is not None:
-        full = {k: crit.comm.gather_ragged_rows(v, crit.shard_sizes()) for k, v in st.items()
+        full = {k: crit.gather_full(v) for k, v in st.items()
                 if torch.is_tensor(v) and v.shape == crit.weight.shape}  # momentum_buffer / exp_avg / exp_avg_sq
         sd = dict(sd, state=dict(sd["state"]))
         sd["state"][idx] = dict(st, **full)
@@ -113,8 +113,8 @@ def load_optimizer_checkpoint(optimizer, crit, sd):
         idx = _head_state_index(optimizer, crit)
         st = sd["state"].get(idx)
         if st is not None:
-            part = {k: v[crit.lo:crit.hi].clone() for k, v in st.items()
-                    if torch.is_tensor(v) and v.dim() == 2 and v.shape[0] == crit.out_features}
+            part = {k: crit.slice_full(v) for k, v in st.items()
+                    if torch.is_tensor(v) and tuple(v.shape) == crit.full_shape}
             sd = dict(sd, state=dict(sd["state"]))
             sd["state"][idx] = dict(st, **part)
     optimizer.load_state_dict(sd)
@@ -188,9 +188,9 @@ def main():
              "SphereFace": SphereFace(emb, num_class, None), "Am_softmax": Am_softmax(emb, num_class, None),
              "CurricularFace": CurricularFace(emb, num_class, s=s)}
     head = heads[cfg["HEAD_NAME"]]
-    if world > 1 and hasattr(head, "process_group"):
-        # CurricularFace: t follows the mean target cosine of the GLOBAL batch, as under the reference's nn.DataParallel
-        # (equal per-rank batch sizes: DROP_LAST)
+    if world > 1 and hasattr(head, "process_group") and not cfg.get("SHARDED_HEAD", False):
+        # replicated CurricularFace: t follows the mean target cosine of the GLOBAL batch, as under the reference's
+        # nn.DataParallel (equal per-rank batch sizes: DROP_LAST).  The class-sharded head sees the global batch itself.
         head.process_group = dist.group.WORLD
     bn_params, other_params = separate_irse_bn_paras(backbone)
     _, head_params = separate_irse_bn_paras(head)
@@ -218,11 +218,12 @@ def main():
     if cfg.get("SHARDED_HEAD", False):
         # class-sharded head + focal loss over the ranks (frhip/sharded_head.py): the N x 512 weight, its momentum and the
         # [B, N] logits are split by class range; the loss is the focal loss of the GLOBAL batch, as under the
-        # reference's nn.DataParallel.  Checkpoints keep the reference's layout (gathered ``weight``).
-        if cfg["HEAD_NAME"] not in ("ArcFace", "CosFace") or loss_fn is None:
-            raise NotImplementedError("SHARDED_HEAD needs HEAD_NAME ArcFace/CosFace and LOSS_NAME 'Focal'")
+        # reference's nn.DataParallel.  Checkpoints keep the reference's layout: the gathered ``weight`` / ``kernel``,
+        # CurricularFace's ``t`` and SphereFace's forward counter go back into ``head`` before it is saved.
+        if loss_fn is None:
+            raise NotImplementedError("SHARDED_HEAD needs LOSS_NAME 'Focal'")
         from frhip.sharded_head import ShardedMarginLoss
-        crit = ShardedMarginLoss.from_head(head, gamma=loss_fn.gamma).to(device)
+        crit = ShardedMarginLoss.from_head(head, gamma=loss_fn.gamma).to(device)  # takes the resumed weight and t along
         optimizer = make_optimizer([crit.weight])
     # exposes .module like nn.DataParallel; all-reduce only when world > 1 (a weight shard is complete on its owner)
     BACKBONE = DataParallel(backbone, None if crit is not None else head)
@@ -250,6 +251,8 @@ def main():
                   "the stage is applied again".format(state.get("lr_stage_applied")))
         if "head_iter" in state and hasattr(head, "iter"):  # SphereFace's lambda schedule (older State_ files: no key)
             head.iter = int(state["head_iter"])
+            if crit is not None:
+                crit.iter = head.iter
         if "torch_rng" in state:
             torch.set_rng_state(state["torch_rng"])
             n = state["numpy_rng"]
@@ -265,7 +268,7 @@ def main():
     FRF.CHECK_LABELS = False  # labels come from the dataset's own class index
     for epoch in range(start_epoch, cfg["NUM_EPOCH"]):
         epoch_first_batch = batch
-        epoch_first_iter = getattr(head, "iter", None)
+        epoch_first_iter = getattr(crit if crit is not None else head, "iter", None)
         if epoch in cfg["STAGES"] and epoch != lr_stage_done:
             schedule_lr(optimizer)
         backbone.train()
@@ -350,7 +353,13 @@ def main():
             BACKBONE.module.train()
         if crit is not None:
             with torch.no_grad():
-                head.weight.copy_(crit.gather_weight())  # collective: every rank takes part, rank 0 writes the file
+                # collective: every rank takes part, rank 0 writes the file
+                (head.kernel if hasattr(head, "kernel") else head.weight).copy_(crit.gather_weight())
+                if cfg["HEAD_NAME"] not in ("ArcFace", "CosFace"):  # heads with state besides the parameter
+                    if hasattr(crit, "t"):  # CurricularFace
+                        head.t.copy_(crit.t)
+                    if hasattr(crit, "iter"):  # SphereFace's forward counter
+                        head.iter = crit.iter
         opt_state = optimizer_state_for_checkpoint(optimizer, crit)  # collective with a sharded head
         if rank == 0:
             tag = "Epoch_{}_Batch_{}_Time_{}_checkpoint.pth".format(epoch + 1, batch, get_time())
