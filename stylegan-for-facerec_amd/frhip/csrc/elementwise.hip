@@ -1668,6 +1668,7 @@ extern "C" int fr_bn_bwd_apply(const FrBnBwdArgs* args, int dtype, void* stream)
   if (dtype == FR_BF16 && lean_ok(args->C) && !args->slope && scatter_ok && args->rows < (1ll << 31)) {
     const dim3 grid(args->nblocks), blk(NT);
     if (args->se) {
+      if (args->nx) FR_UNSUPPORTED("fr_bn_bwd_apply: nx (the sums of the BatchNorm in front) is not served behind a gate (se)");
       if (args->add_kind == 1) hipLaunchKernelGGL((bn_bwd_apply_lean_kernel<1, true>), grid, blk, 0, st, *args);
       else hipLaunchKernelGGL((bn_bwd_apply_lean_kernel<0, true>), grid, blk, 0, st, *args);
     } else if (args->nx) {

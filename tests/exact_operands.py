@@ -1,4 +1,5 @@
-"""Integer-valued operands for the bf16 convolution kernels, float64 references and bit-exact comparators.
+"""Integer-valued operands for the bf16 convolution kernels and the channel-wise passes, float64 references and bit-exact
+comparators.
 
 Why: on Gaussian data a bf16 kernel can only be compared to a tolerance (tests/test_gpu_kernels.py), and an addressing
 or coverage defect smaller than one rounding passes.  Here every operand is a small integer (or a small integer times a
@@ -6,7 +7,13 @@ power of two) and every true result fits the format it is stored in: bf16 MFMA p
 one-fmaf prologues, the fp32 epilogue sums, the slab sums and the bf16 store are then exact in ANY summation order, and a
 kernel must equal an integer reference bit for bit -- at every pixel, part row and weight-gradient element.
 
-A plain helper module (like shard_ref.py), used by test_exact_operands_host.py (no GPU) and test_gpu_exact_conv.py.
+The channel-wise passes of frhip/csrc/elementwise.hip (BatchNorm apply / backward, channel and image statistics, the
+squeeze-excite squeezes and backward) are chains of fmaf and sums of the same kind: on small dyadic operands every
+intermediate is an fp32 number and every sum is exact in any order, so they are pinned the same way (second half of the
+references below; the recipes assert their own preconditions before anything is compared).
+
+A plain helper module (like shard_ref.py), used by test_exact_operands_host.py (no GPU), test_gpu_exact_conv.py and
+test_gpu_exact_elementwise.py.
 Layout: activations NHWC ``[B, H, W, C]``, weights packed ``[O][kh*kw][I]`` -- what the C ABI takes.
 """
 import math
@@ -172,14 +179,17 @@ def _quantum(t, quantum):
     return m, bool((m == m.round()).all())
 
 
-def assert_exact_range(stored=(), terms=(), images_per_row=1, quantum=1.0, term_quantum=None, wgrad_abs=None, what=""):
+def assert_exact_range(stored=(), terms=(), images_per_row=1, quantum=1.0, term_quantum=None, wgrad_abs=None, fp32=(), what=""):
     """The preconditions of exactness, asserted on the REFERENCE before anything is compared.
       stored   : tensors the kernel stores as bf16 -- multiples of `quantum` (a power of two), every element with at most 8
                  significant bits (for plain integers: |v| <= 256), i.e. unchanged by a round trip through bf16
       terms    : per sum kind the elementwise summands [B, H, W, C] -- multiples of `term_quantum` (default quantum^2) whose
                  per-image, per-channel sum of magnitudes, times the images one part row can hold, is <= 2^23 quanta (half
                  the fp32 integer range)
-      wgrad_abs: an upper bound of sum |g * x| over every weight-gradient element, <= 2^23 quanta."""
+      wgrad_abs: an upper bound of sum |g * x| over every weight-gradient element, <= 2^23 quanta.
+      fp32     : (value, magnitude, q) triples of results a kernel leaves as fp32 behind a sum it may take in any order (the
+                 squeeze-excite backward): `value` is a multiple of the power of two q and an fp32 number, `magnitude` -- the
+                 sum of the magnitudes of its summands, same shape -- is <= 2^23 q, so every partial sum is an fp32 number."""
     assert math.log2(quantum) == round(math.log2(quantum)), "quantum must be a power of two"
     for i, t in enumerate(stored):
         m, whole = _quantum(t, quantum)
@@ -198,6 +208,13 @@ def assert_exact_range(stored=(), terms=(), images_per_row=1, quantum=1.0, term_
         q2 = quantum * quantum if term_quantum is None else term_quantum
         assert float(wgrad_abs) / q2 <= FP32_HALF_RANGE, "%s: weight-gradient sums reach %.3g" % (
             what, float(wgrad_abs))
+    for i, (value, magnitude, q) in enumerate(fp32):
+        assert math.log2(q) == round(math.log2(q)), "quantum must be a power of two"
+        _, whole = _quantum(value, q)
+        assert whole, "%s: fp32 result %d is not a multiple of %g" % (what, i, q)
+        assert torch.equal(value.double().float().double(), value.double()), "%s: fp32 result %d is not an fp32 number" % (what, i)
+        worst = float(magnitude.double().abs().max()) / q
+        assert worst <= FP32_HALF_RANGE, "%s: the sum behind fp32 result %d reaches %.3g quanta (> 2^23)" % (what, i, worst)
 
 
 def wgrad_abs_bound(g, xin):
@@ -265,3 +282,265 @@ def assert_sums_equal(part, ref, what=""):
     raise AssertionError("%s: %d of %d per-channel sums differ; first: sum %d, channel %d: got %r, want %r (difference %r); "
                          "channels %s" % (what, idx.shape[0], got.numel(), k, c, float(got[k, c]), float(ref[k, c]),
                                           float(got[k, c] - ref[k, c]), sorted(set(idx[:, 1].tolist()))[:16]))
+
+
+# ------------------------------------------------------------------------------------------------------------ channel-wise passes
+# References of the passes of frhip/csrc/elementwise.hip, written from the formulas of include/frhip.h in float64, and the
+# operand recipes of test_gpu_exact_elementwise.py.  Part rows of these kernels are not tied to images (a workgroup strides
+# over all rows), so every range condition takes the sum over ALL rows (all_rows).
+SCALES = [1.0, 2.0, -1.0, 0.5]       # BatchNorm scale / rscale
+SHIFTS = [-1.0, 0.0, 1.0]
+GATES = [0.5, 1.0, 2.0]              # squeeze-excite gates of the BatchNorm passes
+SLOPES = [0.25, 0.5]
+INV_COUNT = 2.0 ** -10               # fr_bn_bwd_apply takes 1 / count as an argument: a power of two, whatever the row count
+
+# (B, H, W, C, nblocks): the smallest shapes that reach each edge of the [row-thread][channel-chunk] kernels (256 threads; the
+# lean bf16 kernels: 4 channels per thread, 4 forward / 3 backward rows in flight)
+EW_SHAPES = [(3, 5, 7, 64, 7),       # 105 rows: below one block trip, idle blocks, non-square
+             (5, 7, 7, 128, 2),      # 49-row images straddle the rows in flight; several grid-stride trips, ragged last trip
+             (2, 14, 14, 256, 3),    # 392 rows
+             (37, 2, 6, 512, 5),     # many 12-row images
+             (1, 2, 2, 64, 1),       # fewer rows than row-threads
+             (2, 4, 4, 1024, 4),     # one row-thread per trip
+             (2, 3, 3, 2048, 2)]     # bf16 only, not lean-eligible: the general kernel
+SCATTER_SHAPES = [(3, 6, 10, 64), (2, 4, 2, 128), (5, 14, 14, 256)]   # add_kind 2, stride 2 (lean bf16 / general fp32)
+SCATTER_S3 = (2, 9, 6, 64)                                            # add_kind 2, stride 3: the general kernel
+STATS_LONG = (2, 56, 56, 64, 5)                                       # HW = 3136: many trips per thread
+SE_HW = [16, 49, 64, 196]
+SE_SQUEEZE = [(3, 4, 64), (5, 7, 128), (2, 8, 256), (3, 14, 256), (2, 4, 2048), (3, 7, 512)]   # (B, H, C) of the squeezes
+SE_CHAIN = [(5, 4, 128), (3, 8, 256), (130, 4, 64)]   # (B, H, C), power-of-two HW: the full squeeze-excite backward
+SE_REAL_HW = [(5, 7, 128), (3, 14, 256)]              # HW 49 and 196: the per-image sums only (w1 = 0)
+
+
+def small_ints(seed, tag, shape, p=0.5):
+    """Integers -3 .. 3: a ternary tensor plus twice a sparser one."""
+    return ternary(seed, tag + ".1", shape, p) + 2.0 * ternary(seed, tag + ".2", shape, p / 2)
+
+
+def nonzero_ints(seed, tag, shape):
+    """Integers from {-2, -1, 1, 2}: never zero, so a missed or an extra hit of a scattered tensor shows."""
+    return pick(seed, tag, int(math.prod(shape)), [-2.0, -1.0, 1.0, 2.0]).view(shape)
+
+
+def per_image(seed, tag, B, C, values, weights=None):
+    return pick(seed, tag, B * C, values, weights).view(B, C)
+
+
+def all_rows(t):
+    """[B, H, W, C] -> [1, 1, B*H*W, C]: the view assert_exact_range sums over when part rows are not tied to images."""
+    return t.reshape(1, 1, -1, t.shape[-1])
+
+
+def _img(v, like):
+    """[B][C] per-image values against [B, H, W, C]."""
+    return v.to(like.device, torch.float64).view(v.shape[0], 1, 1, v.shape[1])
+
+
+def bn_apply(x, scale, shift, se=None, slope=None, res=None, rscale=None, rshift=None, res_stride=1):
+    """out = [prelu](x*scale + shift [* se[b][c]]) [+ res*rscale + rshift]; res_stride > 1: the identity shortcut reads
+    res[b, h*stride, w*stride] of a [B, H*stride, W*stride, C] tensor.  Returns (out, [out, out^2])."""
+    v = x.double() * _ch(scale, x) + _ch(shift, x)
+    if se is not None:
+        v = v * _img(se, x)
+    if slope is not None:
+        v = torch.where(v > 0, v, v * _ch(slope, x))
+    if res is not None:
+        r = res.double()[:, ::res_stride, ::res_stride]
+        if rscale is not None:
+            r = r * _ch(rscale, x) + _ch(rshift, x)
+        v = v + r
+    return v, [v, v * v]
+
+
+def bn_bwd_gprime(g, x, scale=None, shift=None, slope=None, se=None, gse=None):
+    """(g', g*u*[u <= 0]): g' = g | g * prelu'(u), u = x*scale + shift | g * se[b][c] + gse[b][c]."""
+    gp = g.double()
+    st = torch.zeros_like(gp)
+    if slope is not None:
+        u = x.double() * _ch(scale, x) + _ch(shift, x)
+        st = torch.where(u > 0, st, gp * u)
+        gp = torch.where(u > 0, gp, gp * _ch(slope, x))
+    if se is not None:
+        gp = gp * _img(se, x)
+        if gse is not None:
+            gp = gp + _img(gse, x)
+    return gp, st
+
+
+def xhat(x, mean, invstd):
+    return (x.double() - _ch(mean, x)) * _ch(invstd, x)
+
+
+def scatter(add, H, W, stride):
+    """MaxPool2d(1, stride) backwards: add[b, h/stride, w/stride] lands on the pixels with h % stride == w % stride == 0."""
+    B, _, _, C = add.shape
+    full = torch.zeros(B, H, W, C, dtype=torch.float64, device=add.device)
+    full[:, ::stride, ::stride] = add.double()
+    return full
+
+
+def bn_bwd_apply(gp, xh, gamma, invstd, s0, s1, inv_count, add=None):
+    """gx = gamma*invstd*(g' - s0*inv_count - xhat*s1*inv_count) [+ add], add of gx's geometry."""
+    gx = _ch(gamma, gp) * _ch(invstd, gp) * (gp - _ch(s0, gp) * inv_count - xh * (_ch(s1, gp) * inv_count))
+    return gx if add is None else gx + add.double()
+
+
+def _bn_images(seed, tag, B, hwc, p):
+    return batch(ternary(seed, tag, (BASE_IMAGES,) + tuple(hwc), p), B)
+
+
+def bn_apply_case(B, H, W, C, res_kind=0, gate=False, slope=False, res_stride=1, seed=211):
+    """Operands and reference of fr_bn_apply: x and res small integers (behind a slope: -4, 0, 1, as activations(.., "prelu")),
+    scale / rscale from {1, 2, -1, 1/2}, shifts from {-1, 0, 1}, gates from {1/2, 1, 2}, slopes from {1/4, 1/2}.  Everything is a
+    multiple of 1/16.  Returns (operands, out, [out, out^2])."""
+    hwc = (H, W, C)
+    x = batch(activations(seed, "a.xp", hwc, 0.6, "prelu") if slope else small_ints(seed, "a.x", (BASE_IMAGES,) + hwc), B)
+    o = dict(x=x, scale=pick(seed, "a.scale", C, SCALES), shift=pick(seed, "a.shift", C, SHIFTS))
+    if gate:
+        o["se"] = per_image(seed, "a.se", B, C, GATES)
+    if slope:
+        o["slope"] = pick(seed, "a.slope", C, SLOPES)
+    if res_kind:
+        o["res"] = batch(small_ints(seed, "a.res", (BASE_IMAGES, H * res_stride, W * res_stride, C)), B)
+    if res_kind == 2:
+        o.update(rscale=pick(seed, "a.rscale", C, SCALES), rshift=pick(seed, "a.rshift", C, SHIFTS))
+    out, terms = bn_apply(res_stride=res_stride, **o)
+    what = "bn_apply %s res%d gate%d slope%d" % ((B, H, W, C), res_kind, gate, slope)
+    assert_exact_range(stored=[out], terms=[all_rows(t) for t in terms], quantum=1.0 / 16, what=what)
+    assert float((out != 0).double().mean()) > 0.4, what + ": mostly zeros"
+    return o, out, terms
+
+
+def bn_bwd_case(B, H, W, C, mode="plain", seed=223):
+    """Operands and reference sums of fr_bn_bwd_reduce.  mode: plain | slope | gate | gate_gse.  g and x ternary, mean from
+    {-1, 0, 1}, invstd from {1/2, 1, 2}, gse from the multiples of 1/4 up to 1/2.  Returns (operands, g', xhat, the three
+    elementwise summands)."""
+    hwc = (H, W, C)
+    o = dict(g=_bn_images(seed, "b.g", B, hwc, 0.5), x=_bn_images(seed, "b.x", B, hwc, 0.6),
+             mean=pick(seed, "b.mean", C, SHIFTS), invstd=pick(seed, "b.invstd", C, [0.5, 1.0, 2.0]))
+    if mode == "slope":
+        o.update(scale=pick(seed, "b.scale", C, SCALES), shift=pick(seed, "b.shift", C, SHIFTS), slope=pick(seed, "b.slope", C, SLOPES))
+    if mode in ("gate", "gate_gse"):
+        o["se"] = per_image(seed, "b.se", B, C, GATES)
+    if mode == "gate_gse":
+        o["gse"] = per_image(seed, "b.gse", B, C, [-0.5, -0.25, 0.0, 0.25, 0.5])
+    gp, st = bn_bwd_gprime(o["g"], o["x"], o.get("scale"), o.get("shift"), o.get("slope"), o.get("se"), o.get("gse"))
+    xh = xhat(o["x"], o["mean"], o["invstd"])
+    terms = [gp, gp * xh, st]
+    assert_exact_range(terms=[all_rows(t) for t in terms], term_quantum=1.0 / 8, what="bn_bwd %s %s" % ((B, H, W, C), mode))
+    return o, gp, xh, terms
+
+
+def bn_bwd_apply_case(B, H, W, C, mode="plain", add_kind=0, add_stride=2, nxt=False, seed=223):
+    """Operands and reference of fr_bn_bwd_apply on the data of bn_bwd_case: gamma from {1, 2, -1}, inv_count = 2^-10, s0 and s1
+    multiples of 2^9 (both quotients multiples of 1/2 up to 1), add from {-2, -1, 1, 2} on EVERY pixel.  gx is a multiple of 1/8
+    below 32 in magnitude: at most 8 significant bits.  nxt: nx ternary, nmean / ninvstd as mean / invstd.
+    Returns (operands, gx, [gx, gx * xhat_n] or [])."""
+    o, gp, xh, _ = bn_bwd_case(B, H, W, C, mode, seed)
+    halves = [-1.0, -0.5, 0.0, 0.5, 1.0]
+    o.update(gamma=pick(seed, "c.gamma", C, [1.0, 2.0, -1.0]), s0=pick(seed, "c.s0", C, halves) / INV_COUNT,
+             s1=pick(seed, "c.s1", C, halves) / INV_COUNT, inv_count=INV_COUNT)
+    add = None
+    if add_kind == 1:
+        o["add"] = add = batch(nonzero_ints(seed, "c.add", (BASE_IMAGES, H, W, C)), B)
+    elif add_kind == 2:
+        assert H % add_stride == 0 and W % add_stride == 0
+        o["add"] = batch(nonzero_ints(seed, "c.add", (BASE_IMAGES, H // add_stride, W // add_stride, C)), B)
+        add = scatter(o["add"], H, W, add_stride)
+    gx = bn_bwd_apply(gp, xh, o["gamma"], o["invstd"], o["s0"], o["s1"], INV_COUNT, add)
+    what = "bn_bwd_apply %s %s add%d" % ((B, H, W, C), mode, add_kind)
+    terms = []
+    if nxt:
+        o.update(nx=_bn_images(seed, "c.nx", B, (H, W, C), 0.6), nmean=pick(seed, "c.nmean", C, SHIFTS),
+                 ninvstd=pick(seed, "c.ninvstd", C, [0.5, 1.0, 2.0]))
+        terms = [gx, gx * xhat(o["nx"], o["nmean"], o["ninvstd"])]
+    assert_exact_range(stored=[gx], terms=[all_rows(t) for t in terms], quantum=1.0 / 8, term_quantum=1.0 / 16, what=what)
+    assert float((gx != 0).double().mean()) > 0.4, what + ": mostly zeros"
+    return o, gx, terms
+
+
+def image_sums(terms):
+    """[B][k][C] float64 per-image sums."""
+    return torch.stack([t.sum((1, 2)) for t in terms], 1)
+
+
+def stats_case(B, H, W, C, seed=229):
+    """fr_channel_stats / fr_image_moments: x small integers; the summands (x, x^2)."""
+    x = batch(small_ints(seed, "s.x", (BASE_IMAGES, H, W, C)), B)
+    terms = [x.double(), x.double() * x.double()]
+    assert_exact_range(stored=[x], terms=[all_rows(t) for t in terms], what="stats %s" % ((B, H, W, C),))
+    return x, terms
+
+
+def se_squeeze_case(B, H, C, seed=233):
+    """fr_se_gscale (gs[b][c] = sum_hw g*(x*scale + shift), any HW) and fr_se_pool (pooled[b][c] = scale*mean_hw(x) + shift: the
+    kernel DIVIDES the sum by HW, so it is exact at power-of-two HW only -- H = 4, 8; elsewhere `pooled` is None)."""
+    hwc = (H, H, C)
+    g, x = _bn_images(seed, "q.g", B, hwc, 0.5), batch(small_ints(seed, "q.x", (BASE_IMAGES,) + hwc), B)
+    scale, shift = pick(seed, "q.scale", C, SCALES), pick(seed, "q.shift", C, SHIFTS)
+    t = g.double() * (x.double() * _ch(scale, x) + _ch(shift, x))
+    gs = t.sum((1, 2))
+    what = "se squeeze %s" % ((B, H, C),)
+    assert_exact_range(stored=[g, x], fp32=[(gs, t.abs().sum((1, 2)), 0.5)], what=what)
+    pooled = None
+    HW = H * H
+    if HW & (HW - 1) == 0:
+        sx = x.double().sum((1, 2))
+        pooled = sx / HW * scale.double() + shift.double()
+        assert_exact_range(fp32=[(sx, x.double().abs().sum((1, 2)), 1.0), (pooled, pooled, 0.5 / HW)], what=what + " pool")
+    return dict(g=g, x=x, scale=scale, shift=shift), gs, pooled
+
+
+def se_mlp_bwd(gs, s, hidden, w1, w2, HW):
+    """Backward of s = sigmoid(W2 relu(W1 pooled)) from gs = dL/ds: gz = gs*s*(1-s) at the fc2 output, gh = relu'(hidden) *
+    (W2^T gz) at the fc1 output, gpooled = (W1^T gh) / HW.  w1 [R][C], w2 [C][R]."""
+    gz = gs.double() * s.double() * (1.0 - s.double())
+    gh = torch.where(hidden.double() > 0, gz @ w2.double(), torch.zeros((), dtype=torch.float64))
+    return gz, gh, (gh @ w1.double()) / HW
+
+
+def se_mlp_wgrad(gz, gh, hidden, pooled):
+    """dW1[r][c] = sum_b gh[b][r] * pooled[b][c], dW2[c][r] = sum_b gz[b][c] * hidden[b][r]."""
+    return gh.double().t() @ pooled.double(), gz.double().t() @ hidden.double()
+
+
+def se_bwd_case(B, H, C, zero_w1=False, seed=239):
+    """The squeeze-excite backward (fr_se_gscale_mlp_bwd[_sums], fr_se_mlp_wgrad): g and x ternary (g sparse), gates s from
+    {1/4, 1/2, 3/4} (s*(1-s) is 3/16 or 1/4), w1 / w2 ternary, hidden from {0, 1/2, 1, 2} with half of it exactly 0 (the ReLU mask
+    matters), pooled a small multiple of 1/4.  gpooled multiplies by 1 / HW: the full chain is exact at power-of-two HW only;
+    zero_w1 (gse = 0) serves the per-image sums at the real HW values 49 and 196.
+    Returns (operands, reference dict): gs, gz, gh, gpooled, dw1, dw2, parts [B][4][C] (per image: gs, sum g, sum g*xhat, sum
+    xhat) and bn [B][2][C] (sum g', sum g'*xhat with g' = g*s + gpooled)."""
+    HW, R = H * H, max(C // 16, 1)
+    assert zero_w1 or HW & (HW - 1) == 0, "gpooled is exact at power-of-two HW only"
+    hwc = (H, H, C)
+    o = dict(g=_bn_images(seed, "e.g", B, hwc, 0.25), x=_bn_images(seed, "e.x", B, hwc, 0.5),
+             scale=pick(seed, "e.scale", C, SCALES), shift=pick(seed, "e.shift", C, [0.0, -1.0, 1.0], [0.875, 0.0625, 0.0625]),
+             mean=pick(seed, "e.mean", C, SHIFTS), invstd=pick(seed, "e.invstd", C, [0.5, 1.0, 2.0]),
+             s=per_image(seed, "e.s", B, C, [0.25, 0.5, 0.75]),
+             hidden=per_image(seed, "e.hidden", B, R, [0.0, 0.5, 1.0, 2.0], [0.5, 0.2, 0.2, 0.1]),
+             pooled=per_image(seed, "e.pooled", B, C, [-0.5, -0.25, 0.0, 0.25, 0.5, 1.0]),
+             w1=torch.zeros(R, C) if zero_w1 else ternary(seed, "e.w1", (R, C), 0.5), w2=ternary(seed, "e.w2", (C, R), 0.25))
+    g, x = o["g"].double(), o["x"].double()
+    t = g * (x * o["scale"].double() + o["shift"].double())
+    gs = t.sum((1, 2))
+    gz, gh, gpooled = se_mlp_bwd(gs, o["s"], o["hidden"], o["w1"], o["w2"], HW)
+    dw1, dw2 = se_mlp_wgrad(gz, gh, o["hidden"], o["pooled"])
+    xh = xhat(o["x"], o["mean"], o["invstd"])
+    parts = image_sums([t, g, g * xh, xh])
+    gp = g * _img(o["s"], g) + _img(gpooled, g)
+    bn = image_sums([gp, gp * xh])
+    what = "se backward %s" % ((B, H, C),)
+    q = 1.0 / 32                                     # gs is a multiple of 1/2, s*(1-s) of 1/16
+    qp = q / (1 << (HW - 1).bit_length())            # gpooled (exact: zero, or HW a power of two)
+    sd, G, GX, XH = o["s"].double(), parts[:, 1], parts[:, 2], parts[:, 3]
+    assert_exact_range(stored=[o["g"], o["x"]], what=what, fp32=[
+        (gs, t.abs().sum((1, 2)), 0.5), (G, g.abs().sum((1, 2)), 1.0), (GX, (g * xh).abs().sum((1, 2)), 0.5),
+        (XH, xh.abs().sum((1, 2)), 0.5), (gz, gz, q), (gh, gz.abs() @ o["w2"].double().abs(), q),
+        (gpooled * HW, gh.abs() @ o["w1"].double().abs(), q), (gpooled, gpooled, qp),
+        (dw1, gh.abs().t() @ o["pooled"].double().abs(), q / 4), (dw2, gz.abs().t() @ o["hidden"].double().abs(), q / 2),
+        # the rows of BN2's sums as the kernel forms them: s*G + HW*gse and s*GX + gse*XH, one fused multiply-add each
+        (gpooled * XH, gpooled * XH, qp / 2), (bn[:, 0], (sd * G).abs() + (HW * gpooled).abs(), q),
+        (bn[:, 1], (sd * GX).abs() + (gpooled * XH).abs(), qp / 2)])
+    assert float((gh != 0).double().mean()) > 0.2 and float((o["hidden"] == 0).double().mean()) > 0.3, what + ": the ReLU mask"
+    return o, dict(gs=gs, gz=gz, gh=gh, gpooled=gpooled, dw1=dw1, dw2=dw2, parts=parts, bn=bn)

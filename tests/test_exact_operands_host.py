@@ -9,6 +9,7 @@
 """
 import pytest
 import torch
+import torch.nn.functional as F
 
 import exact_operands as X
 import test_gpu_kernels as T
@@ -216,3 +217,214 @@ def test_stem_operands_are_in_the_exact_range(Kp, M):
     X.assert_exact_range(terms=terms, term_quantum=0.25, what="stem backward sums")
     X.assert_exact_range(wgrad_abs=X.wgrad_abs_bound(g.view(1, 1, M, 64), x), what="stem wgrad")
     assert float((y != 0).double().mean()) > 0.5
+
+
+# ------------------------------------------------------------------------------------------------------------ channel-wise passes
+# The recipes of test_gpu_exact_elementwise.py: each asserts its own preconditions (assert_exact_range) when it is built, so
+# building it at every shape of the GPU tests IS the range check; then every reference against a second formulation.
+
+EW = X.EW_SHAPES
+EW_IDS = ["%d_%d_%d_%d" % s[:4] for s in EW]
+MODES = ["plain", "slope", "gate", "gate_gse"]
+
+
+@pytest.mark.parametrize("B,H,W,C,nb", EW, ids=EW_IDS)
+def test_batchnorm_operands_are_in_the_exact_range(B, H, W, C, nb):
+    """fr_bn_apply (every residual kind, gate, slope, gate + slope, the strided identity shortcut), fr_bn_bwd_reduce (four
+    forms of g') and fr_bn_bwd_apply (add kinds 0 / 1, the rows of the BatchNorm in front) at every shape of the GPU tests."""
+    for res_kind in (0, 1, 2):
+        for gate in (False, True):
+            for slope in (False, True):
+                X.bn_apply_case(B, H, W, C, res_kind, gate, slope)
+    for gate in (False, True):
+        for slope in (False, True):
+            X.bn_apply_case(B, H, W, C, 1, gate, slope, res_stride=2)
+    for mode in MODES:
+        X.bn_bwd_case(B, H, W, C, mode)
+        for add_kind in (0, 1):
+            X.bn_bwd_apply_case(B, H, W, C, mode, add_kind, nxt=mode == "plain")
+    X.stats_case(B, H, W, C)
+
+
+def test_scatter_and_long_statistics_operands_are_in_the_exact_range():
+    for shape in X.SCATTER_SHAPES:
+        for mode in ("plain", "slope", "gate_gse"):
+            X.bn_bwd_apply_case(*shape, mode=mode, add_kind=2, nxt=mode == "plain")
+    X.bn_bwd_apply_case(*X.SCATTER_S3, add_kind=2, add_stride=3)
+    X.stats_case(*X.STATS_LONG[:4])
+
+
+def test_squeeze_excite_operands_are_in_the_exact_range():
+    assert {s[1] ** 2 for s in X.SE_SQUEEZE} == set(X.SE_HW)
+    for shape in X.SE_SQUEEZE:
+        _, _, pooled = X.se_squeeze_case(*shape)
+        assert (pooled is not None) == (shape[1] in (4, 8))
+    for shape in X.SE_CHAIN:
+        X.se_bwd_case(*shape)
+        X.se_bwd_case(*shape, zero_w1=True)
+    for shape in X.SE_REAL_HW:
+        X.se_bwd_case(*shape, zero_w1=True)
+    with pytest.raises(AssertionError):  # 1 / 49 is not a power of two: the full chain is refused there
+        X.se_bwd_case(5, 7, 128)
+
+
+def _nchw(t):
+    return t.double().permute(0, 3, 1, 2)
+
+
+def test_bn_apply_reference_equals_torch_modules():
+    """out = prelu(batch_norm(x) * gate) + batch_norm(res[:, ::s, ::s]) with F.batch_norm in eval mode (running mean 0, variance
+    + eps = 1: weight and bias ARE scale and shift), F.prelu and F.max_pool2d(1, s) -- equal, the data being exact."""
+    B, H, W, C = 3, 5, 7, 64
+    eps = 2.0 ** -10
+    zero, one = torch.zeros(C, dtype=torch.float64), torch.full((C,), 1.0 - eps, dtype=torch.float64)
+    for res_kind, gate, slope, stride in ((0, False, False, 1), (1, True, False, 1), (2, True, True, 1), (1, False, True, 2),
+                                          (2, False, False, 1)):
+        o, out, terms = X.bn_apply_case(B, H, W, C, res_kind, gate, slope, stride)
+        v = F.batch_norm(_nchw(o["x"]), zero, one, o["scale"].double(), o["shift"].double(), False, 0.0, eps)
+        if gate:
+            v = v * o["se"].double().view(B, C, 1, 1)
+        if slope:
+            v = F.prelu(v, o["slope"].double())
+        if res_kind:
+            r = F.max_pool2d(_nchw(o["res"]), 1, stride)
+            if res_kind == 2:
+                r = F.batch_norm(r, zero, one, o["rscale"].double(), o["rshift"].double(), False, 0.0, eps)
+            v = v + r
+        assert torch.equal(v.permute(0, 2, 3, 1), out)
+        assert torch.equal(X.column_sums(terms)[1], (v * v).sum((0, 2, 3)))
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("add_kind", [0, 1, 2])
+def test_bn_backward_references_equal_autograd(mode, add_kind):
+    """Training-mode F.batch_norm in float64 on Gaussian data (where its statistics mean something): with the batch's own mean
+    and invstd, s0 = sum g', s1 = sum g' * xhat and inv_count = 1 / rows the formulas of include/frhip.h ARE its backward --
+    d beta, d gamma, d slope and gx (+ the gradient of the MaxPool2d(1, 2) shortcut) against autograd."""
+    from frhip import synth
+    B, H, W, C, eps = 3, 6, 10, 8, 1e-5
+    rows = B * H * W
+    rnd = lambda tag, shape: synth.normal(241, tag, shape).double()  # noqa: E731
+    x, g = rnd("x", (B, H, W, C)).requires_grad_(True), rnd("g", (B, H, W, C))
+    gamma, beta = (rnd("gamma", (C,)) + 2.0).requires_grad_(True), rnd("beta", (C,)).requires_grad_(True)
+    slope = (0.25 + 0.1 * rnd("slope", (C,)).abs()).requires_grad_(True)
+    se, gse = rnd("se", (B, C)).abs() + 0.5, rnd("gse", (B, C))
+    u = F.batch_norm(x.permute(0, 3, 1, 2), None, None, gamma, beta, True, 0.1, eps)
+    kw = {}
+    if mode == "slope":
+        loss = (F.prelu(u, slope) * _nchw(g)).sum()
+    elif mode.startswith("gate"):
+        loss = (u * se.view(B, C, 1, 1) * _nchw(g)).sum()  # the excite multiplies BN's output by the gate ...
+        kw["se"] = se
+        if mode == "gate_gse":
+            loss = loss + (u.sum((2, 3)) * gse).sum()       # ... and the squeeze hands back gse for every pixel of the image
+            kw["gse"] = gse
+    else:
+        loss = (u * _nchw(g)).sum()
+    add = None
+    if add_kind == 1:
+        add = rnd("add", (B, H, W, C))
+        loss = loss + (x * add).sum()
+    elif add_kind == 2:
+        a = rnd("add", (B, H // 2, W // 2, C))
+        loss = loss + (F.max_pool2d(x.permute(0, 3, 1, 2), 1, 2) * _nchw(a)).sum()
+        add = X.scatter(a, H, W, 2)
+    want_gx, want_dg, want_db, want_ds = torch.autograd.grad(loss, [x, gamma, beta, slope], allow_unused=True)
+    xd = x.detach()
+    mean = xd.mean((0, 1, 2))
+    invstd = 1.0 / torch.sqrt(xd.var((0, 1, 2), unbiased=False) + eps)
+    scale = gamma.detach() * invstd
+    shift = beta.detach() - mean * scale
+    if mode == "slope":
+        kw.update(scale=scale, shift=shift, slope=slope.detach())
+    gp, st = X.bn_bwd_gprime(g, xd, **kw)
+    xh = X.xhat(xd, mean, invstd)
+    s = X.column_sums([gp, gp * xh, st])
+    gx = X.bn_bwd_apply(gp, xh, gamma.detach(), invstd, s[0], s[1], 1.0 / rows, add)
+    close = lambda a, b: torch.allclose(a, b, rtol=1e-9, atol=1e-9)  # noqa: E731  (float64 against float64)
+    assert close(s[0], want_db) and close(s[1], want_dg) and close(gx, want_gx)
+    if mode == "slope":
+        assert close(s[2], want_ds)
+
+
+def test_squeeze_excite_references_equal_autograd():
+    """Stage by stage, autograd in float64: gs through the excite product, gz through a sigmoid AT the gate s (z = logit s), gh
+    through the ReLU mask of `hidden`, gpooled through the mean over the image, dW1 / dW2 through the two matrices; the rows of
+    BN2's sums in their closed form s*G + HW*gse, s*GX + gse*XH; fr_se_pool as F.adaptive_avg_pool2d."""
+    B, H, C = 5, 4, 128
+    HW = H * H
+    o, r = X.se_bwd_case(B, H, C)
+    d = {k: v.double() for k, v in o.items()}
+    close = lambda a, b: torch.allclose(a, b, rtol=1e-12, atol=1e-12)  # noqa: E731
+    gate = torch.ones(B, C, dtype=torch.float64, requires_grad=True)
+    y = d["x"] * d["scale"] + d["shift"]
+    (gs,) = torch.autograd.grad((d["g"] * y * gate.view(B, 1, 1, C)).sum(), gate)
+    assert torch.equal(gs, r["gs"])
+    z = torch.logit(d["s"]).requires_grad_(True)
+    (gz,) = torch.autograd.grad((torch.sigmoid(z) * r["gs"]).sum(), z)
+    assert close(gz, r["gz"])
+    w1, w2 = d["w1"].clone().requires_grad_(True), d["w2"].clone().requires_grad_(True)
+    ymap = torch.zeros(B, H, H, C, dtype=torch.float64, requires_grad=True)  # the map the squeeze averages
+    pooled = d["pooled"] + ymap.mean((1, 2))
+    pre = (pooled @ w1.t())
+    pre = pre + (torch.where(d["hidden"] > 0, d["hidden"], -torch.ones_like(d["hidden"])) - pre).detach()  # relu(pre) == hidden
+    pre.retain_grad()
+    hid = torch.relu(pre)
+    assert torch.equal(hid.detach(), d["hidden"])
+    loss = ((hid @ w2.t()) * r["gz"]).sum()
+    gmap, gw1, gw2 = torch.autograd.grad(loss, [ymap, w1, w2], retain_graph=True)
+    (gpre,) = torch.autograd.grad(loss, pre)
+    assert close(gpre, r["gh"])
+    assert close(gmap, r["gpooled"].view(B, 1, 1, C).expand(B, H, H, C))
+    assert close(gw2, r["dw2"])
+    # the weight gradient of fc1 multiplies gh by the pooled INPUT of the recipe (ymap is zero): gh^T pooled
+    assert close(gw1, r["dw1"])
+    sd, gse = d["s"], r["gpooled"]
+    assert torch.equal(r["parts"][:, 0], r["gs"])
+    assert torch.equal(r["bn"][:, 0], sd * r["parts"][:, 1] + HW * gse)
+    assert torch.equal(r["bn"][:, 1], sd * r["parts"][:, 2] + gse * r["parts"][:, 3])
+    q, gs2, pooled2 = X.se_squeeze_case(3, 4, 64)
+    u = F.adaptive_avg_pool2d(_nchw(q["x"]), 1).view(3, 64) * q["scale"].double() + q["shift"].double()
+    assert torch.equal(u, pooled2)
+    assert torch.equal(torch.einsum("bhwc,bhwc->bc", q["g"].double(), q["x"].double() * q["scale"].double() + q["shift"].double()), gs2)
+    x, terms = X.stats_case(3, 5, 7, 64)
+    flat = x.double().reshape(-1, 64)
+    assert torch.equal(X.column_sums(terms), torch.stack([flat.sum(0), (flat * flat).sum(0)]))
+    assert torch.equal(X.image_sums(terms)[:, 1], torch.einsum("bhwc,bhwc->bc", x.double(), x.double()))
+
+
+def test_elementwise_comparators_catch_planted_differences():
+    """One wrong row, one wrong image's gate, one even-row / odd-column hit of the strided scatter -- and a part row left unwritten
+    or taken from one row too many."""
+    B, H, W, C = 5, 7, 7, 128
+    o, out, terms = X.bn_apply_case(B, H, W, C, 1, True, False)
+    X.assert_equal_nhwc(out.to(torch.bfloat16), out, "control")
+    bad = out.clone()
+    bad[3, 6, 2] = 0.0  # one row of the [rows][C] tensor: row 3*49 + 6*7 + 2 never written
+    assert not torch.equal(bad, out)
+    with pytest.raises(AssertionError) as e:
+        X.assert_equal_nhwc(bad.to(torch.bfloat16), out, "control")
+    assert "image 3, row 6, column 2" in str(e.value) and "images [3]" in str(e.value), str(e.value)
+    se = o["se"].clone()
+    se[2] = o["se"][1]  # image 2 reads image 1's gate
+    assert not torch.equal(se[2], o["se"][2])
+    bad, _ = X.bn_apply(**dict(o, se=se))
+    with pytest.raises(AssertionError) as e:
+        X.assert_equal_nhwc(bad.to(torch.bfloat16), out, "control")
+    assert "images [2]" in str(e.value) and "image 2, row 0, column 0" in str(e.value), str(e.value)
+    o, gx, terms = X.bn_bwd_apply_case(3, 6, 10, 64, add_kind=2, nxt=True)
+    X.assert_equal_nhwc(gx.to(torch.bfloat16), gx, "control")
+    bad = gx.clone()
+    bad[:, ::2, 1::2] += o["add"].double()  # hits whenever h is even: the odd columns take their left neighbour's value
+    with pytest.raises(AssertionError) as e:
+        X.assert_equal_nhwc(bad.to(torch.bfloat16), gx, "control")
+    assert "first at (image 0, row 0, column 1, channel 0)" in str(e.value), str(e.value)
+    assert "%d of" % (3 * 3 * 5 * 64) in str(e.value), str(e.value)  # every planted hit counts: add is non-zero everywhere
+    want = X.column_sums(terms)
+    flat = [t.reshape(-1, 64) for t in terms]
+    rows = lambda lo, hi: torch.stack([t[lo:hi].sum(0) for t in flat], 0).float()  # noqa: E731
+    X.assert_sums_equal(torch.stack([rows(0, 100), rows(100, 180)]), want, "control")
+    for parts in (torch.stack([rows(0, 100), torch.full((2, 64), 24576.0)]),   # an idle workgroup left its sentinels
+                  torch.stack([rows(0, 100), rows(99, 180)])):                 # one row counted twice
+        with pytest.raises(AssertionError):
+            X.assert_sums_equal(parts, want, "control")

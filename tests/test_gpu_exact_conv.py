@@ -11,6 +11,8 @@ untouched, and a second launch into the same buffers must leave the same bits.
 The case tables are those of test_gpu_kernels.py, which keeps the checks of the rounding behaviour (integer data cannot
 see rounding).  Not covered here because they divide or multiply by 1 / rows: the moments -> statistics finalisation
 (fr_bn_finalize_res) and the BatchNorm-backward weight gradient of the stem (fr_stem_wgrad_bn / _r).
+The channel-wise passes (BatchNorm apply / backward, statistics, squeeze-excite) are pinned the same way by the sibling
+test_gpu_exact_elementwise.py.
 """
 import pytest
 import torch
