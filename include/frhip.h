@@ -576,6 +576,30 @@ int fr_curricular_apply(const float* cos, const int64_t* label, const float* row
 int fr_curricular_bwd(const float* g, const float* cos, const int64_t* label, const float* rowv, const float* t, float* gcos,
                       int rows, int N, int ld, int ldg, float cos_m, float sin_m, float s, void* stream);
 
+/* ---- MagFace (head/metrics.py:512-553) on the raw cosines cos [rows][ld] of the FR_EPI_STORE GEMM between
+ *      fr_row_normalize'd embeddings and the fr_col_normalize'd [D][N] weight; c = clamp(cos, -1, 1) (NaN passes). */
+/* per-row values (:533-536, :545), rowv [6][rows], from the embeddings' norms ||x_m||, RECOMPUTED from x [rows][D] (summed
+ * in double in a fixed order, then rounded; not 1 / inv_x of fr_row_normalize, whose two reciprocals would cost the
+ * difference 1/u_a^2 - 1/a^2 of the backward pass three digits near u_a):  a = clamp(||x||, l_a, u_a);  cos_m = cos(m(a)), sin_m = sin(m(a)) with
+ * m(a) = (u_margin - l_margin) / (u_a - l_a) * (a - l_a) + l_margin;  min_cos = cos(pi - m(a));
+ * loss_g = lamda * (a / u_a^2 + 1 / a);  inside = 1.0 if l_a <= ||x|| <= u_a else 0.0 (the mask of torch.clamp's
+ * backward).  0 < l_a < u_a. */
+int fr_magface_rows(const float* x, float* rowv, int rows, int D, float l_a, float u_a, float l_margin, float u_margin,
+                    float lamda, void* stream);
+/* out[m][n] = s * (n == label[m] ? (c > min_cos[m] ? c*cos_m[m] - sqrt(1 - c^2)*sin_m[m] : c - margin_am) : c)  (:540-552);
+ * ld a multiple of 4, columns N..ld of out are written as 0.  A label outside [0, N) selects nothing. */
+int fr_magface_apply(const float* cos, const int64_t* label, const float* rowv, float* out, int rows, int N, int ld, float s,
+                     float margin_am, void* stream);
+/* backward of :533-552.  g is [rows][N] contiguous, glossg [rows] the upstream gradient of loss_g (NULL: zeros).
+ * gcos[m][n] = g[m][n] * d out / d cos: s off the label column, s*(cos_m + sin_m*c/sqrt(1 - c^2)) on it in the margin branch
+ * (c > min_cos) and s in the other; 0 where the clamp saturated (the closed interval passes) and in the padding columns
+ * N..ldg.  r[m] = d loss / d ||x_m|| = inside[m] * (g[m][label]*s*(-(sqrt(1 - c^2)*cos_m + c*sin_m))*(u_margin - l_margin)
+ * / (u_a - l_a) [margin branch only; 0 where the label selects nothing] + glossg[m]*lamda*(1/u_a^2 - 1/a^2)): one writer per
+ * row, no sum; it goes through fr_normalize_bwd_radial with nparts = 1. */
+int fr_magface_bwd(const float* g, const float* glossg, const float* cos, const int64_t* label, const float* rowv,
+                   float* gcos, float* r, int rows, int N, int ld, int ldg, float s, float l_a, float u_a, float l_margin,
+                   float u_margin, float lamda, void* stream);
+
 /* ---- focal loss on the batch-mean cross entropy (loss/focal.py:17-21) + top-k (util/utils.py:343-358) */
 /* per row: lse[m], ce[m] = lse - z[label], rank[m] = #{n: z[n] > z[label]} */
 int fr_ce_rows(const float* logits, const int64_t* label, float* lse, float* ce, int32_t* rank, int rows, int N,

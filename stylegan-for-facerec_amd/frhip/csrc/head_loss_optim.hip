@@ -6,6 +6,7 @@
 //   SphereFace margin (clamp, k, Chebyshev phi, lambda blend, *||x||)  head/metrics.py:236-268
 //   Am_softmax l2_norm(kernel, axis=0), clamp, label margin, *s         head/metrics.py:280-284, :302-331
 //   CurricularFace per-row margin, EMA of t, hard-negative re-weighting head/metrics.py:494-509
+//   MagFace magnitude-dependent margin, loss_g, label-column margin      head/metrics.py:533-552
 //   FocalLoss on mean CE                                              loss/focal.py:17-21
 //   accuracy top-1/5                                                  util/utils.py:343-358
 //   optim.SGD(momentum, coupled weight decay on group 0)              train.py:196, :313-316
@@ -421,6 +422,91 @@ __global__ __launch_bounds__(256) void curricular_bwd_kernel(const float* __rest
   });
 }
 
+// ------------------------------------------------------------------------------------------ MagFace
+// head/metrics.py:533-552 on the raw cosines of the FR_EPI_STORE GEMM.  rowv is [6][rows]: a = clamp(||x||, l_a, u_a),
+// cos_m = cos(m(a)), sin_m = sin(m(a)), min_cos = cos(pi - m(a)), loss_g = lamda (a / u_a^2 + 1 / a) and inside (1: the
+// clamp passes gradient, l_a <= ||x|| <= u_a).  ||x|| is recomputed from x, one wave per row, summed in double in a fixed
+// order: a is the correctly rounded norm, and 1 / u_a^2 - 1 / a^2 of the backward pass cancels up to 3x near u_a.
+__global__ __launch_bounds__(256) void magface_rows_kernel(const float* __restrict__ x, float* __restrict__ rowv, int rows,
+                                                           int D, float l_a, float u_a, float l_margin, float u_margin,
+                                                           float lamda) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= rows) return;
+  const float* xr = x + (size_t)i * D;
+  double ss = 0.0;
+  if (D % 4 == 0) {
+    for (int d = lane * 4; d < D; d += 256) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(xr + d);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) ss += (double)v[j] * (double)v[j];
+    }
+  } else {
+    for (int d = lane; d < D; d += 64) ss += (double)xr[d] * (double)xr[d];
+  }
+  ss = wave_sum_d(ss);
+  if (lane != 0) return;
+  const float nrm = (float)sqrt(ss);
+  const float a = nrm < l_a ? l_a : (nrm > u_a ? u_a : nrm);  // torch.clamp: NaN passes
+  const float m = (u_margin - l_margin) / (u_a - l_a) * (a - l_a) + l_margin;
+  rowv[i] = a;
+  rowv[rows + i] = cosf(m);
+  rowv[2 * rows + i] = sinf(m);
+  rowv[3 * rows + i] = cosf(3.14159265358979323846f - m);
+  rowv[4 * rows + i] = lamda * (float)((double)a / ((double)u_a * u_a) + 1.0 / (double)a);
+  rowv[5 * rows + i] = (nrm >= l_a && nrm <= u_a) ? 1.f : 0.f;
+}
+
+// out = s * (label ? (c > min_cos ? c cos_m - sqrt(1 - c^2) sin_m : c - margin_am) : c), c = clamp(cos)
+__global__ __launch_bounds__(256) void magface_apply_kernel(const float* __restrict__ cos,
+                                                            const long long* __restrict__ label,
+                                                            const float* __restrict__ rowv, float* __restrict__ out,
+                                                            int rows, int N, int ld, float s, float margin_am) {
+  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const long long lab = label[row];
+  const float cos_m = rowv[rows + row], sin_m = rowv[2 * rows + row], min_cos = rowv[3 * rows + row];
+  margin_cols_fwd(cos, out, row, N, ld, [&](int n, float raw) {
+    const float c = clamp1(raw);
+    float v = c;
+    if (n == lab) v = c > min_cos ? c * cos_m - sqrtf(1.0f - c * c) * sin_m : c - margin_am;
+    return v * s;
+  });
+}
+
+// gcos = g * d out / d cos: s, and s (cos_m + sin_m c / sqrt(1 - c^2)) on the label column in the margin branch.  The wave
+// whose column chunk holds the label (chunk 0 when no column is selected) also writes the row's radial scalar
+// r = inside (g[label] s (-(sqrt(1 - c^2) cos_m + c sin_m)) dm/da [margin branch] + glossg lamda (1 / u_a^2 - 1 / a^2)):
+// d loss / d ||x|| through the margin and through loss_g, one writer per row, no sum.
+__global__ __launch_bounds__(256) void magface_bwd_kernel(const float* __restrict__ g, const float* __restrict__ glossg,
+                                                          const float* __restrict__ cos, const long long* __restrict__ label,
+                                                          const float* __restrict__ rowv, float* __restrict__ gcos,
+                                                          float* __restrict__ r, int rows, int N, int ld, int ldg, float s,
+                                                          float slope, double inv_ua2, float lamda) {
+  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const long long lab = label[row];
+  const bool has = lab >= 0 && lab < N;
+  const float cos_m = rowv[rows + row], sin_m = rowv[2 * rows + row], min_cos = rowv[3 * rows + row];
+  margin_cols_bwd(g, cos, gcos, row, N, ld, ldg, [&](int n, float raw, float gg) {
+    const float c = clamp1(raw);
+    float d = 1.f;
+    if (n == lab && c > min_cos) d = cos_m + sin_m * c / sqrtf(1.0f - c * c);
+    return gg * s * d;
+  });
+  const int owner = has ? (int)(lab / MARGIN_COLS) : 0;
+  if ((int)blockIdx.x == owner && (threadIdx.x & 63) == 0) {
+    const float a = rowv[row];
+    float v = 0.f;
+    if (has) {
+      const float c = clamp1(cos[(size_t)row * ld + lab]);
+      if (c > min_cos) v = g[(size_t)row * N + lab] * s * (-(sqrtf(1.0f - c * c) * cos_m + c * sin_m)) * slope;
+    }
+    if (glossg) v += glossg[row] * lamda * (float)(inv_ua2 - 1.0 / ((double)a * a));
+    r[row] = rowv[5 * rows + row] != 0.f ? v : 0.f;
+  }
+}
+
 // ------------------------------------------------------------------------------------------ cross entropy rows
 __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ z, const long long* __restrict__ label,
                                                       float* __restrict__ lse, float* __restrict__ ce,
@@ -789,6 +875,35 @@ extern "C" int fr_curricular_bwd(const float* g, const float* cos, const int64_t
     FR_UNSUPPORTED("fr_curricular_bwd: shape (ldg >= ld >= N, multiples of 4)");
   hipLaunchKernelGGL(curricular_bwd_kernel, dim3(fr_margin_apply_parts(ldg), (rows + 3) / 4), dim3(256), 0,
                      (hipStream_t)stream, g, cos, (const long long*)label, rowv, t, gcos, rows, N, ld, ldg, cos_m, sin_m, s);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_magface_rows(const float* x, float* rowv, int rows, int D, float l_a, float u_a, float l_margin,
+                               float u_margin, float lamda, void* stream) {
+  if (rows <= 0 || D <= 0) FR_UNSUPPORTED("fr_magface_rows: shape (rows > 0, D > 0)");
+  if (!(l_a > 0.f && u_a > l_a)) FR_UNSUPPORTED("fr_magface_rows: 0 < l_a < u_a");
+  hipLaunchKernelGGL(magface_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, rowv, rows, D, l_a,
+                     u_a, l_margin, u_margin, lamda);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_magface_apply(const float* cos, const int64_t* label, const float* rowv, float* out, int rows, int N,
+                                int ld, float s, float margin_am, void* stream) {
+  if (rows <= 0 || N <= 0 || ld < N || ld % 4) FR_UNSUPPORTED("fr_magface_apply: shape (ld >= N, multiple of 4)");
+  hipLaunchKernelGGL(magface_apply_kernel, dim3(fr_margin_apply_parts(ld), (rows + 3) / 4), dim3(256), 0,
+                     (hipStream_t)stream, cos, (const long long*)label, rowv, out, rows, N, ld, s, margin_am);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_magface_bwd(const float* g, const float* glossg, const float* cos, const int64_t* label,
+                              const float* rowv, float* gcos, float* r, int rows, int N, int ld, int ldg, float s, float l_a,
+                              float u_a, float l_margin, float u_margin, float lamda, void* stream) {
+  if (rows <= 0 || N <= 0 || ld < N || ld % 4 || ldg < ld || ldg % 4)
+    FR_UNSUPPORTED("fr_magface_bwd: shape (ldg >= ld >= N, multiples of 4)");
+  if (!(l_a > 0.f && u_a > l_a)) FR_UNSUPPORTED("fr_magface_bwd: 0 < l_a < u_a");
+  hipLaunchKernelGGL(magface_bwd_kernel, dim3(fr_margin_apply_parts(ldg), (rows + 3) / 4), dim3(256), 0,
+                     (hipStream_t)stream, g, glossg, cos, (const long long*)label, rowv, gcos, r, rows, N, ld, ldg, s,
+                     (u_margin - l_margin) / (u_a - l_a), 1.0 / ((double)u_a * u_a), lamda);
   FR_LAUNCH_CHECK();
 }
 

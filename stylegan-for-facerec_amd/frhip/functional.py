@@ -30,13 +30,14 @@ def _pad(n, m):
 # One cosine-head pipeline under the five heads.  Forward: ``_cosine_operands`` (normalised operands), the cosine GEMM
 # (``_raw_cosines``, or ArcFace / CosFace's fused margin epilogue), the head's row kernels.  Backward: the head's gcos
 # kernel, then ``_cosine_backward`` (both GEMMs and the normalisation backwards).
-ARCFACE, COSFACE, SPHEREFACE, AM_SOFTMAX, CURRICULAR = range(5)  # 0..3 are the margin kinds of the kernels
+ARCFACE, COSFACE, SPHEREFACE, AM_SOFTMAX, CURRICULAR, MAGFACE = range(6)  # 0..3 are the margin kinds of the kernels
 
 # What a forward call keeps for its backward call; a head leaves what it does not use at None.  xn / wn [Np, D] / wt
 # [D, Np] are the GEMM operands (xn is x itself for Am_softmax), inv_x / inv_w the reciprocal norms, cos_t the target
-# cosines of the fused epilogue, cos the raw cosines [B, ld], rowv and t CurricularFace's row values and the t it used.
+# cosines of the fused epilogue, cos the raw cosines [B, ld], rowv and t CurricularFace's row values and the t it used
+# (rowv: MagFace's six row values too).  HeadCfg.mag: MagFace's (margin_am, l_a, u_a, l_margin, u_margin, lamda).
 HeadSaved = collections.namedtuple("HeadSaved", "x w label xn wn wt inv_x inv_w cos_t cos rowv t", defaults=(None,) * 12)
-HeadCfg = collections.namedtuple("HeadCfg", "kind Np ld s cos_m sin_m th easy mi p0 p1", defaults=(None,) * 8)
+HeadCfg = collections.namedtuple("HeadCfg", "kind Np ld s cos_m sin_m th easy mi p0 p1 mag", defaults=(None,) * 9)
 
 
 def _cosine_operands(x, weight, label, norm_x, col_weight):
@@ -243,6 +244,38 @@ def curricular_backward(saved, cfg, g, need_x, need_w, raw_x_grad=False):
     return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, None if raw_x_grad else "normalize", col_weight=True)
 
 
+def magface_forward(x, kernel, label, s, margin_am, l_a, u_a, l_margin, u_margin, lamda):
+    """MagFace (head/metrics.py:512-553) for fp32 device tensors; ``kernel`` is [D, N].  Returns (logits [B, N], loss_g
+    [B, 1] = lamda * (a / u_a^2 + 1 / a) with a = clamp(||x||, l_a, u_a), saved, cfg) for ``magface_backward``.  The row
+    kernel takes the norms from x itself.  A label outside [0, N) selects nothing in its row."""
+    sv, N, Np, ld = _cosine_operands(x, kernel, label, norm_x=True, col_weight=True)
+    B = x.shape[0]
+    st = ops.current_stream_ptr()
+    cos = _raw_cosines(sv, N, ld)
+    mag = tuple(float(v) for v in (margin_am, l_a, u_a, l_margin, u_margin, lamda))
+    rowv = torch.empty(6, B, device=x.device)  # a, cos_m, sin_m, min_cos, loss_g, inside
+    ops.call("fr_magface_rows", sv.x, rowv, B, x.shape[1], *mag[1:], st)()
+    store, logits = _logit_store(sv, N, ld)
+    ops.call("fr_magface_apply", cos, sv.label, rowv, store, B, N, ld, float(s), mag[0], st)()
+    return logits, rowv[4].clone().view(B, 1), sv._replace(cos=cos, rowv=rowv), HeadCfg(MAGFACE, Np, ld, s=float(s), mag=mag)
+
+
+def magface_backward(saved, cfg, g, glossg, need_x, need_w):
+    """(gx, gkernel) of ``magface_forward`` from the upstream gradients of the logits and of loss_g; either may be None
+    (zeros).  gx leaves the tangent plane of normalize(x): the radial scalar r [B] of fr_magface_bwd (the margin's and
+    loss_g's dependence on ||x||) goes through fr_normalize_bwd_radial."""
+    B, N = saved.x.shape[0], saved.inv_w.shape[0]
+    dev = saved.x.device
+    g = torch.zeros(B, N, device=dev) if g is None else g.contiguous().float()
+    if glossg is not None:
+        glossg = glossg.contiguous().float()
+    gcos = torch.empty(B, cfg.Np, device=dev)
+    r = torch.empty(B, device=dev)
+    ops.call("fr_magface_bwd", g, glossg, saved.cos, saved.label, saved.rowv, gcos, r, B, N, cfg.ld, cfg.Np, cfg.s,
+             *cfg.mag[1:], ops.current_stream_ptr())()
+    return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, "radial", col_weight=True, r_part=r.view(B, 1))
+
+
 def _head_fn(name, fwd, bwd, doc):
     """The autograd.Function of a head from its forward / backward pair; it takes the forward function's arguments (x,
     weight, label and four head-specific values)."""
@@ -262,6 +295,29 @@ def _head_fn(name, fwd, bwd, doc):
                 {"forward": staticmethod(forward), "backward": staticmethod(backward), "__doc__": doc})
 
 
+def _head_fn2(name, fwd, bwd, doc):
+    """``_head_fn`` for a head with a second output (MagFace's loss_g): ``fwd`` returns (logits, second, saved, cfg), ``bwd``
+    takes both upstream gradients, None where an output took no part in the loss."""
+
+    def forward(ctx, x, weight, label, *args):
+        logits, second, saved, cfg = fwd(x, weight, label, *args)
+        ctx.save_for_backward(*saved)
+        ctx.cfg = cfg
+        ctx.nargs = len(args)
+        ctx.mark_non_differentiable(label)
+        ctx.set_materialize_grads(False)
+        return logits, second
+
+    def backward(ctx, g, g2):
+        gx = gw = None
+        if g is not None or g2 is not None:
+            gx, gw = bwd(HeadSaved(*ctx.saved_tensors), ctx.cfg, g, g2, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return (gx, gw, None) + (None,) * ctx.nargs
+
+    return type(name, (torch.autograd.Function,),
+                {"forward": staticmethod(forward), "backward": staticmethod(backward), "__doc__": doc})
+
+
 MarginHeadFn = _head_fn("MarginHeadFn", margin_forward, margin_backward, """
     logits = s * where(j == label, phi(cos), cos),  cos = normalize(x) . normalize(W)^T
 
@@ -271,6 +327,9 @@ MarginExtHeadFn = _head_fn("MarginExtHeadFn", margin_ext_forward, margin_ext_bac
     SphereFace (head/metrics.py:236-268) and Am_softmax (:302-331) on the HIP path; see ``margin_ext_forward``.""")
 CurricularHeadFn = _head_fn("CurricularHeadFn", curricular_forward, curricular_backward, """
     CurricularFace (head/metrics.py:475-510) on the HIP path; see ``curricular_forward``.""")
+
+MagFaceHeadFn = _head_fn2("MagFaceHeadFn", magface_forward, magface_backward, """
+    MagFace (head/metrics.py:512-553) on the HIP path: (logits, loss_g); see ``magface_forward``.""")
 
 CHECK_LABELS = True  # host-side range check of the labels (one device sync per call); loops with validated data clear it
 
@@ -305,6 +364,14 @@ def curricular_head(x, kernel, label, t, s, m, group=None):
     """CurricularFace logits; the empty batch and label check of ``margin_head``.  ``t`` (float32 [1] on x's device) is
     updated in place; an empty batch leaves it as it is (the reference's mean over no rows turns it into NaN for good)."""
     return _head_entry(CurricularHeadFn, kernel.shape[1], x, kernel, label, t, s, m, group, t=t)
+
+
+def magface_head(x, kernel, label, s, margin_am, l_a, u_a, l_margin, u_margin, lamda):
+    """MagFace (logits [B, N], loss_g [B, 1]); the empty batch and label check of ``margin_head``."""
+    out = _head_entry(MagFaceHeadFn, kernel.shape[1], x, kernel, label, s, margin_am, l_a, u_a, l_margin, u_margin, lamda)
+    if torch.is_tensor(out):  # the empty batch: [0, N] logits, and no rows of loss_g either
+        return out, out[:, :1]
+    return out
 
 
 class FocalLossFn(torch.autograd.Function):

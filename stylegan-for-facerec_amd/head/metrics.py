@@ -1,11 +1,11 @@
 """Margin-softmax heads with the reference's import path, constructor signatures and state-dict keys.
 
     from head.metrics import ArcFace, CosFace, SphereFace, Am_softmax        (reference train.py:9)
-    from head.metrics import CurricularFace                                  (reference head/metrics.py:475)
+    from head.metrics import CurricularFace, MagFace                         (reference head/metrics.py:475, :512)
 
-The four heads the reference driver can select (``HEAD_NAME``, train.py:56,178-182) and ``CurricularFace`` (one of the
-FaceX-Zoo heads of the reference's head/metrics.py that its driver never names; train.py here accepts it) run on the HIP
-kernels when their input is a device tensor:
+The four heads the reference driver can select (``HEAD_NAME``, train.py:56,178-182) and ``CurricularFace`` / ``MagFace``
+(two of the FaceX-Zoo heads of the reference's head/metrics.py that its driver never names; train.py here accepts them) run
+on the HIP kernels when their input is a device tensor:
   * ``ArcFace`` / ``CosFace`` (the two heads the shipped configs and BASELINE.json name): row normalise -> MFMA cosine
     GEMM with the margin / label-select / scale epilogue -> closed-form backward;
   * ``SphereFace`` / ``Am_softmax``: the same cosine GEMM stores the raw cosines, a row kernel applies the clamp and the
@@ -15,8 +15,12 @@ kernels when their input is a device tensor:
   * ``CurricularFace``: rows and ``kernel`` columns normalised, raw cosines from the same GEMM; one workgroup takes the
     per-row target cosine, cos(theta + m), the label column's value and the batch mean, and moves the buffer ``t`` on the
     device (no host read in the step); a row kernel re-weights the negatives above their row's cos(theta + m) by
-    ``t + c``; the backward pass treats ``t``, that mask and the branch choice as constants.
-On host tensors ``SphereFace`` / ``Am_softmax`` / ``CurricularFace`` run the reference's plain-PyTorch arithmetic (the
+    ``t + c``; the backward pass treats ``t``, that mask and the branch choice as constants;
+  * ``MagFace``: rows and ``weight`` columns normalised, raw cosines from the same GEMM; a row kernel turns each embedding's
+    norm into its clamped magnitude a, the margin m(a) (cos, sin, cos(pi - m)), the regulariser ``loss_g`` and the clamp's
+    mask; a row kernel applies the per-row margin on the label column.  It returns ``(logits, lamda * loss_g)``.  The
+    backward pass adds a radial term r * xhat to the feature gradient: the margin and ``loss_g`` both depend on ||x||.
+On host tensors ``SphereFace`` / ``Am_softmax`` / ``CurricularFace`` / ``MagFace`` run the reference's plain-PyTorch arithmetic (the
 restatement the tests compare with); ``ArcFace`` / ``CosFace`` refuse host tensors.  ``SphereFace.iter`` counts forward
 calls on either path, as in the reference; train.py carries it across a resume in the State_* file.  ``CurricularFace.t``
 is a buffer: the Head_* file carries it.
@@ -32,6 +36,9 @@ Differences from the reference that a caller can observe:
     reference's ``F.normalize(kernel, dim=0)``: a column of norm below 1e-12 is out of contract.  A target cosine of
     exactly +-1 makes the reference's own gradient infinite (sin_m * tl / sqrt(1 - tl^2)); nothing is done about it here
     either.  An empty batch leaves ``t`` as it is (the reference's mean over no rows makes it NaN for good).
+  * ``MagFace`` on the device path: the same two limits (no eps on the ``weight`` columns, a target cosine of exactly +-1).
+    The label select is a ``where`` on the label column, so negatives at a cosine of exactly +-1 get a finite gradient
+    (the reference's sqrt(1 - c^2) over the whole matrix makes theirs NaN).
 """
 import math
 
@@ -195,3 +202,36 @@ class CurricularFace(nn.Module):
         hard = (c > ctm).detach()
         out = torch.where(hard, c * (self.t + c), c).scatter(1, at, final)
         return out * self.s
+
+
+class MagFace(nn.Module):
+    """MagFace (reference head/metrics.py:512-553): HIP kernels on device tensors, plain PyTorch on the host.
+
+    Returns ``(logits, lamda * loss_g)``, loss_g [B, 1] = a / u_a^2 + 1 / a with a = clamp(||x||, l_a, u_a); the margin on
+    the label column is m(a), linear from l_margin at l_a to u_margin at u_a.  train.py adds ``loss_g.mean()`` to the loss."""
+
+    def __init__(self, feat_dim, num_class, margin_am=0.0, scale=32, l_a=10, u_a=110, l_margin=0.45, u_margin=0.8, lamda=20):
+        super().__init__()
+        self.weight = Parameter(torch.empty(feat_dim, num_class))
+        self.weight.data.uniform_(-1, 1).renorm_(2, 1, 1e-5).mul_(1e5)
+        self.margin_am, self.scale, self.l_a, self.u_a = margin_am, scale, l_a, u_a
+        self.l_margin, self.u_margin, self.lamda = l_margin, u_margin, lamda
+
+    def calc_margin(self, x):
+        return (self.u_margin - self.l_margin) / (self.u_a - self.l_a) * (x - self.l_a) + self.l_margin
+
+    def forward(self, feats, labels):
+        if feats.is_cuda:
+            _beside(self, self.weight, feats)
+            return FRF.magface_head(feats, self.weight, labels.to(feats.device), self.scale, self.margin_am, self.l_a,
+                                    self.u_a, self.l_margin, self.u_margin, self.lamda)
+        weight = self.weight.to(feats.device)
+        a = torch.norm(feats, dim=1, keepdim=True).clamp(self.l_a, self.u_a)
+        m = self.calc_margin(a)
+        loss_g = 1 / (self.u_a ** 2) * a + 1 / a
+        c = torch.mm(F.normalize(feats), F.normalize(weight, dim=0)).clamp(-1, 1)
+        at = labels.view(-1, 1).long()
+        tl = c.gather(1, at)
+        ctm = tl * torch.cos(m) - torch.sqrt(1.0 - torch.pow(tl, 2)) * torch.sin(m)  # cos(theta_target + m(a))
+        final = torch.where(tl > torch.cos(math.pi - m), ctm, tl - self.margin_am)
+        return c.scatter(1, at, final) * self.scale, self.lamda * loss_g

@@ -5,7 +5,7 @@
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 train.py --config configs/...
     python train.py --config configs/config_synthetic_smoke.py --synthetic 100x12 --max-steps 20
 
-Kept from the reference (train.py:41-421): every config key, module construction order (all four heads are built
+Kept from the reference (train.py:41-421): every config key, module construction order (all heads are built
 eagerly), the BN / non-BN parameter groups, LR stages (/1.5), optional warm-up, the freeze -> unfreeze schedule on
 ``.module.encoder.body``, per-step top-1/5, per-epoch checkpoint file names.  Changed on purpose (SURVEY.md section 7,
 hard parts): one process per GPU with RCCL gradient all-reduce instead of nn.DataParallel (BATCH_SIZE is per GPU),
@@ -35,7 +35,7 @@ from frhip import functional as FRF
 from frhip import set_compute_dtype
 from frhip.optim import SGD, Adam
 from frhip.parallel import DataParallel
-from head.metrics import Am_softmax, ArcFace, CosFace, CurricularFace, SphereFace
+from head.metrics import Am_softmax, ArcFace, CosFace, CurricularFace, MagFace, SphereFace
 from loss.focal import FocalLoss
 from util.utils import (AverageMeter, accuracy, buffer_val, collate_fn_ignore_none, get_time, get_val_data, perform_val,
                         schedule_lr, separate_irse_bn_paras, warm_up_lr)
@@ -120,6 +120,14 @@ def load_optimizer_checkpoint(optimizer, crit, sd):
     optimizer.load_state_dict(sd)
 
 
+def check_head_config(cfg):
+    """Refuse, before anything is built, a combination the driver does not serve."""
+    if cfg.get("SHARDED_HEAD", False) and cfg["HEAD_NAME"] == "MagFace":
+        raise NotImplementedError("SHARDED_HEAD=True with HEAD_NAME 'MagFace': the class-sharded head does not serve MagFace "
+                                  "(its radial term and loss_g need an exchange of their own); run it replicated, "
+                                  "SHARDED_HEAD=False")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=str, default="config.py")
@@ -127,6 +135,7 @@ def main():
     ap.add_argument("--max-steps", type=int, default=0)
     args = ap.parse_args()
     cfg = importlib.import_module(args.config.replace(".py", "").replace("/", ".")).configurations[1]
+    check_head_config(cfg)
 
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -187,6 +196,8 @@ def main():
     heads = {"ArcFace": ArcFace(emb, num_class, None, s=s), "CosFace": CosFace(emb, num_class, None),
              "SphereFace": SphereFace(emb, num_class, None), "Am_softmax": Am_softmax(emb, num_class, None),
              "CurricularFace": CurricularFace(emb, num_class, s=s)}
+    with torch.random.fork_rng(devices=[]):  # built last and off the generator: the five above keep their initial weights
+        heads["MagFace"] = MagFace(emb, num_class)  # and what is drawn after them; the reference's own scale (32)
     head = heads[cfg["HEAD_NAME"]]
     if world > 1 and hasattr(head, "process_group") and not cfg.get("SHARDED_HEAD", False):
         # replicated CurricularFace: t follows the mean target cosine of the GLOBAL batch, as under the reference's
@@ -302,7 +313,12 @@ def main():
                 loss, prec1, prec5 = crit(BACKBONE(inputs), labels)
             else:
                 outputs = head(BACKBONE(inputs), labels)
+                loss_g = None
+                if isinstance(outputs, tuple):  # MagFace: (logits, lamda * loss_g [B, 1]), combined as in FaceX-Zoo
+                    outputs, loss_g = outputs
                 loss = loss_fn(outputs, labels)[0] if loss_fn is not None else ce(outputs, labels)
+                if loss_g is not None:
+                    loss = loss + loss_g.mean()
                 prec1, prec5 = accuracy(outputs.data, labels, topk=(1, 5))
             pending.append((loss.detach(), prec1, prec5, inputs.size(0)))
             optimizer.zero_grad()

@@ -2,13 +2,16 @@
 calls (mode fwdbwd) after 3 warm-up calls, event-timed; run it under `rocprofv3 --kernel-trace --stats -- ...` for the
 kernel times (profiles/margin_heads_b256_n28000.txt).
 
-    python tools/head_time.py {ArcFace|CosFace|SphereFace|Am_softmax|CurricularFace} {fwd|fwdbwd} ITERS
+    python tools/head_time.py {ArcFace|CosFace|SphereFace|Am_softmax|CurricularFace|MagFace} {fwd|fwdbwd} ITERS
 
 Several heads, comma separated, are timed in ONE process in alternating rounds (ROUNDS rounds of ITERS calls per head, the
 median round of each head reported, and the ratio to the first head named), so clocks and allocator state are shared
-(profiles/curricular_head_b256_n28000.txt):
+(profiles/curricular_head_b256_n28000.txt, profiles/magface_head_b256_n28000.txt):
 
     python tools/head_time.py Am_softmax,ArcFace,CurricularFace fwdbwd ITERS [ROUNDS]
+
+MagFace returns (logits, loss_g); its backward call takes ``g`` for the logits and ones / B for loss_g (train.py's
+``loss_g.mean()``), so both of its radial terms are in the timed path.
 """
 import os
 import sys
@@ -26,11 +29,12 @@ FRF.CHECK_LABELS = False
 x = synth.normal(5, "t.x", (B, D)).cuda().requires_grad_(mode == "fwdbwd")
 label = synth.labels(5, "t.y", B, N).cuda()
 g = synth.normal(5, "t.g", (B, N)).cuda()
+gg = torch.full((B, 1), 1.0 / B).cuda()
 
 
 def make(name):
     cls = getattr(H, name)
-    head = (cls(D, N) if name == "CurricularFace" else cls(D, N, None)).cuda()  # FaceX-Zoo heads take no device_id
+    head = (cls(D, N) if name in ("CurricularFace", "MagFace") else cls(D, N, None)).cuda()  # FaceX-Zoo heads: no device_id
     p = list(head.parameters())[0]
 
     def step():
@@ -38,7 +42,10 @@ def make(name):
         if mode == "fwdbwd":
             x.grad = None
             p.grad = None
-            y.backward(g)
+            if isinstance(y, tuple):
+                torch.autograd.backward(y, [g, gg])
+            else:
+                y.backward(g)
 
     return step
 
