@@ -600,6 +600,29 @@ int fr_magface_bwd(const float* g, const float* glossg, const float* cos, const 
                    float* gcos, float* r, int rows, int N, int ld, int ldg, float s, float l_a, float u_a, float l_margin,
                    float u_margin, float lamda, void* stream);
 
+/* ---- AdaCos (head/metrics.py:336-369) on the raw cosines cos [rows][ld] of the FR_EPI_STORE GEMM between
+ *      fr_row_normalize'd embeddings and the fr_row_normalize'd [N][D] weight.  scale is the head's one-float device buffer:
+ *      read by fr_adacos_rows, moved by fr_adacos_scale (its only writer), read by fr_adacos_apply; never by the host. */
+/* per-row values (:363, :366), rowv [2][rows]:  rowv[0][m] = sum over n < N, n != label[m] of expf(scale[0] * cos[m][n]), the
+ * raw cosine without a clamp, added in a fixed order (per-thread sums in double over ascending columns, the wave's xor
+ * butterfly, the sixteen waves of the row's workgroup in order);  rowv[1][m] = cos[m][label[m]], the raw target cosine.
+ * A row whose label lies outside [0, N) has no target: all N columns enter its sum and rowv[1][m] is the marker 2.0f.
+ * ld a multiple of 4. */
+int fr_adacos_rows(const float* cos, const int64_t* label, const float* scale, float* rowv, int rows, int N, int ld,
+                   void* stream);
+/* scale[0] <- log(B_avg) / cos(min(pi/4, theta_med))  (:364-367), one workgroup, one writer:  B_avg = sum(rowv[0]) / rows,
+ * added in double in a fixed order;  theta_med = torch.median of acos(clamp(rowv[1], -1 + 1e-7, 1 - 1e-7)) over the rows
+ * that have a target, i.e. the LOWER median, the angle of the cosine at descending rank (n - 1) / 2 (ties by row index).
+ * Any rows >= 0 (a rank-counting select through fixed-size LDS tiles: rows^2 / 256 compares per thread); rowv may be the
+ * all-gathered rows of every rank.  rows == 0, or no row with a target: scale is left as it is.  A NaN target cosine
+ * makes it NaN. */
+int fr_adacos_scale(const float* rowv, int rows, float* scale, void* stream);
+/* out[m][n] = scale[0] * src[m][n] for n < N and 0 for N <= n < ld_out; src has the pitch ld_src >= N, out the pitch
+ * ld_out >= N, a multiple of 4.  Forward (:368): src = the raw cosines (pitch ld), out = the logits store (pitch ld): the
+ * NEW scale times the unclamped cosine.  Backward: src = g [rows][N] contiguous, out = gcos (pitch Np), the scale this
+ * forward call used: it is a constant of the graph (:362 no_grad), so d out / d cos = scale everywhere. */
+int fr_adacos_apply(const float* src, const float* scale, float* out, int rows, int N, int ld_src, int ld_out, void* stream);
+
 /* ---- focal loss on the batch-mean cross entropy (loss/focal.py:17-21) + top-k (util/utils.py:343-358) */
 /* per row: lse[m], ce[m] = lse - z[label], rank[m] = #{n: z[n] > z[label]} */
 int fr_ce_rows(const float* logits, const int64_t* label, float* lse, float* ce, int32_t* rank, int rows, int N,

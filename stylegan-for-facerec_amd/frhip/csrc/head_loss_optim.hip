@@ -7,6 +7,7 @@
 //   Am_softmax l2_norm(kernel, axis=0), clamp, label margin, *s         head/metrics.py:280-284, :302-331
 //   CurricularFace per-row margin, EMA of t, hard-negative re-weighting head/metrics.py:494-509
 //   MagFace magnitude-dependent margin, loss_g, label-column margin      head/metrics.py:533-552
+//   AdaCos row sums of exp(s cos), median target angle, the scale moved  head/metrics.py:359-368
 //   FocalLoss on mean CE                                              loss/focal.py:17-21
 //   accuracy top-1/5                                                  util/utils.py:343-358
 //   optim.SGD(momentum, coupled weight decay on group 0)              train.py:196, :313-316
@@ -507,6 +508,137 @@ __global__ __launch_bounds__(256) void magface_bwd_kernel(const float* __restric
   }
 }
 
+// ------------------------------------------------------------------------------------------ AdaCos
+// head/metrics.py:359-368 on the raw cosines of the FR_EPI_STORE GEMM.  The scale is a one-float device buffer: the row
+// kernel reads the old value inside exp, one workgroup turns the row values into the new one and writes it (the only
+// writer), and the apply kernel reads that.  rowv is [2][rows]: the row's sum of exp(scale * cos) over the columns that
+// are not its label, and its raw target cosine, ADACOS_NO_TARGET where the label lies outside [0, N).
+constexpr float ADACOS_NO_TARGET = 2.0f;  // no cosine reaches it
+
+// One workgroup of 1024 threads per row (a whole-row reduction: one wave per row would leave 256 waves on the chip at batch
+// 256; sixteen per row keep enough loads in flight).  Order of the sum, fixed: thread t adds its columns 4t .. 4t+3,
+// 4t+4096 .. in ascending order in double, the 64 lanes of a wave go through wave_sum_d's xor butterfly, and thread 0 adds
+// the sixteen waves' sums in wave order.
+constexpr int ADACOS_ROW_THREADS = 1024;
+
+__global__ __launch_bounds__(ADACOS_ROW_THREADS) void adacos_rows_kernel(const float* __restrict__ cos, const long long* __restrict__ label,
+                                                          const float* __restrict__ scale, float* __restrict__ rowv,
+                                                          int rows, int N, int ld) {
+  __shared__ double dred[ADACOS_ROW_THREADS / 64];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const long long lab = label[row];
+  const float s = scale[0];
+  const float* crow = cos + (size_t)row * ld;
+  double acc = 0.0;
+  for (int n = tid * 4; n < N; n += 4 * ADACOS_ROW_THREADS) {  // n + 3 < ld: n < N <= ld, both multiples of 4
+    const f32x4 ch = *reinterpret_cast<const f32x4*>(crow + n);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (n + j < N && n + j != lab) acc += (double)expf(s * ch[j]);  // the raw cosine, no clamp (:363)
+  }
+  acc = wave_sum_d(acc);
+  if ((tid & 63) == 0) dred[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    double sum = 0.0;
+    for (int w = 0; w < ADACOS_ROW_THREADS / 64; ++w) sum += dred[w];
+    rowv[row] = (float)sum;
+    rowv[rows + row] = (lab >= 0 && lab < N) ? crow[lab] : ADACOS_NO_TARGET;
+  }
+}
+
+// One workgroup: B_avg = sum(rowv[0]) / rows in double in a fixed order (thread t adds rows t, t + 256, .., then as
+// above), and the lower median of the target angles = the angle of the target cosine at descending rank (n - 1) / 2 among
+// the n rows that have one (acos falls, so the order statistic is taken on the cosines).  Rank of row i: the number of rows j with c_j > c_i, or c_j == c_i and j < i -- a permutation
+// of 0 .. n-1, so exactly one row has the wanted rank; found by counting through 256-float LDS tiles, no sort and no
+// storage that grows with rows.  A NaN target cosine makes the scale NaN (torch.median propagates it).  rows without a
+// target enter B_avg (their whole row is in rowv[0]) and not the median; with none that has one the scale stays.
+__global__ __launch_bounds__(256) void adacos_scale_kernel(const float* __restrict__ rowv, int rows,
+                                                           float* __restrict__ scale) {
+  __shared__ double dred[4];
+  __shared__ float tile[256];
+  __shared__ int nred[4], bad[4];
+  __shared__ float sel;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* tc = rowv + rows;
+  double acc = 0.0;
+  int cnt = 0, isn = 0;
+  for (int i = tid; i < rows; i += 256) {
+    acc += (double)rowv[i];
+    const float c = tc[i];
+    cnt += c != ADACOS_NO_TARGET;
+    isn |= c != c;
+  }
+  acc = wave_sum_d(acc);
+  const int wcnt = (int)wave_sum((float)cnt);  // cnt <= rows / 256 + 1 per thread: exact in fp32 below 2^24 rows
+  const int wnan = __any(isn);
+  if (lane == 0) {
+    dred[wave] = acc;
+    nred[wave] = wcnt;
+    bad[wave] = wnan;
+  }
+  __syncthreads();
+  const int n = nred[0] + nred[1] + nred[2] + nred[3];
+  if (n == 0) return;  // no row has a target: the scale stays (uniform over the workgroup)
+  const int want = (n - 1) / 2;
+  for (int base = 0; base < rows; base += 256) {
+    const int i = base + tid;
+    const float ci = i < rows ? tc[i] : ADACOS_NO_TARGET;
+    int rank = 0;
+    for (int jb = 0; jb < rows; jb += 256) {
+      __syncthreads();
+      tile[tid] = jb + tid < rows ? tc[jb + tid] : ADACOS_NO_TARGET;
+      __syncthreads();
+      const int jn = min(256, rows - jb);
+      for (int jj = 0; jj < jn; ++jj) {
+        const float cj = tile[jj];
+        rank += cj != ADACOS_NO_TARGET && (cj > ci || (cj == ci && jb + jj < i));
+      }
+    }
+    if (ci != ADACOS_NO_TARGET && rank == want) sel = ci;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const double b_avg = (dred[0] + dred[1] + dred[2] + dred[3]) / rows;
+    const float lo = (float)(-1.0 + 1e-7), hi = (float)(1.0 - 1e-7);  // the clamp of :359 on fp32 cosines
+    const float c = sel < lo ? lo : (sel > hi ? hi : sel);
+    // cos(min(pi/4, acos(c))) = max(cos(pi/4), c): cos falls on [0, pi], so neither the angle nor its cosine is formed
+    float v = (float)(log(b_avg) / fmax(0.70710678118654752440, (double)c));
+    if (bad[0] | bad[1] | bad[2] | bad[3]) v = __builtin_nanf("");
+    scale[0] = v;
+  }
+}
+
+// out[m][n] = scale[0] * src[m][n] for n < N, 0 in the padding columns [N, ld_out): the logits from the raw cosines
+// (:368, the NEW scale times the unclamped cosine) and gcos from g (the scale is a constant of the graph).  One wave per
+// row, four rows per workgroup, 1024 columns per block as the margin walkers; src is read as f32x4 where its pitch allows.
+__global__ __launch_bounds__(256) void adacos_apply_kernel(const float* __restrict__ src, const float* __restrict__ scale,
+                                                           float* __restrict__ out, int rows, int N, int ld_src,
+                                                           int ld_out) {
+  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int lane = threadIdx.x & 63;
+  const float s = scale[0];
+  const float* srow = src + (size_t)row * ld_src;
+  float* orow = out + (size_t)row * ld_out;
+  const bool vec = ld_src % 4 == 0;
+  const int end = min(ld_out, (int)(blockIdx.x + 1) * MARGIN_COLS);
+  for (int n = blockIdx.x * MARGIN_COLS + lane * 4; n < end; n += 256) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (vec) {
+      if (n < ld_src) v = *reinterpret_cast<const f32x4*>(srow + n);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (n + j < N) v[j] = srow[n + j];
+    }
+    f32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = n + j < N ? __fmul_rn(s, v[j]) : 0.f;
+    *reinterpret_cast<f32x4*>(orow + n) = o;
+  }
+}
+
 // ------------------------------------------------------------------------------------------ cross entropy rows
 __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ z, const long long* __restrict__ label,
                                                       float* __restrict__ lse, float* __restrict__ ce,
@@ -904,6 +1036,30 @@ extern "C" int fr_magface_bwd(const float* g, const float* glossg, const float* 
   hipLaunchKernelGGL(magface_bwd_kernel, dim3(fr_margin_apply_parts(ldg), (rows + 3) / 4), dim3(256), 0,
                      (hipStream_t)stream, g, glossg, cos, (const long long*)label, rowv, gcos, r, rows, N, ld, ldg, s,
                      (u_margin - l_margin) / (u_a - l_a), 1.0 / ((double)u_a * u_a), lamda);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_adacos_rows(const float* cos, const int64_t* label, const float* scale, float* rowv, int rows, int N,
+                              int ld, void* stream) {
+  if (rows <= 0 || N <= 0 || ld < N || ld % 4) FR_UNSUPPORTED("fr_adacos_rows: shape (rows > 0, ld >= N > 0, ld a multiple of 4)");
+  hipLaunchKernelGGL(adacos_rows_kernel, dim3(rows), dim3(ADACOS_ROW_THREADS), 0, (hipStream_t)stream, cos, (const long long*)label, scale,
+                     rowv, rows, N, ld);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_adacos_scale(const float* rowv, int rows, float* scale, void* stream) {
+  if (rows < 0) FR_UNSUPPORTED("fr_adacos_scale: rows >= 0");
+  if (rows == 0) return 0;  // no rows: the scale stays, nothing to launch
+  hipLaunchKernelGGL(adacos_scale_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, rowv, rows, scale);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_adacos_apply(const float* src, const float* scale, float* out, int rows, int N, int ld_src, int ld_out,
+                               void* stream) {
+  if (rows <= 0 || N <= 0 || ld_src < N || ld_out < N || ld_out % 4)
+    FR_UNSUPPORTED("fr_adacos_apply: shape (ld_src >= N, ld_out >= N and a multiple of 4)");
+  hipLaunchKernelGGL(adacos_apply_kernel, dim3(fr_margin_apply_parts(ld_out), (rows + 3) / 4), dim3(256), 0,
+                     (hipStream_t)stream, src, scale, out, rows, N, ld_src, ld_out);
   FR_LAUNCH_CHECK();
 }
 

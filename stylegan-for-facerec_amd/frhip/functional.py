@@ -27,15 +27,16 @@ def _pad(n, m):
     return (n + m - 1) // m * m
 
 
-# One cosine-head pipeline under the five heads.  Forward: ``_cosine_operands`` (normalised operands), the cosine GEMM
+# One cosine-head pipeline under the heads.  Forward: ``_cosine_operands`` (normalised operands), the cosine GEMM
 # (``_raw_cosines``, or ArcFace / CosFace's fused margin epilogue), the head's row kernels.  Backward: the head's gcos
 # kernel, then ``_cosine_backward`` (both GEMMs and the normalisation backwards).
-ARCFACE, COSFACE, SPHEREFACE, AM_SOFTMAX, CURRICULAR, MAGFACE = range(6)  # 0..3 are the margin kinds of the kernels
+ARCFACE, COSFACE, SPHEREFACE, AM_SOFTMAX, CURRICULAR, MAGFACE, ADACOS = range(7)  # 0..3 are the margin kinds of the kernels
 
 # What a forward call keeps for its backward call; a head leaves what it does not use at None.  xn / wn [Np, D] / wt
 # [D, Np] are the GEMM operands (xn is x itself for Am_softmax), inv_x / inv_w the reciprocal norms, cos_t the target
 # cosines of the fused epilogue, cos the raw cosines [B, ld], rowv and t CurricularFace's row values and the t it used
-# (rowv: MagFace's six row values too).  HeadCfg.mag: MagFace's (margin_am, l_a, u_a, l_margin, u_margin, lamda).
+# (rowv: MagFace's six row values too; t: the scale an AdaCos call used).  HeadCfg.mag: MagFace's (margin_am, l_a, u_a,
+# l_margin, u_margin, lamda).
 HeadSaved = collections.namedtuple("HeadSaved", "x w label xn wn wt inv_x inv_w cos_t cos rowv t", defaults=(None,) * 12)
 HeadCfg = collections.namedtuple("HeadCfg", "kind Np ld s cos_m sin_m th easy mi p0 p1 mag", defaults=(None,) * 9)
 
@@ -276,9 +277,45 @@ def magface_backward(saved, cfg, g, glossg, need_x, need_w):
     return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, "radial", col_weight=True, r_part=r.view(B, 1))
 
 
+def adacos_forward(x, weight, label, scale, group=None):
+    """AdaCos logits (head/metrics.py:351-369) for fp32 device tensors; ``weight`` is [N, D], ``scale`` the module's
+    one-float device buffer.  It is read and written by kernels only, through its pointer (no host read): the row kernel
+    takes the row sums of exp(scale_old * cos) and the target cosines, the scale kernel moves the buffer in place, and the
+    logits are the NEW scale times the unclamped cosines.  ``group``: every rank all-gathers the [2, B] row values and
+    reduces the gathered rows in rank order, so every rank holds the bits of the scale of one head over the concatenated
+    batch (equal batch sizes on every rank).  Returns (logits, saved, cfg) for ``adacos_backward``."""
+    sv, N, Np, ld = _cosine_operands(x, weight, label, norm_x=True, col_weight=False)
+    B = x.shape[0]
+    st = ops.current_stream_ptr()
+    cos = _raw_cosines(sv, N, ld)
+    rowv = torch.empty(2, B, device=x.device)  # sum of exp(scale * cos) off the label column, raw target cosine
+    ops.call("fr_adacos_rows", cos, sv.label, scale, rowv, B, N, ld, st)()
+    rows = B
+    if group is not None:
+        import torch.distributed as dist
+        world = dist.get_world_size(group)
+        every = torch.empty(world, 2, B, device=x.device)
+        dist.all_gather_into_tensor(every, rowv, group=group)
+        rowv, rows = every.permute(1, 0, 2).reshape(2, world * B), world * B  # [2][world * B], ranks in order
+    ops.call("fr_adacos_scale", rowv, rows, scale, st)()
+    store, logits = _logit_store(sv, N, ld)
+    ops.call("fr_adacos_apply", cos, scale, store, B, N, ld, ld, st)()
+    # the backward pass needs the scale this forward call used: the buffer moves on with the next call
+    return logits, sv._replace(cos=cos, t=scale.clone()), HeadCfg(ADACOS, Np, ld)
+
+
+def adacos_backward(saved, cfg, g, need_x, need_w, raw_x_grad=False):
+    """(gx, gweight) of ``adacos_forward``: the scale is a constant of the graph and the cosines are not clamped, so gcos =
+    scale_used * g (columns N .. Np zero).  ``raw_x_grad``: as in ``margin_backward``."""
+    B, N = saved.x.shape[0], saved.inv_w.shape[0]
+    gcos = torch.empty(B, cfg.Np, device=saved.x.device)
+    ops.call("fr_adacos_apply", g.contiguous().float(), saved.t, gcos, B, N, N, cfg.Np, ops.current_stream_ptr())()
+    return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, None if raw_x_grad else "normalize", col_weight=False)
+
+
 def _head_fn(name, fwd, bwd, doc):
     """The autograd.Function of a head from its forward / backward pair; it takes the forward function's arguments (x,
-    weight, label and four head-specific values)."""
+    weight, label and up to four head-specific values)."""
 
     def forward(ctx, x, weight, label, *args):
         logits, saved, cfg = fwd(x, weight, label, *args)
@@ -328,6 +365,9 @@ MarginExtHeadFn = _head_fn("MarginExtHeadFn", margin_ext_forward, margin_ext_bac
 CurricularHeadFn = _head_fn("CurricularHeadFn", curricular_forward, curricular_backward, """
     CurricularFace (head/metrics.py:475-510) on the HIP path; see ``curricular_forward``.""")
 
+AdaCosHeadFn = _head_fn("AdaCosHeadFn", adacos_forward, adacos_backward, """
+    AdaCos (head/metrics.py:336-369) on the HIP path; see ``adacos_forward``.""")
+
 MagFaceHeadFn = _head_fn2("MagFaceHeadFn", magface_forward, magface_backward, """
     MagFace (head/metrics.py:512-553) on the HIP path: (logits, loss_g); see ``magface_forward``.""")
 
@@ -340,13 +380,15 @@ def _check_labels(label, n):
 
 
 def _head_entry(fn, n, x, weight, label, *args, t=None):
-    """What every head does around its Function: empty batch, label check, CurricularFace's ``t``."""
+    """What every head does around its Function: empty batch, label check, the one-float device buffer ``t`` of a head
+    that has one (CurricularFace's ``t``, AdaCos's ``scale``)."""
     if x.shape[0] == 0:  # the reference returns empty logits (F.linear / scatter_ on zero rows); nothing to launch
         ops.ptr(x)  # host tensors still fail loudly
         return x.new_zeros((0, n), dtype=torch.float32) + 0.0 * (x.sum() + weight.sum())
     _check_labels(label, n)
     if t is not None and (t.dtype != torch.float32 or t.numel() != 1 or t.device != x.device or not t.is_contiguous()):
-        raise ValueError("curricular_head: t must be a contiguous float32 tensor of one element on %s" % (x.device,))
+        raise ValueError("%s: %s must be a contiguous float32 tensor of one element on %s"
+                         % ((("adacos_head", "scale") if fn is AdaCosHeadFn else ("curricular_head", "t")) + (x.device,)))
     return fn.apply(x, weight, label, *args)
 
 
@@ -364,6 +406,12 @@ def curricular_head(x, kernel, label, t, s, m, group=None):
     """CurricularFace logits; the empty batch and label check of ``margin_head``.  ``t`` (float32 [1] on x's device) is
     updated in place; an empty batch leaves it as it is (the reference's mean over no rows turns it into NaN for good)."""
     return _head_entry(CurricularHeadFn, kernel.shape[1], x, kernel, label, t, s, m, group, t=t)
+
+
+def adacos_head(x, W, label, scale, group=None):
+    """AdaCos logits; the empty batch and label check of ``margin_head``.  ``scale`` (float32 [1] on x's device) is updated
+    in place on every call; an empty batch leaves it as it is (the reference divides by zero rows there)."""
+    return _head_entry(AdaCosHeadFn, W.shape[0], x, W, label, scale, group, t=scale)
 
 
 def magface_head(x, kernel, label, s, margin_am, l_a, u_a, l_margin, u_margin, lamda):

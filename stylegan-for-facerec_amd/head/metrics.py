@@ -1,11 +1,11 @@
 """Margin-softmax heads with the reference's import path, constructor signatures and state-dict keys.
 
     from head.metrics import ArcFace, CosFace, SphereFace, Am_softmax        (reference train.py:9)
-    from head.metrics import CurricularFace, MagFace                         (reference head/metrics.py:475, :512)
+    from head.metrics import CurricularFace, MagFace, AdaCos                 (reference head/metrics.py:475, :512, :336)
 
-The four heads the reference driver can select (``HEAD_NAME``, train.py:56,178-182) and ``CurricularFace`` / ``MagFace``
-(two of the FaceX-Zoo heads of the reference's head/metrics.py that its driver never names; train.py here accepts them) run
-on the HIP kernels when their input is a device tensor:
+The four heads the reference driver can select (``HEAD_NAME``, train.py:56,178-182) and ``CurricularFace`` / ``MagFace`` /
+``AdaCos`` (three of the FaceX-Zoo heads of the reference's head/metrics.py that its driver never names; train.py here
+accepts them) run on the HIP kernels when their input is a device tensor:
   * ``ArcFace`` / ``CosFace`` (the two heads the shipped configs and BASELINE.json name): row normalise -> MFMA cosine
     GEMM with the margin / label-select / scale epilogue -> closed-form backward;
   * ``SphereFace`` / ``Am_softmax``: the same cosine GEMM stores the raw cosines, a row kernel applies the clamp and the
@@ -19,11 +19,16 @@ on the HIP kernels when their input is a device tensor:
   * ``MagFace``: rows and ``weight`` columns normalised, raw cosines from the same GEMM; a row kernel turns each embedding's
     norm into its clamped magnitude a, the margin m(a) (cos, sin, cos(pi - m)), the regulariser ``loss_g`` and the clamp's
     mask; a row kernel applies the per-row margin on the label column.  It returns ``(logits, lamda * loss_g)``.  The
-    backward pass adds a radial term r * xhat to the feature gradient: the margin and ``loss_g`` both depend on ||x||.
-On host tensors ``SphereFace`` / ``Am_softmax`` / ``CurricularFace`` / ``MagFace`` run the reference's plain-PyTorch arithmetic (the
+    backward pass adds a radial term r * xhat to the feature gradient: the margin and ``loss_g`` both depend on ||x||;
+  * ``AdaCos``: rows of x and of ``W`` normalised, raw cosines from the same GEMM; no margin and no hyper-parameter.  A row
+    kernel takes each row's sum of exp(scale * cos) off its label column and its target cosine, one workgroup turns them
+    into B_avg and the lower median of the target angles and moves the buffer ``scale`` on the device (no host read in the
+    step), and a row kernel multiplies the unclamped cosines by the new scale; the backward pass treats it as a constant.
+On host tensors ``SphereFace`` / ``Am_softmax`` / ``CurricularFace`` / ``MagFace`` / ``AdaCos`` run the reference's plain-PyTorch arithmetic (the
 restatement the tests compare with); ``ArcFace`` / ``CosFace`` refuse host tensors.  ``SphereFace.iter`` counts forward
 calls on either path, as in the reference; train.py carries it across a resume in the State_* file.  ``CurricularFace.t``
-is a buffer: the Head_* file carries it.
+is a buffer: the Head_* file carries it.  ``AdaCos.scale`` is a non-persistent buffer (the reference's Head_* files have the
+key ``W`` alone): train.py carries it in the State_* file.
 
 Differences from the reference that a caller can observe:
   * ``device_id`` is accepted for signature compatibility but the class-dimension ``.cuda(i)`` split of
@@ -39,6 +44,12 @@ Differences from the reference that a caller can observe:
   * ``MagFace`` on the device path: the same two limits (no eps on the ``weight`` columns, a target cosine of exactly +-1).
     The label select is a ``where`` on the label column, so negatives at a cosine of exactly +-1 get a finite gradient
     (the reference's sqrt(1 - c^2) over the whole matrix makes theirs NaN).
+  * ``AdaCos.scale`` is a one-element float tensor (a non-persistent buffer) from construction on; the reference starts
+    with a Python float and turns it into a 0-dim tensor on the first call.  ``float(head.scale)`` works on both.  ``.double()``
+    converts the fp32 initial value, so a float64 copy starts 3e-8 (relative) from the reference's.  An empty
+    batch leaves ``scale`` as it is, where the reference divides by zero rows.  Limits as in the reference: a ``W`` row of
+    norm below 1e-12 is out of contract, ``scale * cos`` above about 88 overflows exp in fp32, and ``num_classes < 3`` is
+    degenerate (the initial scale is 0 or -inf).
 """
 import math
 
@@ -235,3 +246,52 @@ class MagFace(nn.Module):
         ctm = tl * torch.cos(m) - torch.sqrt(1.0 - torch.pow(tl, 2)) * torch.sin(m)  # cos(theta_target + m(a))
         final = torch.where(tl > torch.cos(math.pi - m), ctm, tl - self.margin_am)
         return c.scatter(1, at, final) * self.scale, self.lamda * loss_g
+
+
+class AdaCos(nn.Module):
+    """AdaCos (reference head/metrics.py:336-369): HIP kernels on device tensors, plain PyTorch on the host.
+
+    No margin and no hyper-parameter: ``scale <- log(B_avg) / cos(min(pi/4, median(theta_target)))`` with ``B_avg = (1/B)
+    sum_i sum_{j != y_i} exp(scale_old * cos_ij)`` on every forward call -- training mode, eval mode and under no_grad, as in
+    the reference -- and the logits are the new scale times the unclamped cosines.  ``torch.median`` of an even count is the
+    LOWER of the two middle values.  ``scale`` is a non-persistent one-float buffer: it follows ``.to()`` / ``.double()``
+    and stays out of the state dict, whose only key is ``W``.
+    ``process_group``: as on ``CurricularFace``, set it to the ranks' group and the statistics are those of one head over the
+    concatenated batch of all ranks (B_avg over world * B rows, the median over all ranks' target angles): each rank
+    all-gathers a [2, B] tensor of per-row sums and target cosines and reduces the gathered rows in rank order, so every rank
+    holds the same bits.  That takes equal batch sizes on every rank (DROP_LAST).
+    Limits, none worked around: a ``W`` row of norm below 1e-12 is out of contract; ``scale_old * cos`` above about 88
+    overflows exp in fp32, exactly as in the reference; ``num_classes < 3`` is degenerate (the initial scale is 0 or -inf);
+    an empty batch, or (device path) one in which no row has a label in [0, N), leaves ``scale`` unchanged where the
+    reference raises or produces NaN."""
+
+    def __init__(self, feat_dim, num_classes):
+        super().__init__()
+        s0 = math.sqrt(2) * math.log(num_classes - 1) if num_classes > 1 else float("-inf")
+        self.register_buffer("scale", torch.full((1,), s0), persistent=False)
+        self.W = Parameter(torch.empty(num_classes, feat_dim))
+        nn.init.xavier_uniform_(self.W)
+        self.process_group = None
+
+    def forward(self, feats, labels):
+        if feats.is_cuda:
+            _beside(self, self.W, feats)
+            return FRF.adacos_head(feats, self.W, labels.to(feats.device), self.scale, self.process_group)
+        logits = F.linear(F.normalize(feats), F.normalize(self.W.to(feats.device)))
+        if logits.shape[0]:
+            with torch.no_grad():
+                one_hot = torch.zeros_like(logits).scatter_(1, labels.view(-1, 1).long(), 1)
+                e = torch.where(one_hot < 1, torch.exp(self.scale * logits), torch.zeros_like(logits))
+                tc = logits[one_hot == 1]
+                if self.process_group is None:
+                    b_avg = torch.sum(e) / logits.size(0)
+                else:  # one head over the concatenated batch: gather (row sums, target cosines), reduce in rank order
+                    mine = torch.stack([e.sum(1), tc])
+                    every = [torch.empty_like(mine) for _ in range(dist.get_world_size(self.process_group))]
+                    dist.all_gather(every, mine, group=self.process_group)
+                    every = torch.cat(every, 1)
+                    b_avg, tc = torch.sum(every[0]) / every.shape[1], every[1]
+                theta_med = torch.median(torch.acos(torch.clamp(tc, -1.0 + 1e-7, 1.0 - 1e-7)))
+                new = torch.log(b_avg) / torch.cos(torch.min(math.pi / 4 * torch.ones_like(theta_med), theta_med))
+                self.scale = new.to(self.scale.dtype).view(1)
+        return self.scale * logits

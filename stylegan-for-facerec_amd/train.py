@@ -35,7 +35,7 @@ from frhip import functional as FRF
 from frhip import set_compute_dtype
 from frhip.optim import SGD, Adam
 from frhip.parallel import DataParallel
-from head.metrics import Am_softmax, ArcFace, CosFace, CurricularFace, MagFace, SphereFace
+from head.metrics import AdaCos, Am_softmax, ArcFace, CosFace, CurricularFace, MagFace, SphereFace
 from loss.focal import FocalLoss
 from util.utils import (AverageMeter, accuracy, buffer_val, collate_fn_ignore_none, get_time, get_val_data, perform_val,
                         schedule_lr, separate_irse_bn_paras, warm_up_lr)
@@ -126,6 +126,10 @@ def check_head_config(cfg):
         raise NotImplementedError("SHARDED_HEAD=True with HEAD_NAME 'MagFace': the class-sharded head does not serve MagFace "
                                   "(its radial term and loss_g need an exchange of their own); run it replicated, "
                                   "SHARDED_HEAD=False")
+    if cfg.get("SHARDED_HEAD", False) and cfg["HEAD_NAME"] == "AdaCos":
+        raise NotImplementedError("SHARDED_HEAD=True with HEAD_NAME 'AdaCos': the class-sharded head does not serve AdaCos "
+                                  "(its row sums and target cosines need an exchange of their own); run it replicated, "
+                                  "SHARDED_HEAD=False")
 
 
 def main():
@@ -198,10 +202,12 @@ def main():
              "CurricularFace": CurricularFace(emb, num_class, s=s)}
     with torch.random.fork_rng(devices=[]):  # built last and off the generator: the five above keep their initial weights
         heads["MagFace"] = MagFace(emb, num_class)  # and what is drawn after them; the reference's own scale (32)
+        heads["AdaCos"] = AdaCos(emb, num_class)  # after MagFace, which keeps its initial weights too
     head = heads[cfg["HEAD_NAME"]]
     if world > 1 and hasattr(head, "process_group") and not cfg.get("SHARDED_HEAD", False):
         # replicated CurricularFace: t follows the mean target cosine of the GLOBAL batch, as under the reference's
-        # nn.DataParallel (equal per-rank batch sizes: DROP_LAST).  The class-sharded head sees the global batch itself.
+        # nn.DataParallel (equal per-rank batch sizes: DROP_LAST); replicated AdaCos: its scale follows B_avg and the median
+        # target angle of the global batch in the same way.  The class-sharded head sees the global batch itself.
         head.process_group = dist.group.WORLD
     bn_params, other_params = separate_irse_bn_paras(backbone)
     _, head_params = separate_irse_bn_paras(head)
@@ -264,6 +270,8 @@ def main():
             head.iter = int(state["head_iter"])
             if crit is not None:
                 crit.iter = head.iter
+        if "head_scale" in state and cfg["HEAD_NAME"] == "AdaCos":  # AdaCos's scale: not in the Head_* file (key W alone)
+            head.scale.fill_(float(state["head_scale"]))
         if "torch_rng" in state:
             torch.set_rng_state(state["torch_rng"])
             n = state["numpy_rng"]
@@ -280,6 +288,8 @@ def main():
     for epoch in range(start_epoch, cfg["NUM_EPOCH"]):
         epoch_first_batch = batch
         epoch_first_iter = getattr(crit if crit is not None else head, "iter", None)
+        # AdaCos: the scale at the epoch's first batch, a device clone; the host reads it only when the checkpoint is written
+        epoch_first_scale = head.scale.clone() if cfg["HEAD_NAME"] == "AdaCos" else None
         if epoch in cfg["STAGES"] and epoch != lr_stage_done:
             schedule_lr(optimizer)
         backbone.train()
@@ -399,6 +409,8 @@ def main():
                          "numpy_rng": _np_state_plain(np.random.get_state())}
             if epoch_first_iter is not None:  # the head's forward counter (SphereFace: lambda), at the same point as "batch"
                 run_state["head_iter"] = int(head.iter if finished else epoch_first_iter)
+            if epoch_first_scale is not None:  # AdaCos's scale, at the same point as "batch" (the exact fp32 value)
+                run_state["head_scale"] = float(head.scale if finished else epoch_first_scale)
             torch.save(run_state, os.path.join(root, "State_{}_{}".format(cfg["HEAD_NAME"], tag)))
         if args.max_steps and batch >= args.max_steps:
             break
