@@ -623,6 +623,27 @@ int fr_adacos_scale(const float* rowv, int rows, float* scale, void* stream);
  * forward call used: it is a constant of the graph (:362 no_grad), so d out / d cos = scale everywhere. */
 int fr_adacos_apply(const float* src, const float* scale, float* out, int rows, int N, int ld_src, int ld_out, void* stream);
 
+/* ---- NPCFace (head/metrics.py:592-636) on the raw cosines cos [rows][ld] of the FR_EPI_STORE GEMM between
+ *      fr_row_normalize'd embeddings and the fr_col_normalize'd kernel.  The head has no state besides its kernel. */
+/* per-row values (:616-632), rowv [6][rows]:  gt = clamp(cos[m][label[m]], -1, 1);  ctm = gt*cos_m - sqrt(1 - gt^2)*sin_m;
+ * final = gt > 0 ? gt*cos(newm) - sqrt(1 - gt^2)*sin(newm) : gt with newm = m0 + m1*avg;  d final / d gt =
+ * cos(newm) + sin(newm)*gt/sqrt(1 - gt^2) where gt > 0, else 1;  avg = (sum of the clamped cosines c[m][n] > ctm over
+ * n < N, n != label[m]) / max(count, 1);  count = the number of those columns, as a float (exact up to 2^24).  The sum is
+ * added in a fixed order (per-thread sums in double over ascending columns, the wave's xor butterfly, the sixteen waves of
+ * the row's workgroup in order), no atomics.  A row whose label lies outside [0, N) has no target: gt = 0, ctm = +inf, so
+ * count = 0 and nothing in it is hard.  ld a multiple of 4. */
+int fr_npcface_rows(const float* cos, const int64_t* label, float* rowv, int rows, int N, int ld, float cos_m, float sin_m,
+                    float m0, float m1, void* stream);
+/* out[m][n] = s * (n == label[m] ? final[m] : (c > ctm[m] ? t*c + a : c)), c the clamped cosine  (:632-635); ld a multiple
+ * of 4, columns N..ld of out are written as 0.  A label outside [0, N) selects nothing. */
+int fr_npcface_apply(const float* cos, const int64_t* label, const float* rowv, float* out, int rows, int N, int ld, float t,
+                     float a, float s, void* stream);
+/* gcos[m][n] = g[m][n] * d out / d cos with newm, the hard mask and the branch constant (:621 no_grad): s*t on hard
+ * negatives, s on easy ones, s * (d final / d gt)[m] on the label column; 0 where the clamp saturated (the closed interval
+ * passes) and in the padding columns N..ldg.  g is [rows][N] contiguous. */
+int fr_npcface_bwd(const float* g, const float* cos, const int64_t* label, const float* rowv, float* gcos, int rows, int N,
+                   int ld, int ldg, float t, float s, void* stream);
+
 /* ---- focal loss on the batch-mean cross entropy (loss/focal.py:17-21) + top-k (util/utils.py:343-358) */
 /* per row: lse[m], ce[m] = lse - z[label], rank[m] = #{n: z[n] > z[label]} */
 int fr_ce_rows(const float* logits, const int64_t* label, float* lse, float* ce, int32_t* rank, int rows, int N,

@@ -639,6 +639,106 @@ __global__ __launch_bounds__(256) void adacos_apply_kernel(const float* __restri
   }
 }
 
+// ------------------------------------------------------------------------------------------ NPCFace
+// head/metrics.py:616-635 on the raw cosines of the FR_EPI_STORE GEMM.  rowv is [6][rows]: gt = clamp(cos[label]),
+// ctm = cos(theta_gt + margin), final (the label column's value), d final / d gt, avg (the mean of the row's hard
+// negatives) and their count as a float (exact up to 2^24).  A row whose label lies outside [0, N) has no target: gt counts
+// as 0 and ctm is +inf, so nothing in it is hard.
+
+// One workgroup of 1024 threads per row, as adacos_rows_kernel (a whole-row reduction).  Order of the sum, fixed: thread t
+// adds the hard cosines among its columns 4t .. 4t+3, 4t+4096 .. in ascending order in double, the 64 lanes of a wave go
+// through wave_sum_d's xor butterfly, and thread 0 adds the sixteen waves' sums in wave order.  The count is an integer.
+constexpr int NPCFACE_ROW_THREADS = 1024;
+
+__global__ __launch_bounds__(NPCFACE_ROW_THREADS) void npcface_rows_kernel(const float* __restrict__ cos,
+                                                                           const long long* __restrict__ label,
+                                                                           float* __restrict__ rowv, int rows, int N, int ld,
+                                                                           float cos_m, float sin_m, float m0, float m1) {
+  __shared__ double dred[NPCFACE_ROW_THREADS / 64];
+  __shared__ int nred[NPCFACE_ROW_THREADS / 64];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const long long lab = label[row];
+  const bool has = lab >= 0 && lab < N;
+  const float* crow = cos + (size_t)row * ld;
+  const float gt = has ? clamp1(crow[lab]) : 0.f;
+  const float sn = sqrtf(1.0f - gt * gt);
+  const float ctm = has ? gt * cos_m - sn * sin_m : __builtin_inff();
+  double acc = 0.0;
+  int cnt = 0;
+  for (int n = tid * 4; n < N; n += 4 * NPCFACE_ROW_THREADS) {  // n + 3 < ld: n < N <= ld, both multiples of 4
+    const f32x4 ch = *reinterpret_cast<const f32x4*>(crow + n);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float c = clamp1(ch[j]);
+      if (n + j < N && n + j != lab && c > ctm) {  // the label column is taken out of the mask (:623)
+        acc += (double)c;
+        ++cnt;
+      }
+    }
+  }
+  acc = wave_sum_d(acc);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+  if ((tid & 63) == 0) {
+    dred[tid >> 6] = acc;
+    nred[tid >> 6] = cnt;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double sum = 0.0;
+    int count = 0;
+    for (int w = 0; w < NPCFACE_ROW_THREADS / 64; ++w) {
+      sum += dred[w];
+      count += nred[w];
+    }
+    const float avg = (float)(sum / (double)max(count, 1));  // clamp(count, 1, num_class) (:627): count <= N - 1
+    const float newm = m0 + m1 * avg;
+    const float cn = cosf(newm), sm = sinf(newm);
+    const bool pos = gt > 0.f;
+    rowv[row] = gt;
+    rowv[rows + row] = ctm;
+    rowv[2 * rows + row] = pos ? gt * cn - sn * sm : gt;
+    rowv[3 * rows + row] = pos ? cn + sm * gt / sn : 1.f;
+    rowv[4 * rows + row] = avg;
+    rowv[5 * rows + row] = (float)count;
+  }
+}
+
+// out = s * (label ? final : (c > ctm ? t c + a : c)), c = clamp(cos)
+__global__ __launch_bounds__(256) void npcface_apply_kernel(const float* __restrict__ cos,
+                                                            const long long* __restrict__ label,
+                                                            const float* __restrict__ rowv, float* __restrict__ out,
+                                                            int rows, int N, int ld, float t, float a, float s) {
+  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const long long lab = label[row];
+  const float ctm = rowv[rows + row], fin = rowv[2 * rows + row];
+  margin_cols_fwd(cos, out, row, N, ld, [&](int n, float raw) {
+    const float c = clamp1(raw);
+    float v = c > ctm ? t * c + a : c;
+    if (n == lab) v = fin;
+    return v * s;
+  });
+}
+
+// gcos = g * d out / d cos with newm, the hard mask and the branch constant: s t on hard negatives, s on easy ones,
+// s * rowv[3] (cos(newm) + sin(newm) gt / sqrt(1 - gt^2), or 1) on the label column
+__global__ __launch_bounds__(256) void npcface_bwd_kernel(const float* __restrict__ g, const float* __restrict__ cos,
+                                                          const long long* __restrict__ label,
+                                                          const float* __restrict__ rowv, float* __restrict__ gcos, int rows,
+                                                          int N, int ld, int ldg, float t, float s) {
+  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const long long lab = label[row];
+  const float ctm = rowv[rows + row], dlab = rowv[3 * rows + row];
+  margin_cols_bwd(g, cos, gcos, row, N, ld, ldg, [&](int n, float raw, float gg) {
+    const float c = clamp1(raw);
+    float d = c > ctm ? t : 1.f;
+    if (n == lab) d = dlab;
+    return gg * s * d;
+  });
+}
+
 // ------------------------------------------------------------------------------------------ cross entropy rows
 __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ z, const long long* __restrict__ label,
                                                       float* __restrict__ lse, float* __restrict__ ce,
@@ -1060,6 +1160,31 @@ extern "C" int fr_adacos_apply(const float* src, const float* scale, float* out,
     FR_UNSUPPORTED("fr_adacos_apply: shape (ld_src >= N, ld_out >= N and a multiple of 4)");
   hipLaunchKernelGGL(adacos_apply_kernel, dim3(fr_margin_apply_parts(ld_out), (rows + 3) / 4), dim3(256), 0,
                      (hipStream_t)stream, src, scale, out, rows, N, ld_src, ld_out);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_npcface_rows(const float* cos, const int64_t* label, float* rowv, int rows, int N, int ld, float cos_m,
+                               float sin_m, float m0, float m1, void* stream) {
+  if (rows <= 0 || N <= 0 || ld < N || ld % 4) FR_UNSUPPORTED("fr_npcface_rows: shape (rows > 0, ld >= N > 0, ld a multiple of 4)");
+  hipLaunchKernelGGL(npcface_rows_kernel, dim3(rows), dim3(NPCFACE_ROW_THREADS), 0, (hipStream_t)stream, cos,
+                     (const long long*)label, rowv, rows, N, ld, cos_m, sin_m, m0, m1);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_npcface_apply(const float* cos, const int64_t* label, const float* rowv, float* out, int rows, int N,
+                                int ld, float t, float a, float s, void* stream) {
+  if (rows <= 0 || N <= 0 || ld < N || ld % 4) FR_UNSUPPORTED("fr_npcface_apply: shape (ld >= N, multiple of 4)");
+  hipLaunchKernelGGL(npcface_apply_kernel, dim3(fr_margin_apply_parts(ld), (rows + 3) / 4), dim3(256), 0,
+                     (hipStream_t)stream, cos, (const long long*)label, rowv, out, rows, N, ld, t, a, s);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_npcface_bwd(const float* g, const float* cos, const int64_t* label, const float* rowv, float* gcos,
+                              int rows, int N, int ld, int ldg, float t, float s, void* stream) {
+  if (rows <= 0 || N <= 0 || ld < N || ld % 4 || ldg < ld || ldg % 4)
+    FR_UNSUPPORTED("fr_npcface_bwd: shape (ldg >= ld >= N, multiples of 4)");
+  hipLaunchKernelGGL(npcface_bwd_kernel, dim3(fr_margin_apply_parts(ldg), (rows + 3) / 4), dim3(256), 0,
+                     (hipStream_t)stream, g, cos, (const long long*)label, rowv, gcos, rows, N, ld, ldg, t, s);
   FR_LAUNCH_CHECK();
 }
 

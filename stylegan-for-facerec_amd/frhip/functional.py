@@ -30,13 +30,13 @@ def _pad(n, m):
 # One cosine-head pipeline under the heads.  Forward: ``_cosine_operands`` (normalised operands), the cosine GEMM
 # (``_raw_cosines``, or ArcFace / CosFace's fused margin epilogue), the head's row kernels.  Backward: the head's gcos
 # kernel, then ``_cosine_backward`` (both GEMMs and the normalisation backwards).
-ARCFACE, COSFACE, SPHEREFACE, AM_SOFTMAX, CURRICULAR, MAGFACE, ADACOS = range(7)  # 0..3 are the margin kinds of the kernels
+ARCFACE, COSFACE, SPHEREFACE, AM_SOFTMAX, CURRICULAR, MAGFACE, ADACOS, NPCFACE = range(8)  # 0..3: the kernels' margin kinds
 
 # What a forward call keeps for its backward call; a head leaves what it does not use at None.  xn / wn [Np, D] / wt
 # [D, Np] are the GEMM operands (xn is x itself for Am_softmax), inv_x / inv_w the reciprocal norms, cos_t the target
 # cosines of the fused epilogue, cos the raw cosines [B, ld], rowv and t CurricularFace's row values and the t it used
-# (rowv: MagFace's six row values too; t: the scale an AdaCos call used).  HeadCfg.mag: MagFace's (margin_am, l_a, u_a,
-# l_margin, u_margin, lamda).
+# (rowv: MagFace's and NPCFace's six row values too; t: the scale an AdaCos call used).  HeadCfg.mag: MagFace's (margin_am,
+# l_a, u_a, l_margin, u_margin, lamda); HeadCfg.p0 / p1: NPCFace's t / a.
 HeadSaved = collections.namedtuple("HeadSaved", "x w label xn wn wt inv_x inv_w cos_t cos rowv t", defaults=(None,) * 12)
 HeadCfg = collections.namedtuple("HeadCfg", "kind Np ld s cos_m sin_m th easy mi p0 p1 mag", defaults=(None,) * 9)
 
@@ -313,6 +313,35 @@ def adacos_backward(saved, cfg, g, need_x, need_w, raw_x_grad=False):
     return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, None if raw_x_grad else "normalize", col_weight=False)
 
 
+def npcface_forward(x, kernel, label, s, npc):
+    """NPCFace logits (head/metrics.py:612-636) for fp32 device tensors; ``kernel`` is [D, N], ``npc`` the head's (cos_m,
+    sin_m, m0, m1, t, a), the attributes its forward pass reads.  A row kernel takes per row the target cosine,
+    cos(theta + m), the mean and the count of the hard negatives (the clamped cosines above cos(theta + m), label column
+    excluded; the sum in a fixed order) and from them the label column's value at the margin m0 + m1 * mean; a row kernel
+    re-weights the hard negatives to t * c + a.  Nothing waits on the host.  A label outside [0, N) selects nothing and
+    makes nothing hard in its row.  Returns (logits, saved, cfg) for ``npcface_backward``."""
+    sv, N, Np, ld = _cosine_operands(x, kernel, label, norm_x=True, col_weight=True)
+    B = x.shape[0]
+    st = ops.current_stream_ptr()
+    cos_m, sin_m, m0, m1, t, a = (float(v) for v in npc)
+    cos = _raw_cosines(sv, N, ld)
+    rowv = torch.empty(6, B, device=x.device)  # gt, ctm, final, d final / d gt, avg, count
+    ops.call("fr_npcface_rows", cos, sv.label, rowv, B, N, ld, cos_m, sin_m, m0, m1, st)()
+    store, logits = _logit_store(sv, N, ld)
+    ops.call("fr_npcface_apply", cos, sv.label, rowv, store, B, N, ld, t, a, float(s), st)()
+    return logits, sv._replace(cos=cos, rowv=rowv), HeadCfg(NPCFACE, Np, ld, s=float(s), p0=t, p1=a)
+
+
+def npcface_backward(saved, cfg, g, need_x, need_w, raw_x_grad=False):
+    """(gx, gkernel) of ``npcface_forward``; gkernel is [D, N].  The margin m0 + m1 * mean, the hard mask and the branch are
+    constants of the graph (:621 no_grad).  ``raw_x_grad``: as in ``margin_backward``."""
+    B, N = saved.x.shape[0], saved.inv_w.shape[0]
+    gcos = torch.empty(B, cfg.Np, device=saved.x.device)
+    ops.call("fr_npcface_bwd", g.contiguous().float(), saved.cos, saved.label, saved.rowv, gcos, B, N, cfg.ld, cfg.Np,
+             cfg.p0, cfg.s, ops.current_stream_ptr())()
+    return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, None if raw_x_grad else "normalize", col_weight=True)
+
+
 def _head_fn(name, fwd, bwd, doc):
     """The autograd.Function of a head from its forward / backward pair; it takes the forward function's arguments (x,
     weight, label and up to four head-specific values)."""
@@ -368,6 +397,9 @@ CurricularHeadFn = _head_fn("CurricularHeadFn", curricular_forward, curricular_b
 AdaCosHeadFn = _head_fn("AdaCosHeadFn", adacos_forward, adacos_backward, """
     AdaCos (head/metrics.py:336-369) on the HIP path; see ``adacos_forward``.""")
 
+NPCFaceHeadFn = _head_fn("NPCFaceHeadFn", npcface_forward, npcface_backward, """
+    NPCFace (head/metrics.py:592-636) on the HIP path; see ``npcface_forward``.""")
+
 MagFaceHeadFn = _head_fn2("MagFaceHeadFn", magface_forward, magface_backward, """
     MagFace (head/metrics.py:512-553) on the HIP path: (logits, loss_g); see ``magface_forward``.""")
 
@@ -412,6 +444,11 @@ def adacos_head(x, W, label, scale, group=None):
     """AdaCos logits; the empty batch and label check of ``margin_head``.  ``scale`` (float32 [1] on x's device) is updated
     in place on every call; an empty batch leaves it as it is (the reference divides by zero rows there)."""
     return _head_entry(AdaCosHeadFn, W.shape[0], x, W, label, scale, group, t=scale)
+
+
+def npcface_head(x, kernel, label, s, cos_m, sin_m, m0, m1, t, a):
+    """NPCFace logits; the empty batch and label check of ``margin_head``."""
+    return _head_entry(NPCFaceHeadFn, kernel.shape[1], x, kernel, label, s, (cos_m, sin_m, m0, m1, t, a))
 
 
 def magface_head(x, kernel, label, s, margin_am, l_a, u_a, l_margin, u_margin, lamda):

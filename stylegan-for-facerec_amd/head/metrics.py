@@ -1,11 +1,11 @@
 """Margin-softmax heads with the reference's import path, constructor signatures and state-dict keys.
 
     from head.metrics import ArcFace, CosFace, SphereFace, Am_softmax        (reference train.py:9)
-    from head.metrics import CurricularFace, MagFace, AdaCos                 (reference head/metrics.py:475, :512, :336)
+    from head.metrics import CurricularFace, MagFace, AdaCos, NPCFace        (reference head/metrics.py:475, :512, :336, :592)
 
 The four heads the reference driver can select (``HEAD_NAME``, train.py:56,178-182) and ``CurricularFace`` / ``MagFace`` /
-``AdaCos`` (three of the FaceX-Zoo heads of the reference's head/metrics.py that its driver never names; train.py here
-accepts them) run on the HIP kernels when their input is a device tensor:
+``AdaCos`` / ``NPCFace`` (four of the FaceX-Zoo heads of the reference's head/metrics.py that its driver never names; train.py
+here accepts them) run on the HIP kernels when their input is a device tensor:
   * ``ArcFace`` / ``CosFace`` (the two heads the shipped configs and BASELINE.json name): row normalise -> MFMA cosine
     GEMM with the margin / label-select / scale epilogue -> closed-form backward;
   * ``SphereFace`` / ``Am_softmax``: the same cosine GEMM stores the raw cosines, a row kernel applies the clamp and the
@@ -23,8 +23,13 @@ accepts them) run on the HIP kernels when their input is a device tensor:
   * ``AdaCos``: rows of x and of ``W`` normalised, raw cosines from the same GEMM; no margin and no hyper-parameter.  A row
     kernel takes each row's sum of exp(scale * cos) off its label column and its target cosine, one workgroup turns them
     into B_avg and the lower median of the target angles and moves the buffer ``scale`` on the device (no host read in the
-    step), and a row kernel multiplies the unclamped cosines by the new scale; the backward pass treats it as a constant.
-On host tensors ``SphereFace`` / ``Am_softmax`` / ``CurricularFace`` / ``MagFace`` / ``AdaCos`` run the reference's plain-PyTorch arithmetic (the
+    step), and a row kernel multiplies the unclamped cosines by the new scale; the backward pass treats it as a constant;
+  * ``NPCFace``: rows and ``kernel`` columns normalised, raw cosines from the same GEMM; one workgroup per row takes the
+    target cosine, cos(theta + margin) and, in one more pass over the row, the mean and the count of the hard negatives
+    (the cosines above cos(theta + margin), label column excluded; summed in a fixed order), and from them the label
+    column's value at the margin ``m0 + m1 * mean``; a row kernel re-weights the hard negatives to ``t * c + a``; the
+    backward pass treats that margin, the mask and the ``gt > 0`` branch as constants.  No state besides ``kernel``.
+On host tensors ``SphereFace`` / ``Am_softmax`` / ``CurricularFace`` / ``MagFace`` / ``AdaCos`` / ``NPCFace`` run the reference's plain-PyTorch arithmetic (the
 restatement the tests compare with); ``ArcFace`` / ``CosFace`` refuse host tensors.  ``SphereFace.iter`` counts forward
 calls on either path, as in the reference; train.py carries it across a resume in the State_* file.  ``CurricularFace.t``
 is a buffer: the Head_* file carries it.  ``AdaCos.scale`` is a non-persistent buffer (the reference's Head_* files have the
@@ -50,6 +55,10 @@ Differences from the reference that a caller can observe:
     batch leaves ``scale`` as it is, where the reference divides by zero rows.  Limits as in the reference: a ``W`` row of
     norm below 1e-12 is out of contract, ``scale * cos`` above about 88 overflows exp in fp32, and ``num_classes < 3`` is
     degenerate (the initial scale is 0 or -inf).
+  * ``NPCFace`` on the device path: the same two limits as ``CurricularFace`` (no eps on the ``kernel`` columns: a column of
+    norm below 1e-12 is out of contract; a target cosine of exactly +-1 makes the reference's own gradient infinite, and
+    nothing is done about it here either).  The reference builds its hard mask with ``.cuda()`` (:622) and so runs on no
+    other device; the host path here leaves that call out and is otherwise its arithmetic.
 """
 import math
 
@@ -295,3 +304,43 @@ class AdaCos(nn.Module):
                 new = torch.log(b_avg) / torch.cos(torch.min(math.pi / 4 * torch.ones_like(theta_med), theta_med))
                 self.scale = new.to(self.scale.dtype).view(1)
         return self.scale * logits
+
+
+class NPCFace(nn.Module):
+    """NPCFace (reference head/metrics.py:592-636): HIP kernels on device tensors, plain PyTorch on the host.
+
+    The margin on the label column follows the row's hard negatives: ``newm = m0 + m1 * mean(c | c > cos(theta + margin),
+    label column excluded)``, with the count clamped at 1, so a row without hard negatives gets ``m0``.  Hard negatives
+    become ``t * c + a``.  ``newm``, the mask and the ``gt > 0`` branch take no gradient.  The constants are plain
+    attributes read on every call (``cos_m`` / ``sin_m``, not ``margin``, as in the reference); the state dict holds the key
+    ``kernel`` alone.  Limits: see the module docstring (kernel columns of norm below 1e-12; target cosines of exactly +-1)."""
+
+    def __init__(self, feat_dim=512, num_class=86876, margin=0.5, scale=64):
+        super().__init__()
+        self.kernel = Parameter(torch.empty(feat_dim, num_class))
+        self.kernel.data.uniform_(-1, 1).renorm_(2, 1, 1e-5).mul_(1e5)
+        self.margin, self.scale = margin, scale
+        self.cos_m, self.sin_m = math.cos(margin), math.sin(margin)
+        self.m0, self.m1, self.t, self.a = 0.40, 0.20, 1.10, 0.20
+        self.cos_m0, self.sin_m0 = math.cos(self.m0), math.sin(self.m0)
+        self.num_class = num_class
+
+    def forward(self, x, label):
+        if x.is_cuda:
+            _beside(self, self.kernel, x)
+            return FRF.npcface_head(x, self.kernel, label.to(x.device), self.scale, self.cos_m, self.sin_m, self.m0,
+                                    self.m1, self.t, self.a)
+        kernel = self.kernel.to(x.device)
+        c = torch.mm(F.normalize(x), F.normalize(kernel, dim=0)).clamp(-1, 1)
+        at = label.view(-1, 1).long()
+        gt = c.gather(1, at)
+        sin_theta = torch.sqrt(1.0 - torch.pow(gt, 2))
+        ctm = gt * self.cos_m - sin_theta * self.sin_m  # cos(theta_target + margin)
+        with torch.no_grad():
+            hard = (c > ctm).to(c.dtype).scatter_(1, at, 0)
+            sum_hard = torch.where(hard > 0, c, torch.zeros_like(c)).sum(1, keepdim=True)
+            newm = self.m0 + self.m1 * (sum_hard / hard.sum(1, keepdim=True).clamp(1, self.num_class))
+            cos_newm, sin_newm = torch.cos(newm), torch.sin(newm)
+        final = torch.where(gt > 0, gt * cos_newm - sin_theta * sin_newm, gt)
+        out = torch.where(c > ctm, self.t * c + self.a, c).scatter(1, at, final)
+        return out * self.scale

@@ -35,7 +35,7 @@ from frhip import functional as FRF
 from frhip import set_compute_dtype
 from frhip.optim import SGD, Adam
 from frhip.parallel import DataParallel
-from head.metrics import AdaCos, Am_softmax, ArcFace, CosFace, CurricularFace, MagFace, SphereFace
+from head.metrics import AdaCos, Am_softmax, ArcFace, CosFace, CurricularFace, MagFace, NPCFace, SphereFace
 from loss.focal import FocalLoss
 from util.utils import (AverageMeter, accuracy, buffer_val, collate_fn_ignore_none, get_time, get_val_data, perform_val,
                         schedule_lr, separate_irse_bn_paras, warm_up_lr)
@@ -130,6 +130,10 @@ def check_head_config(cfg):
         raise NotImplementedError("SHARDED_HEAD=True with HEAD_NAME 'AdaCos': the class-sharded head does not serve AdaCos "
                                   "(its row sums and target cosines need an exchange of their own); run it replicated, "
                                   "SHARDED_HEAD=False")
+    if cfg.get("SHARDED_HEAD", False) and cfg["HEAD_NAME"] == "NPCFace":
+        raise NotImplementedError("SHARDED_HEAD=True with HEAD_NAME 'NPCFace': the class-sharded head does not serve NPCFace "
+                                  "(its target cosines and per-row hard sums and counts need an exchange of their own); run "
+                                  "it replicated, SHARDED_HEAD=False")
 
 
 def main():
@@ -203,6 +207,7 @@ def main():
     with torch.random.fork_rng(devices=[]):  # built last and off the generator: the five above keep their initial weights
         heads["MagFace"] = MagFace(emb, num_class)  # and what is drawn after them; the reference's own scale (32)
         heads["AdaCos"] = AdaCos(emb, num_class)  # after MagFace, which keeps its initial weights too
+        heads["NPCFace"] = NPCFace(emb, num_class, scale=s)  # after AdaCos, likewise
     head = heads[cfg["HEAD_NAME"]]
     if world > 1 and hasattr(head, "process_group") and not cfg.get("SHARDED_HEAD", False):
         # replicated CurricularFace: t follows the mean target cosine of the GLOBAL batch, as under the reference's

@@ -2,12 +2,12 @@
 calls (mode fwdbwd) after 3 warm-up calls, event-timed; run it under `rocprofv3 --kernel-trace --stats -- ...` for the
 kernel times (profiles/margin_heads_b256_n28000.txt).
 
-    python tools/head_time.py {ArcFace|CosFace|SphereFace|Am_softmax|CurricularFace|MagFace|AdaCos} {fwd|fwdbwd} ITERS
+    python tools/head_time.py {ArcFace|CosFace|SphereFace|Am_softmax|CurricularFace|MagFace|AdaCos|NPCFace} {fwd|fwdbwd} ITERS
 
 Several heads, comma separated, are timed in ONE process in alternating rounds (ROUNDS rounds of ITERS calls per head, the
 median round of each head reported, and the ratio to the first head named), so clocks and allocator state are shared
 (profiles/curricular_head_b256_n28000.txt, profiles/magface_head_b256_n28000.txt,
-profiles/adacos_head_b256_n28000.txt):
+profiles/adacos_head_b256_n28000.txt, profiles/npcface_head_b256_n28000.txt):
 
     python tools/head_time.py Am_softmax,ArcFace,CurricularFace fwdbwd ITERS [ROUNDS]
 
@@ -35,7 +35,8 @@ gg = torch.full((B, 1), 1.0 / B).cuda()
 
 def make(name):
     cls = getattr(H, name)
-    head = (cls(D, N) if name in ("CurricularFace", "MagFace", "AdaCos") else cls(D, N, None)).cuda()  # FaceX-Zoo heads: no device_id
+    zoo = name in ("CurricularFace", "MagFace", "AdaCos", "NPCFace")  # FaceX-Zoo heads: no device_id
+    head = (cls(D, N) if zoo else cls(D, N, None)).cuda()
     p = list(head.parameters())[0]
 
     def step():
