@@ -644,6 +644,24 @@ int fr_npcface_apply(const float* cos, const int64_t* label, const float* rowv, 
 int fr_npcface_bwd(const float* g, const float* cos, const int64_t* label, const float* rowv, float* gcos, int rows, int N,
                    int ld, int ldg, float t, float s, void* stream);
 
+/* ---- MV_Softmax (head/metrics.py:555-590) on the raw cosines cos [rows][ld] of the FR_EPI_STORE GEMM between
+ *      fr_row_normalize'd embeddings and the fr_col_normalize'd weight.  The head never clamps its cosines (a raw cosine of
+ *      1 + 2^-23 keeps its value and its gradient) and has no state besides its weight. */
+/* replaces :576-589.  Per row (every wave derives them from one load of the target cosine; the wave of column chunk 0
+ * stores them), rowv [4][rows]:  gt = cos[m][label[m]];  is_am != 0 (:578-579, p0 = margin, p1 unused): thr = gt - p0,
+ * final = gt > p0 ? gt - p0 : gt, d final / d gt = 1;  is_am == 0 (:581-584, p0 = cos_m, p1 = sin_m): thr = gt*p0 -
+ * sqrt(1 - gt^2)*p1, final = gt > 0 ? thr : gt, d final / d gt = gt > 0 ? p0 + p1*gt/sqrt(1 - gt^2) : 1, unguarded: |gt| > 1
+ * makes thr NaN and no column of the row hard.  out[m][n] = s * (n == label[m] ? final[m] : (c > thr[m] ? w*c + w - 1 : c))
+ * with c the raw cosine (:586-589); ld a multiple of 4, columns N..ld of out are written as 0.  A row whose label lies
+ * outside [0, N) has no target: rowv = 0, +inf, 0, 0, nothing in it is hard and no column is selected. */
+int fr_mv_softmax_apply(const float* cos, const int64_t* label, float* rowv, float* out, int rows, int N, int ld, int is_am,
+                        float p0, float p1, float w, float s, void* stream);
+/* the backward of :576-589 with the hard mask and the branch constant (comparisons take no gradient): gcos[m][n] = g[m][n] *
+ * (s*w on hard negatives, s on easy ones, s * (d final / d gt)[m] on the label column), whatever the raw cosine (no clamp,
+ * no pass mask); 0 in the padding columns N..ldg.  g is [rows][N] contiguous, rowv as fr_mv_softmax_apply left it. */
+int fr_mv_softmax_bwd(const float* g, const float* cos, const int64_t* label, const float* rowv, float* gcos, int rows, int N,
+                      int ld, int ldg, float w, float s, void* stream);
+
 /* ---- focal loss on the batch-mean cross entropy (loss/focal.py:17-21) + top-k (util/utils.py:343-358) */
 /* per row: lse[m], ce[m] = lse - z[label], rank[m] = #{n: z[n] > z[label]} */
 int fr_ce_rows(const float* logits, const int64_t* label, float* lse, float* ce, int32_t* rank, int rows, int N,

@@ -148,8 +148,9 @@ __device__ __forceinline__ void margin_cols_fwd(const float* __restrict__ cos, f
 }
 
 // Backward walker of one row: gcos[n] = body(n, raw cosine, g[n]) where the clamp passes gradient (torch.clamp: the closed
-// interval), 0 where it saturated and in the padding columns [N, ldg).  cos has the pitch ld <= ldg.
-template <typename Body>
+// interval), 0 where it saturated and in the padding columns [N, ldg).  cos has the pitch ld <= ldg.  kPassMask = false is
+// for a head that never clamps (MV_Softmax): every column n < N gets body's value, whatever its raw cosine.
+template <bool kPassMask = true, typename Body>
 __device__ __forceinline__ void margin_cols_bwd(const float* __restrict__ g, const float* __restrict__ cos,
                                                 float* __restrict__ gcos, int row, int N, int ld, int ldg, Body body) {
   const int lane = threadIdx.x & 63;
@@ -166,7 +167,7 @@ __device__ __forceinline__ void margin_cols_bwd(const float* __restrict__ g, con
       float v = 0.f;
       if (n + j < N) {
         const float gg = grow[n + j];
-        const bool pass = ch[j] >= -1.f && ch[j] <= 1.f;
+        const bool pass = !kPassMask || (ch[j] >= -1.f && ch[j] <= 1.f);
         const float d = body(n + j, ch[j], gg);
         v = pass ? d : 0.f;
       }
@@ -739,6 +740,78 @@ __global__ __launch_bounds__(256) void npcface_bwd_kernel(const float* __restric
   });
 }
 
+// ------------------------------------------------------------------------------------------ MV_Softmax
+// head/metrics.py:571-590 on the raw cosines of the FR_EPI_STORE GEMM; the head never clamps.  Its per-row values depend on
+// the target cosine alone, so there is no rows launch: every wave of mv_softmax_apply_kernel loads its row's target cosine
+// (one address per wave) and derives the same bits, and the wave of column chunk 0 leaves them in rowv [4][rows] for the
+// backward pass: gt, thr, final, d final / d gt.  is_am: thr = gt - p0 (p0 = margin), final = gt > p0 ? thr : gt, slope 1.
+// Otherwise (p0, p1) = (cos_m, sin_m): thr = gt p0 - sqrt(1 - gt^2) p1, final = gt > 0 ? thr : gt, slope p0 + p1 gt / sqrt(..)
+// or 1; |gt| > 1 makes thr NaN, unguarded as in the reference (no column is hard then).  A row whose label lies outside
+// [0, N) has no target: 0, +inf, 0, 0.
+struct MvRow {
+  float gt, thr, fin, dfin;
+};
+
+__device__ __forceinline__ MvRow mv_softmax_row(const float* __restrict__ crow, long long lab, int N, int is_am, float p0,
+                                                float p1) {
+  MvRow r = {0.f, __builtin_inff(), 0.f, 0.f};
+  if (lab < 0 || lab >= N) return r;
+  const float gt = crow[lab];
+  r.gt = gt;
+  if (is_am) {
+    r.thr = gt - p0;
+    r.fin = gt > p0 ? r.thr : gt;
+    r.dfin = 1.f;
+  } else {
+    const float sn = sqrtf(1.0f - gt * gt);
+    r.thr = gt * p0 - sn * p1;
+    r.fin = gt > 0.f ? r.thr : gt;
+    r.dfin = gt > 0.f ? p0 + p1 * gt / sn : 1.f;
+  }
+  return r;
+}
+
+// out = s * (label ? final : (c > thr ? w c + w - 1 : c)), c the raw cosine
+__global__ __launch_bounds__(256) void mv_softmax_apply_kernel(const float* __restrict__ cos,
+                                                               const long long* __restrict__ label,
+                                                               float* __restrict__ rowv, float* __restrict__ out, int rows,
+                                                               int N, int ld, int is_am, float p0, float p1, float w,
+                                                               float s) {
+  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const long long lab = label[row];
+  const MvRow r = mv_softmax_row(cos + (size_t)row * ld, lab, N, is_am, p0, p1);
+  if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) {
+    rowv[row] = r.gt;
+    rowv[rows + row] = r.thr;
+    rowv[2 * rows + row] = r.fin;
+    rowv[3 * rows + row] = r.dfin;
+  }
+  const float thr = r.thr, fin = r.fin, w1 = w - 1.0f;
+  margin_cols_fwd(cos, out, row, N, ld, [&](int n, float c) {
+    float v = c > thr ? w * c + w1 : c;
+    if (n == lab) v = fin;
+    return v * s;
+  });
+}
+
+// gcos = g * d out / d cos with the hard mask and the branch constant: s w on hard negatives, s on easy ones,
+// s * rowv[3] on the label column; no clamp, so no pass mask
+__global__ __launch_bounds__(256) void mv_softmax_bwd_kernel(const float* __restrict__ g, const float* __restrict__ cos,
+                                                             const long long* __restrict__ label,
+                                                             const float* __restrict__ rowv, float* __restrict__ gcos,
+                                                             int rows, int N, int ld, int ldg, float w, float s) {
+  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const long long lab = label[row];
+  const float thr = rowv[rows + row], dlab = rowv[3 * rows + row];
+  margin_cols_bwd<false>(g, cos, gcos, row, N, ld, ldg, [&](int n, float c, float gg) {
+    float d = c > thr ? w : 1.f;
+    if (n == lab) d = dlab;
+    return gg * s * d;
+  });
+}
+
 // ------------------------------------------------------------------------------------------ cross entropy rows
 __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ z, const long long* __restrict__ label,
                                                       float* __restrict__ lse, float* __restrict__ ce,
@@ -1185,6 +1258,23 @@ extern "C" int fr_npcface_bwd(const float* g, const float* cos, const int64_t* l
     FR_UNSUPPORTED("fr_npcface_bwd: shape (ldg >= ld >= N, multiples of 4)");
   hipLaunchKernelGGL(npcface_bwd_kernel, dim3(fr_margin_apply_parts(ldg), (rows + 3) / 4), dim3(256), 0,
                      (hipStream_t)stream, g, cos, (const long long*)label, rowv, gcos, rows, N, ld, ldg, t, s);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_mv_softmax_apply(const float* cos, const int64_t* label, float* rowv, float* out, int rows, int N, int ld,
+                                   int is_am, float p0, float p1, float w, float s, void* stream) {
+  if (rows <= 0 || N <= 0 || ld < N || ld % 4) FR_UNSUPPORTED("fr_mv_softmax_apply: shape (rows > 0, ld >= N > 0, ld a multiple of 4)");
+  hipLaunchKernelGGL(mv_softmax_apply_kernel, dim3(fr_margin_apply_parts(ld), (rows + 3) / 4), dim3(256), 0,
+                     (hipStream_t)stream, cos, (const long long*)label, rowv, out, rows, N, ld, is_am, p0, p1, w, s);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_mv_softmax_bwd(const float* g, const float* cos, const int64_t* label, const float* rowv, float* gcos,
+                                 int rows, int N, int ld, int ldg, float w, float s, void* stream) {
+  if (rows <= 0 || N <= 0 || ld < N || ld % 4 || ldg < ld || ldg % 4)
+    FR_UNSUPPORTED("fr_mv_softmax_bwd: shape (rows > 0, ldg >= ld >= N > 0, multiples of 4)");
+  hipLaunchKernelGGL(mv_softmax_bwd_kernel, dim3(fr_margin_apply_parts(ldg), (rows + 3) / 4), dim3(256), 0,
+                     (hipStream_t)stream, g, cos, (const long long*)label, rowv, gcos, rows, N, ld, ldg, w, s);
   FR_LAUNCH_CHECK();
 }
 

@@ -30,13 +30,13 @@ def _pad(n, m):
 # One cosine-head pipeline under the heads.  Forward: ``_cosine_operands`` (normalised operands), the cosine GEMM
 # (``_raw_cosines``, or ArcFace / CosFace's fused margin epilogue), the head's row kernels.  Backward: the head's gcos
 # kernel, then ``_cosine_backward`` (both GEMMs and the normalisation backwards).
-ARCFACE, COSFACE, SPHEREFACE, AM_SOFTMAX, CURRICULAR, MAGFACE, ADACOS, NPCFACE = range(8)  # 0..3: the kernels' margin kinds
+ARCFACE, COSFACE, SPHEREFACE, AM_SOFTMAX, CURRICULAR, MAGFACE, ADACOS, NPCFACE, MV_SOFTMAX = range(9)  # 0..3: the margin kinds
 
 # What a forward call keeps for its backward call; a head leaves what it does not use at None.  xn / wn [Np, D] / wt
 # [D, Np] are the GEMM operands (xn is x itself for Am_softmax), inv_x / inv_w the reciprocal norms, cos_t the target
 # cosines of the fused epilogue, cos the raw cosines [B, ld], rowv and t CurricularFace's row values and the t it used
-# (rowv: MagFace's and NPCFace's six row values too; t: the scale an AdaCos call used).  HeadCfg.mag: MagFace's (margin_am,
-# l_a, u_a, l_margin, u_margin, lamda); HeadCfg.p0 / p1: NPCFace's t / a.
+# (rowv: MagFace's and NPCFace's six row values and MV_Softmax's four too; t: the scale an AdaCos call used).  HeadCfg.mag:
+# MagFace's (margin_am, l_a, u_a, l_margin, u_margin, lamda); HeadCfg.p0 / p1: NPCFace's t / a; p0: MV_Softmax's mv_weight.
 HeadSaved = collections.namedtuple("HeadSaved", "x w label xn wn wt inv_x inv_w cos_t cos rowv t", defaults=(None,) * 12)
 HeadCfg = collections.namedtuple("HeadCfg", "kind Np ld s cos_m sin_m th easy mi p0 p1 mag", defaults=(None,) * 9)
 
@@ -342,6 +342,35 @@ def npcface_backward(saved, cfg, g, need_x, need_w, raw_x_grad=False):
     return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, None if raw_x_grad else "normalize", col_weight=True)
 
 
+def mv_softmax_forward(x, weight, label, s, mv):
+    """MV_Softmax logits (head/metrics.py:571-590) for fp32 device tensors; ``weight`` is [D, N], ``mv`` the head's (is_am,
+    p0, p1, w): p0 = margin with ``is_am``, (p0, p1) = (cos_m, sin_m) without, w = mv_weight.  The row values depend on the
+    target cosine alone, so one row kernel does it all: every wave reads its row's target cosine, derives thr and the label
+    column's value, re-weights the hard negatives (c > thr) to w * c + w - 1, and leaves rowv [4, B] (gt, thr, final,
+    d final / d gt) for the backward pass.  The cosines are never clamped.  Nothing waits on the host.  A label outside
+    [0, N) selects nothing and makes nothing hard in its row.  Returns (logits, saved, cfg) for ``mv_softmax_backward``."""
+    sv, N, Np, ld = _cosine_operands(x, weight, label, norm_x=True, col_weight=True)
+    B = x.shape[0]
+    is_am, p0, p1, w = bool(mv[0]), float(mv[1]), float(mv[2]), float(mv[3])
+    cos = _raw_cosines(sv, N, ld)
+    rowv = torch.empty(4, B, device=x.device)  # gt, thr, final, d final / d gt
+    store, logits = _logit_store(sv, N, ld)
+    ops.call("fr_mv_softmax_apply", cos, sv.label, rowv, store, B, N, ld, int(is_am), p0, p1, w, float(s),
+             ops.current_stream_ptr())()
+    return logits, sv._replace(cos=cos, rowv=rowv), HeadCfg(MV_SOFTMAX, Np, ld, s=float(s), p0=w)
+
+
+def mv_softmax_backward(saved, cfg, g, need_x, need_w, raw_x_grad=False):
+    """(gx, gweight) of ``mv_softmax_forward``; gweight is [D, N].  The hard mask and the branch of the label column are
+    comparisons and take no gradient; no cosine is masked out (the head never clamps).  ``raw_x_grad``: as in
+    ``margin_backward``."""
+    B, N = saved.x.shape[0], saved.inv_w.shape[0]
+    gcos = torch.empty(B, cfg.Np, device=saved.x.device)
+    ops.call("fr_mv_softmax_bwd", g.contiguous().float(), saved.cos, saved.label, saved.rowv, gcos, B, N, cfg.ld, cfg.Np,
+             cfg.p0, cfg.s, ops.current_stream_ptr())()
+    return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, None if raw_x_grad else "normalize", col_weight=True)
+
+
 def _head_fn(name, fwd, bwd, doc):
     """The autograd.Function of a head from its forward / backward pair; it takes the forward function's arguments (x,
     weight, label and up to four head-specific values)."""
@@ -400,6 +429,9 @@ AdaCosHeadFn = _head_fn("AdaCosHeadFn", adacos_forward, adacos_backward, """
 NPCFaceHeadFn = _head_fn("NPCFaceHeadFn", npcface_forward, npcface_backward, """
     NPCFace (head/metrics.py:592-636) on the HIP path; see ``npcface_forward``.""")
 
+MVSoftmaxHeadFn = _head_fn("MVSoftmaxHeadFn", mv_softmax_forward, mv_softmax_backward, """
+    MV_Softmax (head/metrics.py:555-590) on the HIP path; see ``mv_softmax_forward``.""")
+
 MagFaceHeadFn = _head_fn2("MagFaceHeadFn", magface_forward, magface_backward, """
     MagFace (head/metrics.py:512-553) on the HIP path: (logits, loss_g); see ``magface_forward``.""")
 
@@ -449,6 +481,12 @@ def adacos_head(x, W, label, scale, group=None):
 def npcface_head(x, kernel, label, s, cos_m, sin_m, m0, m1, t, a):
     """NPCFace logits; the empty batch and label check of ``margin_head``."""
     return _head_entry(NPCFaceHeadFn, kernel.shape[1], x, kernel, label, s, (cos_m, sin_m, m0, m1, t, a))
+
+
+def mv_softmax_head(x, weight, label, s, is_am, p0, p1, w):
+    """MV_Softmax logits; the empty batch and label check of ``margin_head``.  p0 = margin with ``is_am``, (p0, p1) =
+    (cos_m, sin_m) without; w = mv_weight."""
+    return _head_entry(MVSoftmaxHeadFn, weight.shape[1], x, weight, label, s, (is_am, p0, p1, w))
 
 
 def magface_head(x, kernel, label, s, margin_am, l_a, u_a, l_margin, u_margin, lamda):

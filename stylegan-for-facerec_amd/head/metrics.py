@@ -2,9 +2,10 @@
 
     from head.metrics import ArcFace, CosFace, SphereFace, Am_softmax        (reference train.py:9)
     from head.metrics import CurricularFace, MagFace, AdaCos, NPCFace        (reference head/metrics.py:475, :512, :336, :592)
+    from head.metrics import MV_Softmax                                      (reference head/metrics.py:555)
 
 The four heads the reference driver can select (``HEAD_NAME``, train.py:56,178-182) and ``CurricularFace`` / ``MagFace`` /
-``AdaCos`` / ``NPCFace`` (four of the FaceX-Zoo heads of the reference's head/metrics.py that its driver never names; train.py
+``AdaCos`` / ``NPCFace`` / ``MV_Softmax`` (five of the FaceX-Zoo heads of the reference's head/metrics.py that its driver never names; train.py
 here accepts them) run on the HIP kernels when their input is a device tensor:
   * ``ArcFace`` / ``CosFace`` (the two heads the shipped configs and BASELINE.json name): row normalise -> MFMA cosine
     GEMM with the margin / label-select / scale epilogue -> closed-form backward;
@@ -28,8 +29,13 @@ here accepts them) run on the HIP kernels when their input is a device tensor:
     target cosine, cos(theta + margin) and, in one more pass over the row, the mean and the count of the hard negatives
     (the cosines above cos(theta + margin), label column excluded; summed in a fixed order), and from them the label
     column's value at the margin ``m0 + m1 * mean``; a row kernel re-weights the hard negatives to ``t * c + a``; the
-    backward pass treats that margin, the mask and the ``gt > 0`` branch as constants.  No state besides ``kernel``.
-On host tensors ``SphereFace`` / ``Am_softmax`` / ``CurricularFace`` / ``MagFace`` / ``AdaCos`` / ``NPCFace`` run the reference's plain-PyTorch arithmetic (the
+    backward pass treats that margin, the mask and the ``gt > 0`` branch as constants.  No state besides ``kernel``;
+  * ``MV_Softmax``: rows and ``weight`` columns normalised, raw cosines from the same GEMM, never clamped.  One row kernel:
+    every wave reads its row's target cosine ``gt``, derives the threshold (``gt - margin`` with ``is_am``, else
+    cos(theta + margin)) and the label column's value, and re-weights the hard negatives (the cosines above the threshold)
+    to ``mv_weight * c + mv_weight - 1``; the backward pass treats the mask and the branch as constants and masks no
+    cosine out.  No state besides ``weight``.
+On host tensors ``SphereFace`` / ``Am_softmax`` / ``CurricularFace`` / ``MagFace`` / ``AdaCos`` / ``NPCFace`` / ``MV_Softmax`` run the reference's plain-PyTorch arithmetic (the
 restatement the tests compare with); ``ArcFace`` / ``CosFace`` refuse host tensors.  ``SphereFace.iter`` counts forward
 calls on either path, as in the reference; train.py carries it across a resume in the State_* file.  ``CurricularFace.t``
 is a buffer: the Head_* file carries it.  ``AdaCos.scale`` is a non-persistent buffer (the reference's Head_* files have the
@@ -59,6 +65,12 @@ Differences from the reference that a caller can observe:
     norm below 1e-12 is out of contract; a target cosine of exactly +-1 makes the reference's own gradient infinite, and
     nothing is done about it here either).  The reference builds its hard mask with ``.cuda()`` (:622) and so runs on no
     other device; the host path here leaves that call out and is otherwise its arithmetic.
+  * ``MV_Softmax``: the host path is the reference's arithmetic out of place (the reference writes into its cosine matrix).
+    Limits, followed as in the reference: on the device path a ``weight`` column of norm below 1e-12 is out of contract (no
+    eps); with ``is_am`` false a target cosine of exactly +-1 makes the reference's own gradient infinite, and a target
+    cosine beyond +-1 by rounding (the head never clamps) makes sqrt(1 - gt^2) and with it the threshold NaN: then no
+    negative of the row is hard, the label column is NaN where ``gt > 1`` and keeps ``gt`` where ``gt < -1`` (gradient 1 on
+    the device path).  The device path computes the same expressions unguarded.
 """
 import math
 
@@ -343,4 +355,49 @@ class NPCFace(nn.Module):
             cos_newm, sin_newm = torch.cos(newm), torch.sin(newm)
         final = torch.where(gt > 0, gt * cos_newm - sin_theta * sin_newm, gt)
         out = torch.where(c > ctm, self.t * c + self.a, c).scatter(1, at, final)
+        return out * self.scale
+
+
+class MV_Softmax(nn.Module):
+    """MV_Softmax, "Mis-classified Vector Guided Softmax" (reference head/metrics.py:555-590): HIP kernels on device tensors,
+    plain PyTorch on the host.
+
+    With ``gt`` a row's target cosine: ``is_am`` true gives the threshold ``gt - margin`` and the label column
+    ``gt - margin`` where ``gt > margin`` (else ``gt``); ``is_am`` false gives cos(theta + margin) from ``cos_m`` /
+    ``sin_m`` (not from ``margin``) for both, the label column where ``gt > 0`` (else ``gt``).  Negatives above the threshold
+    become ``mv_weight * c + mv_weight - 1``; the mask and the branch take no gradient, and no cosine is clamped.  All
+    attributes are plain and read on every call (``threshold`` and ``mm`` are the reference's, unused there too); the state
+    dict holds the key ``weight`` alone.  Limits: see the module docstring."""
+
+    def __init__(self, feat_dim, num_class, is_am, margin=0.35, mv_weight=1.12, scale=32):
+        super().__init__()
+        self.weight = Parameter(torch.empty(feat_dim, num_class))
+        self.weight.data.uniform_(-1, 1).renorm_(2, 1, 1e-5).mul_(1e5)
+        self.margin = margin
+        self.mv_weight = mv_weight
+        self.scale = scale
+        self.is_am = is_am
+        self.cos_m = math.cos(margin)
+        self.sin_m = math.sin(margin)
+        self.threshold = math.cos(math.pi - margin)
+        self.mm = self.sin_m * margin
+
+    def forward(self, x, label):
+        if x.is_cuda:
+            _beside(self, self.weight, x)
+            p0, p1 = (self.margin, 0.0) if self.is_am else (self.cos_m, self.sin_m)
+            return FRF.mv_softmax_head(x, self.weight, label.to(x.device), self.scale, bool(self.is_am), p0, p1,
+                                       self.mv_weight)
+        weight = self.weight.to(x.device)
+        c = torch.mm(F.normalize(x), F.normalize(weight, dim=0))
+        at = label.view(-1, 1).long()
+        gt = c.gather(1, at)
+        if self.is_am:
+            thr = gt - self.margin
+            final = torch.where(gt > self.margin, gt - self.margin, gt)
+        else:
+            sin_theta = torch.sqrt(1.0 - torch.pow(gt, 2))
+            thr = gt * self.cos_m - sin_theta * self.sin_m  # cos(theta_target + margin)
+            final = torch.where(gt > 0.0, thr, gt)
+        out = torch.where(c > thr, self.mv_weight * c + self.mv_weight - 1.0, c).scatter(1, at, final)
         return out * self.scale

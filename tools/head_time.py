@@ -2,12 +2,14 @@
 calls (mode fwdbwd) after 3 warm-up calls, event-timed; run it under `rocprofv3 --kernel-trace --stats -- ...` for the
 kernel times (profiles/margin_heads_b256_n28000.txt).
 
-    python tools/head_time.py {ArcFace|CosFace|SphereFace|Am_softmax|CurricularFace|MagFace|AdaCos|NPCFace} {fwd|fwdbwd} ITERS
+    python tools/head_time.py {ArcFace|CosFace|SphereFace|Am_softmax|CurricularFace|MagFace|AdaCos|NPCFace|MV_Softmax|MV_Softmax-arc}
+                              {fwd|fwdbwd} ITERS
 
 Several heads, comma separated, are timed in ONE process in alternating rounds (ROUNDS rounds of ITERS calls per head, the
 median round of each head reported, and the ratio to the first head named), so clocks and allocator state are shared
 (profiles/curricular_head_b256_n28000.txt, profiles/magface_head_b256_n28000.txt,
-profiles/adacos_head_b256_n28000.txt, profiles/npcface_head_b256_n28000.txt):
+profiles/adacos_head_b256_n28000.txt, profiles/npcface_head_b256_n28000.txt, profiles/mv_softmax_head_b256_n28000.txt;
+MV_Softmax is the additive-margin form, MV_Softmax-arc the ArcFace-style one):
 
     python tools/head_time.py Am_softmax,ArcFace,CurricularFace fwdbwd ITERS [ROUNDS]
 
@@ -34,9 +36,12 @@ gg = torch.full((B, 1), 1.0 / B).cuda()
 
 
 def make(name):
-    cls = getattr(H, name)
     zoo = name in ("CurricularFace", "MagFace", "AdaCos", "NPCFace")  # FaceX-Zoo heads: no device_id
-    head = (cls(D, N) if zoo else cls(D, N, None)).cuda()
+    if name in ("MV_Softmax", "MV_Softmax-arc"):  # is_am is a required argument: the AM form, or the ArcFace-style one
+        head = H.MV_Softmax(D, N, name == "MV_Softmax").cuda()
+    else:
+        cls = getattr(H, name)
+        head = (cls(D, N) if zoo else cls(D, N, None)).cuda()
     p = list(head.parameters())[0]
 
     def step():
