@@ -662,6 +662,24 @@ int fr_mv_softmax_apply(const float* cos, const int64_t* label, float* rowv, flo
 int fr_mv_softmax_bwd(const float* g, const float* cos, const int64_t* label, const float* rowv, float* gcos, int rows, int N,
                       int ld, int ldg, float w, float s, void* stream);
 
+/* ---- CircleLoss (head/metrics.py:435-473), the classification form, on the raw cosines cos [rows][ld] of the FR_EPI_STORE
+ *      GEMM between fr_row_normalize'd embeddings and the fr_col_normalize'd weight.  Element-wise after the clamp: no row
+ *      values, no state besides the weight.  (The FaceX-Zoo AM_Softmax, :371-392, needs no entry of its own: it is
+ *      fr_margin_apply / fr_margin_apply_bwd with kind 3 on the cosines of normalised embeddings.) */
+/* replaces :455-472.  c = clamp(cos, -1, 1);  out[m][n] = gamma * (n == label[m] ? max(o_p - c, 0) * (c - delta_p)
+ * : max(c - o_n, 0) * (c - delta_n)), every operation rounded to fp32 on its own and in this order, so out has the bits of
+ * the reference's fp32 expression on the same cosines; the clamps are comparisons: NaN passes (torch.clamp, torch.clamp_min).
+ * A negative with c <= o_n comes out as 0.  ld a multiple of 4, columns N..ld of out are written as 0.  A row whose label
+ * lies outside [0, N) has no label column: all its columns are negatives. */
+int fr_circle_apply(const float* cos, const int64_t* label, float* out, int rows, int N, int ld, float o_p, float o_n,
+                    float delta_p, float delta_n, float gamma, void* stream);
+/* the backward of :455-472 with alpha detached (:463-464): gcos[m][n] = (g[m][n] * gamma) * alpha, alpha = max(o_p - c, 0)
+ * on the label column and max(c - o_n, 0) off it, recomputed from the raw cosine, where -1 <= cos[m][n] <= 1 (torch.clamp
+ * passes gradient on the closed interval), else 0 (a NaN cosine too); 0 in the padding columns N..ldg.  g is [rows][N]
+ * contiguous. */
+int fr_circle_bwd(const float* g, const float* cos, const int64_t* label, float* gcos, int rows, int N, int ld, int ldg,
+                  float o_p, float o_n, float gamma, void* stream);
+
 /* ---- focal loss on the batch-mean cross entropy (loss/focal.py:17-21) + top-k (util/utils.py:343-358) */
 /* per row: lse[m], ce[m] = lse - z[label], rank[m] = #{n: z[n] > z[label]} */
 int fr_ce_rows(const float* logits, const int64_t* label, float* lse, float* ce, int32_t* rank, int rows, int N,

@@ -812,6 +812,48 @@ __global__ __launch_bounds__(256) void mv_softmax_bwd_kernel(const float* __rest
   });
 }
 
+// ------------------------------------------------------------------------------------------ CircleLoss
+// head/metrics.py:451-473 on the raw cosines of the FR_EPI_STORE GEMM.  Element-wise after the clamp: no row values, no
+// rows launch.  The operations keep the reference's fp32 order, each rounded on its own (O_p - c, the clamp at 0, c - delta_p,
+// the product, then * gamma), so the result has the bits of the torch expression on the same cosines; the clamps are
+// comparisons and let NaN through, as torch.clamp and torch.clamp_min do (fmaxf would not).
+__device__ __forceinline__ float clamp_min0(float a) { return a < 0.f ? 0.f : a; }
+
+// alpha of a clamped cosine, detached in the reference: clamp_min(O_p - c, 0) on the label column, clamp_min(c - O_n, 0) off it
+__device__ __forceinline__ float circle_alpha(float c, bool lab, float o_p, float o_n) {
+  return clamp_min0(lab ? __fsub_rn(o_p, c) : __fsub_rn(c, o_n));
+}
+
+// out = gamma * (label ? alpha_p (c - delta_p) : alpha_n (c - delta_n)), c the clamped cosine; a label outside [0, N)
+// matches no column: every column of its row is a negative
+__global__ __launch_bounds__(256) void circle_apply_kernel(const float* __restrict__ cos, const long long* __restrict__ label,
+                                                           float* __restrict__ out, int rows, int N, int ld, float o_p,
+                                                           float o_n, float delta_p, float delta_n, float gamma) {
+  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const long long lab = label[row];
+  margin_cols_fwd(cos, out, row, N, ld, [&](int n, float raw) {
+    const float c = clamp1(raw);
+    const bool pos = n == lab;
+    const float alpha = circle_alpha(c, pos, o_p, o_n);
+    return __fmul_rn(__fmul_rn(alpha, __fsub_rn(c, pos ? delta_p : delta_n)), gamma);
+  });
+}
+
+// gcos = (g gamma) alpha where the clamp at +-1 passes (the walker's mask), alpha recomputed from the raw cosine: autograd's
+// order, since alpha is a constant of the graph and d (alpha (c - delta)) / dc = alpha
+__global__ __launch_bounds__(256) void circle_bwd_kernel(const float* __restrict__ g, const float* __restrict__ cos,
+                                                         const long long* __restrict__ label, float* __restrict__ gcos,
+                                                         int rows, int N, int ld, int ldg, float o_p, float o_n,
+                                                         float gamma) {
+  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const long long lab = label[row];
+  margin_cols_bwd(g, cos, gcos, row, N, ld, ldg, [&](int n, float raw, float gg) {
+    return __fmul_rn(__fmul_rn(gg, gamma), circle_alpha(clamp1(raw), n == lab, o_p, o_n));
+  });
+}
+
 // ------------------------------------------------------------------------------------------ cross entropy rows
 __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ z, const long long* __restrict__ label,
                                                       float* __restrict__ lse, float* __restrict__ ce,
@@ -1275,6 +1317,23 @@ extern "C" int fr_mv_softmax_bwd(const float* g, const float* cos, const int64_t
     FR_UNSUPPORTED("fr_mv_softmax_bwd: shape (rows > 0, ldg >= ld >= N > 0, multiples of 4)");
   hipLaunchKernelGGL(mv_softmax_bwd_kernel, dim3(fr_margin_apply_parts(ldg), (rows + 3) / 4), dim3(256), 0,
                      (hipStream_t)stream, g, cos, (const long long*)label, rowv, gcos, rows, N, ld, ldg, w, s);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_circle_apply(const float* cos, const int64_t* label, float* out, int rows, int N, int ld, float o_p,
+                               float o_n, float delta_p, float delta_n, float gamma, void* stream) {
+  if (rows <= 0 || N <= 0 || ld < N || ld % 4) FR_UNSUPPORTED("fr_circle_apply: shape (rows > 0, ld >= N > 0, ld a multiple of 4)");
+  hipLaunchKernelGGL(circle_apply_kernel, dim3(fr_margin_apply_parts(ld), (rows + 3) / 4), dim3(256), 0,
+                     (hipStream_t)stream, cos, (const long long*)label, out, rows, N, ld, o_p, o_n, delta_p, delta_n, gamma);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_circle_bwd(const float* g, const float* cos, const int64_t* label, float* gcos, int rows, int N, int ld,
+                             int ldg, float o_p, float o_n, float gamma, void* stream) {
+  if (rows <= 0 || N <= 0 || ld < N || ld % 4 || ldg < ld || ldg % 4)
+    FR_UNSUPPORTED("fr_circle_bwd: shape (rows > 0, ldg >= ld >= N > 0, multiples of 4)");
+  hipLaunchKernelGGL(circle_bwd_kernel, dim3(fr_margin_apply_parts(ldg), (rows + 3) / 4), dim3(256), 0,
+                     (hipStream_t)stream, g, cos, (const long long*)label, gcos, rows, N, ld, ldg, o_p, o_n, gamma);
   FR_LAUNCH_CHECK();
 }
 

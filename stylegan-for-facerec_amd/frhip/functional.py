@@ -30,13 +30,15 @@ def _pad(n, m):
 # One cosine-head pipeline under the heads.  Forward: ``_cosine_operands`` (normalised operands), the cosine GEMM
 # (``_raw_cosines``, or ArcFace / CosFace's fused margin epilogue), the head's row kernels.  Backward: the head's gcos
 # kernel, then ``_cosine_backward`` (both GEMMs and the normalisation backwards).
-ARCFACE, COSFACE, SPHEREFACE, AM_SOFTMAX, CURRICULAR, MAGFACE, ADACOS, NPCFACE, MV_SOFTMAX = range(9)  # 0..3: the margin kinds
+ARCFACE, COSFACE, SPHEREFACE, AM_SOFTMAX, CURRICULAR, MAGFACE, ADACOS, NPCFACE, MV_SOFTMAX, CIRCLE, AM_SOFTMAX_N = range(11)
+# 0..3: the kernels' margin kinds.  AM_SOFTMAX_N is the FaceX-Zoo AM_Softmax (normalised embeddings) on the kernels' kind 3.
 
 # What a forward call keeps for its backward call; a head leaves what it does not use at None.  xn / wn [Np, D] / wt
 # [D, Np] are the GEMM operands (xn is x itself for Am_softmax), inv_x / inv_w the reciprocal norms, cos_t the target
 # cosines of the fused epilogue, cos the raw cosines [B, ld], rowv and t CurricularFace's row values and the t it used
 # (rowv: MagFace's and NPCFace's six row values and MV_Softmax's four too; t: the scale an AdaCos call used).  HeadCfg.mag:
-# MagFace's (margin_am, l_a, u_a, l_margin, u_margin, lamda); HeadCfg.p0 / p1: NPCFace's t / a; p0: MV_Softmax's mv_weight.
+# MagFace's (margin_am, l_a, u_a, l_margin, u_margin, lamda); HeadCfg.p0 / p1: NPCFace's t / a; p0: MV_Softmax's mv_weight;
+# p0 / p1 / s: CircleLoss's O_p / O_n / gamma; p0 / p1: AM_Softmax's margin / scale, as Am_softmax's.
 HeadSaved = collections.namedtuple("HeadSaved", "x w label xn wn wt inv_x inv_w cos_t cos rowv t", defaults=(None,) * 12)
 HeadCfg = collections.namedtuple("HeadCfg", "kind Np ld s cos_m sin_m th easy mi p0 p1 mag", defaults=(None,) * 9)
 
@@ -371,6 +373,53 @@ def mv_softmax_backward(saved, cfg, g, need_x, need_w, raw_x_grad=False):
     return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, None if raw_x_grad else "normalize", col_weight=True)
 
 
+def circle_forward(x, weight, label, circle):
+    """CircleLoss logits (head/metrics.py:451-473, the classification form) for fp32 device tensors; ``weight`` is [D, N],
+    ``circle`` the head's (O_p, O_n, delta_p, delta_n, gamma).  Element-wise on the clamped cosines: one row kernel, no row
+    values, nothing waits on the host.  A label outside [0, N) makes every column of its row a negative.  Returns (logits,
+    saved, cfg) for ``circle_backward``."""
+    sv, N, Np, ld = _cosine_operands(x, weight, label, norm_x=True, col_weight=True)
+    o_p, o_n, delta_p, delta_n, gamma = (float(v) for v in circle)
+    cos = _raw_cosines(sv, N, ld)
+    store, logits = _logit_store(sv, N, ld)
+    ops.call("fr_circle_apply", cos, sv.label, store, x.shape[0], N, ld, o_p, o_n, delta_p, delta_n, gamma,
+             ops.current_stream_ptr())()
+    return logits, sv._replace(cos=cos), HeadCfg(CIRCLE, Np, ld, s=gamma, p0=o_p, p1=o_n)
+
+
+def circle_backward(saved, cfg, g, need_x, need_w, raw_x_grad=False):
+    """(gx, gweight) of ``circle_forward``; gweight is [D, N].  alpha is a constant of the graph (:463-464 detach), so gcos =
+    g * gamma * alpha inside the clamp, alpha recomputed from the saved raw cosines.  ``raw_x_grad``: as in
+    ``margin_backward``."""
+    B, N = saved.x.shape[0], saved.inv_w.shape[0]
+    gcos = torch.empty(B, cfg.Np, device=saved.x.device)
+    ops.call("fr_circle_bwd", g.contiguous().float(), saved.cos, saved.label, gcos, B, N, cfg.ld, cfg.Np, cfg.p0, cfg.p1,
+             cfg.s, ops.current_stream_ptr())()
+    return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, None if raw_x_grad else "normalize", col_weight=True)
+
+
+def am_softmax_n_forward(x, weight, label, m, s):
+    """The FaceX-Zoo AM_Softmax logits (head/metrics.py:380-392) for fp32 device tensors; ``weight`` is [D, N].  It is
+    Am_softmax's arithmetic (fr_margin_apply kind 3: s * (label ? clamp(c) - m : clamp(c))) on the cosines of NORMALISED
+    embeddings.  Returns (logits, saved, cfg) for ``am_softmax_n_backward``."""
+    sv, N, Np, ld = _cosine_operands(x, weight, label, norm_x=True, col_weight=True)
+    cos = _raw_cosines(sv, N, ld)
+    store, logits = _logit_store(sv, N, ld)
+    ops.call("fr_margin_apply", cos, sv.label, None, store, x.shape[0], N, ld, AM_SOFTMAX, 0, float(m), float(s),
+             ops.current_stream_ptr())()
+    return logits, sv._replace(cos=cos), HeadCfg(AM_SOFTMAX_N, Np, ld, mi=0, p0=float(m), p1=float(s))
+
+
+def am_softmax_n_backward(saved, cfg, g, need_x, need_w, raw_x_grad=False):
+    """(gx, gweight) of ``am_softmax_n_forward``; gweight is [D, N].  Unlike Am_softmax's, gx goes back through the row
+    normalisation.  ``raw_x_grad``: as in ``margin_backward``."""
+    B, N = saved.x.shape[0], saved.inv_w.shape[0]
+    gcos = torch.empty(B, cfg.Np, device=saved.x.device)
+    ops.call("fr_margin_apply_bwd", g.contiguous().float(), saved.cos, saved.label, None, gcos, None, B, N, cfg.ld, cfg.Np,
+             AM_SOFTMAX, 0, cfg.p0, cfg.p1, ops.current_stream_ptr())()
+    return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, None if raw_x_grad else "normalize", col_weight=True)
+
+
 def _head_fn(name, fwd, bwd, doc):
     """The autograd.Function of a head from its forward / backward pair; it takes the forward function's arguments (x,
     weight, label and up to four head-specific values)."""
@@ -432,6 +481,12 @@ NPCFaceHeadFn = _head_fn("NPCFaceHeadFn", npcface_forward, npcface_backward, """
 MVSoftmaxHeadFn = _head_fn("MVSoftmaxHeadFn", mv_softmax_forward, mv_softmax_backward, """
     MV_Softmax (head/metrics.py:555-590) on the HIP path; see ``mv_softmax_forward``.""")
 
+CircleHeadFn = _head_fn("CircleHeadFn", circle_forward, circle_backward, """
+    CircleLoss (head/metrics.py:435-473) on the HIP path; see ``circle_forward``.""")
+
+AMSoftmaxNHeadFn = _head_fn("AMSoftmaxNHeadFn", am_softmax_n_forward, am_softmax_n_backward, """
+    The FaceX-Zoo AM_Softmax (head/metrics.py:371-392) on the HIP path; see ``am_softmax_n_forward``.""")
+
 MagFaceHeadFn = _head_fn2("MagFaceHeadFn", magface_forward, magface_backward, """
     MagFace (head/metrics.py:512-553) on the HIP path: (logits, loss_g); see ``magface_forward``.""")
 
@@ -487,6 +542,16 @@ def mv_softmax_head(x, weight, label, s, is_am, p0, p1, w):
     """MV_Softmax logits; the empty batch and label check of ``margin_head``.  p0 = margin with ``is_am``, (p0, p1) =
     (cos_m, sin_m) without; w = mv_weight."""
     return _head_entry(MVSoftmaxHeadFn, weight.shape[1], x, weight, label, s, (is_am, p0, p1, w))
+
+
+def circle_head(x, weight, label, o_p, o_n, delta_p, delta_n, gamma):
+    """CircleLoss logits; the empty batch and label check of ``margin_head``."""
+    return _head_entry(CircleHeadFn, weight.shape[1], x, weight, label, (o_p, o_n, delta_p, delta_n, gamma))
+
+
+def am_softmax_n_head(x, weight, label, m, s):
+    """The FaceX-Zoo AM_Softmax logits; the empty batch and label check of ``margin_head``."""
+    return _head_entry(AMSoftmaxNHeadFn, weight.shape[1], x, weight, label, m, s)
 
 
 def magface_head(x, kernel, label, s, margin_am, l_a, u_a, l_margin, u_margin, lamda):

@@ -3,10 +3,11 @@
     from head.metrics import ArcFace, CosFace, SphereFace, Am_softmax        (reference train.py:9)
     from head.metrics import CurricularFace, MagFace, AdaCos, NPCFace        (reference head/metrics.py:475, :512, :336, :592)
     from head.metrics import MV_Softmax                                      (reference head/metrics.py:555)
+    from head.metrics import CircleLoss, AM_Softmax                          (reference head/metrics.py:435, :371)
 
 The four heads the reference driver can select (``HEAD_NAME``, train.py:56,178-182) and ``CurricularFace`` / ``MagFace`` /
-``AdaCos`` / ``NPCFace`` / ``MV_Softmax`` (five of the FaceX-Zoo heads of the reference's head/metrics.py that its driver never names; train.py
-here accepts them) run on the HIP kernels when their input is a device tensor:
+``AdaCos`` / ``NPCFace`` / ``MV_Softmax`` / ``CircleLoss`` / ``AM_Softmax`` (seven of the FaceX-Zoo heads of the reference's
+head/metrics.py that its driver never names; train.py here accepts them) run on the HIP kernels when their input is a device tensor:
   * ``ArcFace`` / ``CosFace`` (the two heads the shipped configs and BASELINE.json name): row normalise -> MFMA cosine
     GEMM with the margin / label-select / scale epilogue -> closed-form backward;
   * ``SphereFace`` / ``Am_softmax``: the same cosine GEMM stores the raw cosines, a row kernel applies the clamp and the
@@ -34,8 +35,17 @@ here accepts them) run on the HIP kernels when their input is a device tensor:
     every wave reads its row's target cosine ``gt``, derives the threshold (``gt - margin`` with ``is_am``, else
     cos(theta + margin)) and the label column's value, and re-weights the hard negatives (the cosines above the threshold)
     to ``mv_weight * c + mv_weight - 1``; the backward pass treats the mask and the branch as constants and masks no
-    cosine out.  No state besides ``weight``.
-On host tensors ``SphereFace`` / ``Am_softmax`` / ``CurricularFace`` / ``MagFace`` / ``AdaCos`` / ``NPCFace`` / ``MV_Softmax`` run the reference's plain-PyTorch arithmetic (the
+    cosine out.  No state besides ``weight``;
+  * ``CircleLoss`` (the classification form): rows and ``weight`` columns normalised, raw cosines from the same GEMM, clamped
+    to [-1, 1].  One row kernel, element-wise: ``gamma * alpha_p * (c - delta_p)`` on the label column, ``gamma * alpha_n *
+    (c - delta_n)`` off it, with ``alpha_p = max(O_p - c, 0)`` and ``alpha_n = max(c - O_n, 0)`` constants of the graph: a
+    negative at or below ``O_n`` has logit 0 and gradient 0.  The kernels keep the reference's fp32 operation order, so on
+    the same cosines they give its bits.  No state besides ``weight``;
+  * ``AM_Softmax`` (the FaceX-Zoo additive-margin head; not ``Am_softmax``): ``Am_softmax``'s row kernels on the cosines of
+    NORMALISED embeddings, parameter ``weight``, margin 0.35 and scale 32 by default, and a feature gradient that goes back
+    through the row normalisation.  No state besides ``weight``.
+On host tensors ``SphereFace`` / ``Am_softmax`` / ``CurricularFace`` / ``MagFace`` / ``AdaCos`` / ``NPCFace`` / ``MV_Softmax`` /
+``CircleLoss`` / ``AM_Softmax`` run the reference's plain-PyTorch arithmetic (the
 restatement the tests compare with); ``ArcFace`` / ``CosFace`` refuse host tensors.  ``SphereFace.iter`` counts forward
 calls on either path, as in the reference; train.py carries it across a resume in the State_* file.  ``CurricularFace.t``
 is a buffer: the Head_* file carries it.  ``AdaCos.scale`` is a non-persistent buffer (the reference's Head_* files have the
@@ -71,6 +81,10 @@ Differences from the reference that a caller can observe:
     cosine beyond +-1 by rounding (the head never clamps) makes sqrt(1 - gt^2) and with it the threshold NaN: then no
     negative of the row is hard, the label column is NaN where ``gt > 1`` and keeps ``gt`` where ``gt < -1`` (gradient 1 on
     the device path).  The device path computes the same expressions unguarded.
+  * ``CircleLoss`` / ``AM_Softmax``: the host path is the reference's arithmetic out of place (the reference writes into a
+    copy of its cosine matrix through uint8 masks); on the device path a ``weight`` column of norm below 1e-12 is out of
+    contract (no eps), as with the siblings.  A NaN cosine gives a NaN logit and gradient 0 on both paths (torch.clamp
+    lets NaN through and passes no gradient there).
 """
 import math
 
@@ -401,3 +415,61 @@ class MV_Softmax(nn.Module):
             final = torch.where(gt > 0.0, thr, gt)
         out = torch.where(c > thr, self.mv_weight * c + self.mv_weight - 1.0, c).scatter(1, at, final)
         return out * self.scale
+
+
+class CircleLoss(nn.Module):
+    """CircleLoss, the classification form (reference head/metrics.py:435-473): HIP kernels on device tensors, plain PyTorch on
+    the host.
+
+    On the clamped cosines: ``gamma * alpha_p * (c - delta_p)`` on the label column and ``gamma * alpha_n * (c - delta_n)``
+    off it, ``alpha_p = clamp_min(O_p - c, 0)`` and ``alpha_n = clamp_min(c - O_n, 0)`` detached.  ``O_p``, ``O_n``,
+    ``delta_p``, ``delta_n`` and ``gamma`` are plain attributes read on every call (``margin`` is kept and, after
+    construction, not read, as in the reference); the state dict holds the key ``weight`` alone."""
+
+    def __init__(self, feat_dim, num_class, margin=0.25, gamma=256):
+        super().__init__()
+        self.weight = Parameter(torch.empty(feat_dim, num_class))
+        self.weight.data.uniform_(-1, 1).renorm_(2, 1, 1e-5).mul_(1e5)
+        self.margin = margin
+        self.gamma = gamma
+        self.O_p = 1 + margin
+        self.O_n = -margin
+        self.delta_p = 1 - margin
+        self.delta_n = margin
+
+    def forward(self, feats, labels):
+        if feats.is_cuda:
+            _beside(self, self.weight, feats)
+            return FRF.circle_head(feats, self.weight, labels.to(feats.device), self.O_p, self.O_n, self.delta_p,
+                                   self.delta_n, self.gamma)
+        weight = self.weight.to(feats.device)
+        c = torch.mm(F.normalize(feats), F.normalize(weight, dim=0)).clamp(-1, 1)
+        hot = torch.zeros_like(c).scatter_(1, labels.view(-1, 1).long(), 1).bool()
+        alpha_p = torch.clamp_min(self.O_p - c.detach(), min=0.)
+        alpha_n = torch.clamp_min(c.detach() - self.O_n, min=0.)
+        return torch.where(hot, alpha_p * (c - self.delta_p), alpha_n * (c - self.delta_n)) * self.gamma
+
+
+class AM_Softmax(nn.Module):
+    """The FaceX-Zoo additive-margin softmax (reference head/metrics.py:371-392; not ``Am_softmax``, :287-333): HIP kernels on
+    device tensors, plain PyTorch on the host.
+
+    ``scale * (c - margin)`` on the label column and ``scale * c`` off it, c the clamped cosine between the NORMALISED
+    embedding and the normalised ``weight`` column.  ``margin`` and ``scale`` are plain attributes read on every call; the
+    state dict holds the key ``weight`` alone."""
+
+    def __init__(self, feat_dim, num_class, margin=0.35, scale=32):
+        super().__init__()
+        self.weight = Parameter(torch.empty(feat_dim, num_class))
+        self.weight.data.uniform_(-1, 1).renorm_(2, 1, 1e-5).mul_(1e5)
+        self.margin = margin
+        self.scale = scale
+
+    def forward(self, feats, labels):
+        if feats.is_cuda:
+            _beside(self, self.weight, feats)
+            return FRF.am_softmax_n_head(feats, self.weight, labels.to(feats.device), self.margin, self.scale)
+        weight = self.weight.to(feats.device)
+        c = torch.mm(F.normalize(feats), F.normalize(weight, dim=0)).clamp(-1, 1)
+        hot = torch.zeros_like(c).scatter_(1, labels.view(-1, 1).long(), 1).bool()
+        return torch.where(hot, c - self.margin, c) * self.scale

@@ -35,7 +35,8 @@ from frhip import functional as FRF
 from frhip import set_compute_dtype
 from frhip.optim import SGD, Adam
 from frhip.parallel import DataParallel
-from head.metrics import AdaCos, Am_softmax, ArcFace, CosFace, CurricularFace, MagFace, MV_Softmax, NPCFace, SphereFace
+from head.metrics import (AM_Softmax, AdaCos, Am_softmax, ArcFace, CircleLoss, CosFace, CurricularFace, MagFace, MV_Softmax,
+                          NPCFace, SphereFace)
 from loss.focal import FocalLoss
 from util.utils import (AverageMeter, accuracy, buffer_val, collate_fn_ignore_none, get_time, get_val_data, perform_val,
                         schedule_lr, separate_irse_bn_paras, warm_up_lr)
@@ -138,6 +139,11 @@ def check_head_config(cfg):
         raise NotImplementedError("SHARDED_HEAD=True with HEAD_NAME 'MV_Softmax': the class-sharded head does not serve "
                                   "MV_Softmax (its target cosines need an exchange of their own); run it replicated, "
                                   "SHARDED_HEAD=False")
+    if cfg.get("SHARDED_HEAD", False) and cfg["HEAD_NAME"] in ("CircleLoss", "AM_Softmax"):
+        raise NotImplementedError("SHARDED_HEAD=True with HEAD_NAME '%s': the class-sharded head does not serve %s (it is "
+                                  "element-wise on the cosines and needs no exchange of its own, but it is not wired into "
+                                  "the sharded head); run it replicated, SHARDED_HEAD=False"
+                                  % (cfg["HEAD_NAME"], cfg["HEAD_NAME"]))
 
 
 def main():
@@ -214,6 +220,8 @@ def main():
         heads["NPCFace"] = NPCFace(emb, num_class, scale=s)  # after AdaCos, likewise
         heads["MV_Softmax"] = MV_Softmax(emb, num_class, cfg.get("MV_IS_AM", True))  # after NPCFace, likewise; the
         # reference's own margin, weight and scale (0.35, 1.12, 32), as MagFace; MV_IS_AM=False: the ArcFace-style form
+        heads["CircleLoss"] = CircleLoss(emb, num_class)  # after MV_Softmax, likewise; the reference's own margin 0.25, gamma 256
+        heads["AM_Softmax"] = AM_Softmax(emb, num_class)  # after CircleLoss, likewise; the reference's own margin 0.35, scale 32
     head = heads[cfg["HEAD_NAME"]]
     if world > 1 and hasattr(head, "process_group") and not cfg.get("SHARDED_HEAD", False):
         # replicated CurricularFace: t follows the mean target cosine of the GLOBAL batch, as under the reference's
