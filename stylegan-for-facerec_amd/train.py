@@ -121,29 +121,25 @@ def load_optimizer_checkpoint(optimizer, crit, sd):
     optimizer.load_state_dict(sd)
 
 
+# Heads the class-sharded head does not serve, and why.
+_ELEMENT_WISE = ("it is element-wise on the cosines and needs no exchange of its own, but it is not wired into the "
+                 "sharded head")
+NOT_SHARDED = {
+    "MagFace": "its radial term and loss_g need an exchange of their own",
+    "AdaCos": "its row sums and target cosines need an exchange of their own",
+    "NPCFace": "its target cosines and per-row hard sums and counts need an exchange of their own",
+    "MV_Softmax": "its target cosines need an exchange of their own",
+    "CircleLoss": _ELEMENT_WISE,
+    "AM_Softmax": _ELEMENT_WISE,
+}
+
+
 def check_head_config(cfg):
     """Refuse, before anything is built, a combination the driver does not serve."""
-    if cfg.get("SHARDED_HEAD", False) and cfg["HEAD_NAME"] == "MagFace":
-        raise NotImplementedError("SHARDED_HEAD=True with HEAD_NAME 'MagFace': the class-sharded head does not serve MagFace "
-                                  "(its radial term and loss_g need an exchange of their own); run it replicated, "
-                                  "SHARDED_HEAD=False")
-    if cfg.get("SHARDED_HEAD", False) and cfg["HEAD_NAME"] == "AdaCos":
-        raise NotImplementedError("SHARDED_HEAD=True with HEAD_NAME 'AdaCos': the class-sharded head does not serve AdaCos "
-                                  "(its row sums and target cosines need an exchange of their own); run it replicated, "
-                                  "SHARDED_HEAD=False")
-    if cfg.get("SHARDED_HEAD", False) and cfg["HEAD_NAME"] == "NPCFace":
-        raise NotImplementedError("SHARDED_HEAD=True with HEAD_NAME 'NPCFace': the class-sharded head does not serve NPCFace "
-                                  "(its target cosines and per-row hard sums and counts need an exchange of their own); run "
-                                  "it replicated, SHARDED_HEAD=False")
-    if cfg.get("SHARDED_HEAD", False) and cfg["HEAD_NAME"] == "MV_Softmax":
-        raise NotImplementedError("SHARDED_HEAD=True with HEAD_NAME 'MV_Softmax': the class-sharded head does not serve "
-                                  "MV_Softmax (its target cosines need an exchange of their own); run it replicated, "
-                                  "SHARDED_HEAD=False")
-    if cfg.get("SHARDED_HEAD", False) and cfg["HEAD_NAME"] in ("CircleLoss", "AM_Softmax"):
-        raise NotImplementedError("SHARDED_HEAD=True with HEAD_NAME '%s': the class-sharded head does not serve %s (it is "
-                                  "element-wise on the cosines and needs no exchange of its own, but it is not wired into "
-                                  "the sharded head); run it replicated, SHARDED_HEAD=False"
-                                  % (cfg["HEAD_NAME"], cfg["HEAD_NAME"]))
+    if cfg.get("SHARDED_HEAD", False) and cfg["HEAD_NAME"] in NOT_SHARDED:
+        name = cfg["HEAD_NAME"]
+        raise NotImplementedError("SHARDED_HEAD=True with HEAD_NAME '%s': the class-sharded head does not serve %s (%s); run "
+                                  "it replicated, SHARDED_HEAD=False" % (name, name, NOT_SHARDED[name]))
 
 
 def main():

@@ -13,21 +13,19 @@ run's own deviation from float64); the scale within max(1e-6, 8 x the host fp32 
 import copy
 import math
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 import adacos_data as AD
+import head_support as HS
 from frhip import synth
+from head_support import SENTINEL, Guarded, relerr
 
 pytestmark = pytest.mark.gpu
 
 D = 512
-SENTINEL = -12345.0
-BAND = 4096  # floats on either side of a buffer (a multiple of 4: the interior keeps its 16-byte alignment)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -56,10 +54,6 @@ def run(head, x, label, gout):
     y = head(x, label.to(x.device))
     y.backward(gout.to(device=x.device, dtype=y.dtype))
     return y.detach().cpu(), x.grad.cpu(), head.W.grad.cpu(), head.scale.detach().cpu().clone()
-
-
-def relerr(got, ref):
-    return float((got.double() - ref.double()).norm() / ref.double().norm())
 
 
 def srel(got, ref):
@@ -201,63 +195,29 @@ def test_reproducible_labels_checked_and_empty_batch(monkeypatch):
         FRF.adacos_head(xc, head.W, label.cuda(), torch.ones(1, device="cuda", dtype=torch.float64))
 
 
-def _profiled_names(fn):
-    from torch.profiler import ProfilerActivity, profile
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        fn()
-        torch.cuda.synchronize()
-    return [e.name for e in prof.events()]
-
-
-HOST_READS = ("aten::item", "aten::_local_scalar_dense")
-ATEN_GEMMS = ("aten::mm", "aten::addmm", "aten::matmul", "aten::bmm", "aten::linear")
-
-
 def test_forward_keeps_the_scale_on_the_device_and_calls_no_aten_gemm(monkeypatch):
     """torch.profiler over the forward pass (labels validated by the caller, as in train.py): no device-to-host copy, no
     scalar read, no ATen GEMM; the same over forward + backward with torch.mm / matmul / F.linear raising.  The profiler
-    does see such events when they happen (a .item() and a .cpu() of the buffer as the control)."""
+    does see such events when they happen (a .item() and a .cpu() of a device value as the control).  The profiled
+    call moves the scale; the host reads it only afterwards."""
     from frhip import functional as FRF
     B, N = 16, 300
     x, W, label, _ = AD.built(synth, "prof", B, D, N, 12)
     head = make(N, W).cuda()
     xc, lc = x.cuda().requires_grad_(True), label.cuda()
     monkeypatch.setattr(FRF, "CHECK_LABELS", False)
-    head(xc, lc)  # first call: streams, allocator
-    torch.cuda.synchronize()
-    control = _profiled_names(lambda: (head.scale.item(), head.scale.cpu(), torch.mm(xc.detach(), head.W.detach().t())))
-    assert any(n in HOST_READS for n in control) and any("DtoH" in n for n in control), sorted(set(control))
-    assert "aten::mm" in control
-    before = float(head.scale)
-    names = _profiled_names(lambda: head(xc, lc))
-    bad = [n for n in names if n in HOST_READS or n in ATEN_GEMMS or "DtoH" in n or n.startswith("Cijk_")]
-    assert not bad, sorted(set(bad))
-    assert float(head.scale) != before
+    seen = []
 
-    def boom(*a, **kw):
-        raise AssertionError("ATen GEMM called on the HIP path")
+    def forward(x, lab):
+        seen.append(head.scale.clone())  # a device copy: the host reads it after the profiled pass
+        return head(x, lab)
 
-    for mod, name in ((torch, "mm"), (torch, "matmul"), (F, "linear"), (torch.Tensor, "mm"), (torch.Tensor, "__matmul__")):
-        monkeypatch.setattr(mod, name, boom)
-    y = head(xc, lc)
-    y.backward(torch.ones_like(y))
-    torch.cuda.synchronize()
-    assert torch.isfinite(xc.grad).all() and torch.isfinite(head.W.grad).all()
+    HS.assert_forward_stays_on_device(monkeypatch, forward, xc, lc, head.W)
+    scales = [float(v) for v in seen]  # before the first call, before the profiled one, after it
+    assert len(scales) == 3 and scales[2] != scales[1], scales
 
 
 # ------------------------------------------------------------------------------------------------ C ABI, guarded
-
-
-class Guarded(object):
-    """A sentinel-filled device buffer of ``shape`` between two sentinel-filled guard bands."""
-
-    def __init__(self, *shape):
-        n = int(np.prod(shape))
-        self.flat = torch.full((2 * BAND + n,), SENTINEL, device="cuda")
-        self.t = self.flat[BAND:BAND + n].view(*shape)
-
-    def assert_guards(self, what):
-        assert bool((self.flat[:BAND] == SENTINEL).all()) and bool((self.flat[-BAND:] == SENTINEL).all()), what
 
 
 @pytest.mark.parametrize("N", [33, 1000, 1001])
@@ -357,66 +317,19 @@ def test_apply_kernel_forward_and_backward_use(N):
 # ------------------------------------------------------------------------------------------------ train.py
 
 
-def _run_train(tmp, tag, extra_cfg, max_steps=0, ok=True):
-    import subprocess
-    import sys
-    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "stylegan-for-facerec_amd")
-    env = dict(os.environ, PYTHONPATH=root)
-    argv = ["train.py", "--config", "configs/config_synthetic_smoke.py", "--synthetic", "12x10"]
-    if max_steps:
-        argv += ["--max-steps", str(max_steps)]
-    model_dir = tmp / tag
-    cfg_patch = ("import configs.config_synthetic_smoke as c; c.configurations[1].update(BATCH_SIZE=20, NUM_EPOCH=2, "
-                 "MODEL_ROOT=r'%s', LOG_ROOT=r'%s', **%r)" % (model_dir, tmp / "log", extra_cfg))
-    code = "import sys, runpy; sys.argv=%r; %s; runpy.run_path('train.py', run_name='__main__')" % (argv, cfg_patch)
-    out = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, capture_output=True, text=True, timeout=900)
-    if not ok:
-        return out
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    return model_dir, out.stdout
-
-
-def _ckpt(model_dir, prefix):
-    hits = sorted(f for f in os.listdir(model_dir) if f.startswith(prefix))
-    assert len(hits) == 1, (prefix, os.listdir(model_dir))
-    return os.path.join(model_dir, hits[0])
-
-
 def test_train_py_runs_and_resumes_bit_for_bit_with_adacos(tmp_path):
     """HEAD_NAME = 'AdaCos' on the synthetic config: 12 steps with finite loss, the Head_* file with the key W alone and the
     State_* file with a ``head_scale`` that has moved; and 12 steps straight == 6 steps, stop, resume for 6, bit for bit,
     the scale included (the State_* file carries it).  SHARDED_HEAD=True raises before anything is built."""
     cfg = dict(HEAD_NAME="AdaCos")
-    a_dir, a_log = _run_train(tmp_path, "straight", cfg)
-    losses = [float(m.group(1)) for m in re.finditer(r"Training Loss ([0-9.eE+-]+|nan|inf) \(", a_log)]
-    print("losses per step:", losses)
-    assert len(losses) == 12 and all(np.isfinite(losses)), a_log[-2000:]
-    assert "Prec@1" in a_log and "nan" not in a_log.lower()
-    b1_dir, _ = _run_train(tmp_path, "first", cfg, max_steps=6)
-    sd = torch.load(_ckpt(b1_dir, "Head_AdaCos_Epoch_1_Batch_6_"), map_location="cpu")
+    _, sd, _, (a_dir, b1_dir, b2_dir) = HS.straight_and_resumed(tmp_path, cfg, "AdaCos")
     assert list(sd) == ["W"] and tuple(sd["W"].shape) == (12, 512) and bool(torch.isfinite(sd["W"]).all())
-    state1 = torch.load(_ckpt(b1_dir, "State_AdaCos_Epoch_1_Batch_6_"), map_location="cpu")
+    state1 = torch.load(HS.ckpt(b1_dir, "State_AdaCos_Epoch_1_Batch_6_"), map_location="cpu")
     s_mid = state1["head_scale"]
     assert isinstance(s_mid, float) and math.isfinite(s_mid) and abs(s_mid - AD.scale0(12)) > 1e-3
-    resume = dict(cfg, BACKBONE_RESUME_ROOT=_ckpt(b1_dir, "Backbone_IR_50_ReStyle_Epoch_1_Batch_6_"),
-                  HEAD_RESUME_ROOT=_ckpt(b1_dir, "Head_AdaCos_Epoch_1_Batch_6_"),
-                  OPTIMIZER_RESUME_ROOT=_ckpt(b1_dir, "Optimizer_AdaCos_Epoch_1_Batch_6_"),
-                  STATE_RESUME_ROOT=_ckpt(b1_dir, "State_AdaCos_Epoch_1_Batch_6_"))
-    b2_dir, log = _run_train(tmp_path, "second", resume)
-    assert "Resuming at epoch 1 batch 6" in log and "Loading Optimizer Checkpoint" in log
-    for prefix in ("Backbone_IR_50_ReStyle_Epoch_2_Batch_12_", "Head_AdaCos_Epoch_2_Batch_12_"):
-        sa = torch.load(_ckpt(a_dir, prefix), map_location="cpu")
-        sb = torch.load(_ckpt(b2_dir, prefix), map_location="cpu")
-        assert list(sa.keys()) == list(sb.keys())
-        for key in sa:
-            assert torch.equal(sa[key], sb[key]), (prefix, key, float((sa[key].float() - sb[key].float()).abs().max()))
-    ea = torch.load(_ckpt(a_dir, "State_AdaCos_Epoch_2_Batch_12_"), map_location="cpu")
-    eb = torch.load(_ckpt(b2_dir, "State_AdaCos_Epoch_2_Batch_12_"), map_location="cpu")
+    ea = torch.load(HS.ckpt(a_dir, "State_AdaCos_Epoch_2_Batch_12_"), map_location="cpu")
+    eb = torch.load(HS.ckpt(b2_dir, "State_AdaCos_Epoch_2_Batch_12_"), map_location="cpu")
     assert ea["head_scale"] == eb["head_scale"] and ea["head_scale"] != s_mid  # bit for bit, and it went on moving
-    oa = torch.load(_ckpt(a_dir, "Optimizer_AdaCos_Epoch_2_Batch_12_"), map_location="cpu")
-    ob = torch.load(_ckpt(b2_dir, "Optimizer_AdaCos_Epoch_2_Batch_12_"), map_location="cpu")
-    for key in oa["state"]:
-        assert torch.equal(oa["state"][key]["momentum_buffer"], ob["state"][key]["momentum_buffer"]), key
-    out = _run_train(tmp_path, "sharded", dict(cfg, SHARDED_HEAD=True), ok=False)
+    out = HS.run_train(tmp_path, "sharded", dict(cfg, SHARDED_HEAD=True), ok=False)
     assert out.returncode != 0 and "NotImplementedError" in out.stderr and "AdaCos" in out.stderr
     assert "Number of Training Classes" not in out.stdout and not os.path.exists(tmp_path / "sharded")

@@ -9,7 +9,6 @@ copy of the module.  The batches are the constructed ones of tests/circle_data.p
 planted negatives below O_n (dead), just above it and near +0.6, which random embeddings never produce."""
 import copy
 import os
-import re
 
 import numpy as np
 import pytest
@@ -17,14 +16,14 @@ import torch
 import torch.nn.functional as F
 
 import circle_data as CD
+import head_support as HS
 from frhip import synth
+from head_support import Guarded, float64_reference, maxrel, relerr, run
 
 pytestmark = pytest.mark.gpu
 
 CASES = ("circle_rand", "circle_built", "circle_built_m04", "am_rand", "am_built", "am_built_m05")
 D = 512
-SENTINEL = -12345.0
-BAND = 4096  # floats on either side of a buffer (a multiple of 4: the interior keeps its 16-byte alignment)
 HEADS = [pytest.param("circle", id="CircleLoss"), pytest.param("am", id="AM_Softmax")]
 
 
@@ -50,32 +49,10 @@ def make(head, N, k, margin=None, scale=None):
     return mod
 
 
-def run(mod, x, label, gout):
-    """(logits, gx, gweight) of one forward + backward, on whatever device x is on."""
-    x = x.clone().requires_grad_(True)
-    mod.weight.grad = None
-    y = mod(x, label.to(x.device))
-    y.backward(gout.to(device=x.device, dtype=y.dtype))
-    return y.detach().cpu(), x.grad.cpu(), mod.weight.grad.cpu()
-
-
-def float64_reference(mod, x, label, gout):
-    h = copy.deepcopy(mod).cpu().double()
-    return run(h, x.double().cpu(), label.cpu(), gout.double().cpu())
-
-
 def logit_bar(scale):
     """The siblings' 1e-3 was set with scales up to 64; CircleLoss's gamma of 256 makes the same cosine error four times
     larger."""
     return 1e-3 * max(1.0, scale / 64.0)
-
-
-def maxrel(got, ref):
-    return float((got.double() - ref.double()).abs().max() / ref.double().abs().max())
-
-
-def relerr(got, ref):
-    return float((got.double() - ref.double()).norm() / ref.double().norm())
 
 
 @pytest.mark.parametrize("tag", CASES)
@@ -149,18 +126,6 @@ def test_baseline_size_logits_against_float64(head):
 
 
 # ------------------------------------------------------------------------------------------------ C ABI, guarded
-
-
-class Guarded(object):
-    """A sentinel-filled device buffer of ``shape`` between two sentinel-filled guard bands."""
-
-    def __init__(self, *shape):
-        n = int(np.prod(shape))
-        self.flat = torch.full((2 * BAND + n,), SENTINEL, device="cuda")
-        self.t = self.flat[BAND:BAND + n].view(*shape)
-
-    def assert_guards(self, what):
-        assert bool((self.flat[:BAND] == SENTINEL).all()) and bool((self.flat[-BAND:] == SENTINEL).all()), what
 
 
 ROWS = 9  # two full row blocks of four and a third with three idle waves
@@ -312,16 +277,6 @@ def test_am_softmax_is_am_softmax_on_normalised_embeddings():
 # ------------------------------------------------------------------------------------------------ the pipeline
 
 
-def _profiled_names(fn):
-    from torch.profiler import ProfilerActivity, profile
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        fn()
-        torch.cuda.synchronize()
-    return [e.name for e in prof.events()]
-
-
-HOST_READS = ("aten::item", "aten::_local_scalar_dense")
-ATEN_GEMMS = ("aten::mm", "aten::addmm", "aten::matmul", "aten::bmm", "aten::linear")
 ROW_KERNEL = {"circle": "circle_apply", "am": "margin_apply"}
 
 
@@ -337,27 +292,9 @@ def test_forward_waits_for_no_host_read_and_calls_no_aten_gemm(monkeypatch, head
     mod = make(head, N, k).cuda()
     xc, lc = x.cuda().requires_grad_(True), label.cuda()
     monkeypatch.setattr(FRF, "CHECK_LABELS", False)
-    mod(xc, lc)  # first call: streams, allocator
-    torch.cuda.synchronize()
-    one = torch.ones(1, device="cuda")
-    control = _profiled_names(lambda: (one.item(), one.cpu(), torch.mm(xc.detach(), mod.weight.detach())))
-    assert any(n in HOST_READS for n in control) and any("DtoH" in n for n in control), sorted(set(control))
-    assert "aten::mm" in control
-    names = _profiled_names(lambda: mod(xc, lc))
-    bad = [n for n in names if n in HOST_READS or n in ATEN_GEMMS or "DtoH" in n or n.startswith("Cijk_")]
-    assert not bad, sorted(set(bad))
+    names = HS.assert_forward_stays_on_device(monkeypatch, mod, xc, lc, mod.weight)
     assert sum(ROW_KERNEL[head] in n for n in names) == 1, sorted(set(names))
     assert not any(r + "_rows" in n for n in names for r in ("npcface", "curricular", "magface", "adacos", "mv_softmax", "circle"))
-
-    def boom(*a, **kw):
-        raise AssertionError("ATen GEMM called on the HIP path")
-
-    for m, name in ((torch, "mm"), (torch, "matmul"), (F, "linear"), (torch.Tensor, "mm"), (torch.Tensor, "__matmul__")):
-        monkeypatch.setattr(m, name, boom)
-    y = mod(xc, lc)
-    y.backward(torch.ones_like(y))
-    torch.cuda.synchronize()
-    assert torch.isfinite(xc.grad).all() and torch.isfinite(mod.weight.grad).all()
 
 
 @pytest.mark.parametrize("head", HEADS)
@@ -423,29 +360,6 @@ def test_attributes_are_read_at_call_time():
 EPOCHS = 2  # of 6 steps each: the 12 steps of the sibling heads' tests
 
 
-def _run_train(tmp, tag, extra_cfg, max_steps=0):
-    import subprocess
-    import sys
-    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "stylegan-for-facerec_amd")
-    env = dict(os.environ, PYTHONPATH=root)
-    argv = ["train.py", "--config", "configs/config_synthetic_smoke.py", "--synthetic", "12x10"]
-    if max_steps:
-        argv += ["--max-steps", str(max_steps)]
-    model_dir = tmp / tag
-    cfg_patch = ("import configs.config_synthetic_smoke as c; c.configurations[1].update(BATCH_SIZE=20, NUM_EPOCH=%d, "
-                 "MODEL_ROOT=r'%s', LOG_ROOT=r'%s', **%r)" % (EPOCHS, model_dir, tmp / "log", extra_cfg))
-    code = "import sys, runpy; sys.argv=%r; %s; runpy.run_path('train.py', run_name='__main__')" % (argv, cfg_patch)
-    out = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    return model_dir, out.stdout
-
-
-def _ckpt(model_dir, prefix):
-    hits = sorted(f for f in os.listdir(model_dir) if f.startswith(prefix))
-    assert len(hits) == 1, (prefix, os.listdir(model_dir))
-    return os.path.join(model_dir, hits[0])
-
-
 @pytest.mark.parametrize("name", ["CircleLoss", "AM_Softmax"])
 def test_train_py_runs_and_resumes_bit_for_bit(tmp_path, name):
     """HEAD_NAME = 'CircleLoss' / 'AM_Softmax' on the synthetic config, the reference's defaults: 12 steps with finite loss
@@ -454,31 +368,7 @@ def test_train_py_runs_and_resumes_bit_for_bit(tmp_path, name):
     asserted to fall because the host path falls too: the same loop with the head's forward replaced by its plain-PyTorch
     arithmetic on CPU copies of the features and the weight went from 221.6 to 134.0 with CircleLoss (the device path:
     221.6 to 133.9; gamma = 256 makes the focal loss that large) and from 14.2 to 5.06 with AM_Softmax (5.01)."""
-    cfg = dict(HEAD_NAME=name)
-    a_dir, a_log = _run_train(tmp_path, "straight", cfg)
-    losses = [float(m.group(1)) for m in re.finditer(r"Training Loss ([0-9.eE+-]+|nan|inf) \(", a_log)]
-    print("losses per step:", name, losses)
-    assert len(losses) == 6 * EPOCHS and all(np.isfinite(losses)), a_log[-2000:]
+    losses, sd, sa, _ = HS.straight_and_resumed(tmp_path, dict(HEAD_NAME=name), name, EPOCHS)
     assert sum(losses[-3:]) < sum(losses[:3]), losses
-    assert "Prec@1" in a_log and "nan" not in a_log.lower()
-    b1_dir, _ = _run_train(tmp_path, "first", cfg, max_steps=6)
-    sd = torch.load(_ckpt(b1_dir, "Head_%s_Epoch_1_Batch_6_" % name), map_location="cpu")
     assert list(sd) == ["weight"] and tuple(sd["weight"].shape) == (512, 12) and bool(torch.isfinite(sd["weight"]).all())
-    resume = dict(cfg, BACKBONE_RESUME_ROOT=_ckpt(b1_dir, "Backbone_IR_50_ReStyle_Epoch_1_Batch_6_"),
-                  HEAD_RESUME_ROOT=_ckpt(b1_dir, "Head_%s_Epoch_1_Batch_6_" % name),
-                  OPTIMIZER_RESUME_ROOT=_ckpt(b1_dir, "Optimizer_%s_Epoch_1_Batch_6_" % name),
-                  STATE_RESUME_ROOT=_ckpt(b1_dir, "State_%s_Epoch_1_Batch_6_" % name))
-    b2_dir, log = _run_train(tmp_path, "second", resume)
-    assert "Resuming at epoch 1 batch 6" in log and "Loading Optimizer Checkpoint" in log
-    last = "Epoch_%d_Batch_%d_" % (EPOCHS, 6 * EPOCHS)
-    for prefix in ("Backbone_IR_50_ReStyle_" + last, "Head_%s_%s" % (name, last)):
-        sa = torch.load(_ckpt(a_dir, prefix), map_location="cpu")
-        sb = torch.load(_ckpt(b2_dir, prefix), map_location="cpu")
-        assert list(sa.keys()) == list(sb.keys())
-        for key in sa:
-            assert torch.equal(sa[key], sb[key]), (prefix, key, float((sa[key].float() - sb[key].float()).abs().max()))
     assert not torch.equal(sa["weight"], sd["weight"])  # the head went on moving after the resume
-    oa = torch.load(_ckpt(a_dir, "Optimizer_%s_%s" % (name, last)), map_location="cpu")
-    ob = torch.load(_ckpt(b2_dir, "Optimizer_%s_%s" % (name, last)), map_location="cpu")
-    for key in oa["state"]:
-        assert torch.equal(oa["state"][key]["momentum_buffer"], ob["state"][key]["momentum_buffer"]), key

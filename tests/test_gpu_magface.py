@@ -8,15 +8,16 @@ copy of the module.  The batches are the constructed ones of tests/magface_data.
 [l_a, u_a], both target branches, none of them near a branch boundary or an end of the clamp."""
 import copy
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+import head_support as HS
 import magface_data as MD
 from frhip import synth
+from head_support import SENTINEL, Guarded, maxrel, relerr
 
 pytestmark = pytest.mark.gpu
 
@@ -58,14 +59,6 @@ def run(head, x, label, gout, gg):
 def float64_reference(head, x, label, gout, gg):
     h = copy.deepcopy(head).cpu().double()
     return run(h, x.double().cpu(), label.cpu(), None if gout is None else gout.double(), None if gg is None else gg.double())
-
-
-def maxrel(got, ref):
-    return float((got.double() - ref.double()).abs().max() / ref.double().abs().max())
-
-
-def relerr(got, ref):
-    return float((got.double() - ref.double()).norm() / ref.double().norm())
 
 
 @pytest.mark.parametrize("tag", CASES)
@@ -251,17 +244,6 @@ def test_two_runs_are_bit_identical(monkeypatch):
             assert torch.equal(a, b)
 
 
-def _profiled_names(fn):
-    from torch.profiler import ProfilerActivity, profile
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        fn()
-        torch.cuda.synchronize()
-    return [e.name for e in prof.events()]
-
-
-ATEN_GEMMS = ("aten::mm", "aten::addmm", "aten::matmul", "aten::bmm", "aten::linear")
-
-
 def test_forward_calls_no_aten_gemm(monkeypatch):
     """torch.profiler over the forward pass (labels validated by the caller, as in train.py): no ATen GEMM and no
     device-to-host copy; the same over forward + backward with torch.mm / matmul / F.linear raising.  The profiler does see
@@ -274,17 +256,12 @@ def test_forward_calls_no_aten_gemm(monkeypatch):
     monkeypatch.setattr(FRF, "CHECK_LABELS", False)
     head(xc, lc)  # first call: streams, allocator
     torch.cuda.synchronize()
-    control = _profiled_names(lambda: (lc.cpu(), torch.mm(xc.detach(), head.weight.detach())))
+    control = HS.profiled_names(lambda: (lc.cpu(), torch.mm(xc.detach(), head.weight.detach())))
     assert "aten::mm" in control and any("DtoH" in n for n in control), sorted(set(control))
-    names = _profiled_names(lambda: head(xc, lc))
-    bad = [n for n in names if n in ATEN_GEMMS or "DtoH" in n or n.startswith("Cijk_")]
+    names = HS.profiled_names(lambda: head(xc, lc))
+    bad = [n for n in names if n in HS.ATEN_GEMMS or "DtoH" in n or n.startswith("Cijk_")]
     assert not bad, sorted(set(bad))
-
-    def boom(*a, **kw):
-        raise AssertionError("ATen GEMM called on the HIP path")
-
-    for mod, name in ((torch, "mm"), (torch, "matmul"), (F, "linear"), (torch.Tensor, "mm"), (torch.Tensor, "__matmul__")):
-        monkeypatch.setattr(mod, name, boom)
+    HS.forbid_aten_gemm(monkeypatch)
     y, lg = head(xc, lc)
     (y.sum() + lg.mean()).backward()
     torch.cuda.synchronize()
@@ -292,22 +269,6 @@ def test_forward_calls_no_aten_gemm(monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------ row kernels, guarded
-
-SENTINEL = -12345.0
-BAND = 4096  # floats on either side of a buffer (a multiple of 4: the interior keeps its 16-byte alignment)
-
-
-class Guarded(object):
-    """A sentinel-filled device buffer of ``shape`` between two sentinel-filled guard bands."""
-
-    def __init__(self, *shape):
-        n = int(np.prod(shape))
-        self.flat = torch.full((2 * BAND + n,), SENTINEL, device="cuda")
-        self.t = self.flat[BAND:BAND + n].view(*shape)
-
-    def assert_guards(self, what):
-        assert bool((self.flat[:BAND] == SENTINEL).all()) and bool((self.flat[-BAND:] == SENTINEL).all()), what
-
 
 def test_row_kernels_in_sentinel_filled_buffers():
     """fr_magface_rows / _apply / _bwd at rows = 6 (a row block with two idle waves), N = 1001, ld = 1004, ldg = 1024 with
@@ -368,56 +329,10 @@ def test_row_kernels_in_sentinel_filled_buffers():
 # ------------------------------------------------------------------------------------------------ train.py
 
 
-def _run_train(tmp, tag, extra_cfg, max_steps=0):
-    import subprocess
-    import sys
-    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "stylegan-for-facerec_amd")
-    env = dict(os.environ, PYTHONPATH=root)
-    argv = ["train.py", "--config", "configs/config_synthetic_smoke.py", "--synthetic", "12x10"]
-    if max_steps:
-        argv += ["--max-steps", str(max_steps)]
-    model_dir = tmp / tag
-    cfg_patch = ("import configs.config_synthetic_smoke as c; c.configurations[1].update(BATCH_SIZE=20, NUM_EPOCH=2, "
-                 "MODEL_ROOT=r'%s', LOG_ROOT=r'%s', **%r)" % (model_dir, tmp / "log", extra_cfg))
-    code = "import sys, runpy; sys.argv=%r; %s; runpy.run_path('train.py', run_name='__main__')" % (argv, cfg_patch)
-    out = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    return model_dir, out.stdout
-
-
-def _ckpt(model_dir, prefix):
-    hits = sorted(f for f in os.listdir(model_dir) if f.startswith(prefix))
-    assert len(hits) == 1, (prefix, os.listdir(model_dir))
-    return os.path.join(model_dir, hits[0])
-
-
 def test_train_py_learns_and_resumes_bit_for_bit_with_magface(tmp_path):
     """HEAD_NAME = 'MagFace' on the synthetic config: 12 steps with finite loss that decreases (the mean of the last three
     steps below the mean of the first three), the Head_* file in the reference's layout; and 12 steps straight == 6 steps,
     stop, resume for 6, bit for bit."""
-    cfg = dict(HEAD_NAME="MagFace")
-    a_dir, a_log = _run_train(tmp_path, "straight", cfg)
-    losses = [float(m.group(1)) for m in re.finditer(r"Training Loss ([0-9.eE+-]+|nan|inf) \(", a_log)]
-    print("losses per step:", losses)
-    assert len(losses) == 12 and all(np.isfinite(losses)), a_log[-2000:]
+    losses, sd, _, _ = HS.straight_and_resumed(tmp_path, dict(HEAD_NAME="MagFace"), "MagFace")
     assert sum(losses[-3:]) < sum(losses[:3]), losses
-    assert "Prec@1" in a_log and "nan" not in a_log.lower()
-    b1_dir, _ = _run_train(tmp_path, "first", cfg, max_steps=6)
-    sd = torch.load(_ckpt(b1_dir, "Head_MagFace_Epoch_1_Batch_6_"), map_location="cpu")
     assert list(sd) == ["weight"] and tuple(sd["weight"].shape) == (512, 12) and bool(torch.isfinite(sd["weight"]).all())
-    resume = dict(cfg, BACKBONE_RESUME_ROOT=_ckpt(b1_dir, "Backbone_IR_50_ReStyle_Epoch_1_Batch_6_"),
-                  HEAD_RESUME_ROOT=_ckpt(b1_dir, "Head_MagFace_Epoch_1_Batch_6_"),
-                  OPTIMIZER_RESUME_ROOT=_ckpt(b1_dir, "Optimizer_MagFace_Epoch_1_Batch_6_"),
-                  STATE_RESUME_ROOT=_ckpt(b1_dir, "State_MagFace_Epoch_1_Batch_6_"))
-    b2_dir, log = _run_train(tmp_path, "second", resume)
-    assert "Resuming at epoch 1 batch 6" in log and "Loading Optimizer Checkpoint" in log
-    for prefix in ("Backbone_IR_50_ReStyle_Epoch_2_Batch_12_", "Head_MagFace_Epoch_2_Batch_12_"):
-        sa = torch.load(_ckpt(a_dir, prefix), map_location="cpu")
-        sb = torch.load(_ckpt(b2_dir, prefix), map_location="cpu")
-        assert list(sa.keys()) == list(sb.keys())
-        for key in sa:
-            assert torch.equal(sa[key], sb[key]), (prefix, key, float((sa[key].float() - sb[key].float()).abs().max()))
-    oa = torch.load(_ckpt(a_dir, "Optimizer_MagFace_Epoch_2_Batch_12_"), map_location="cpu")
-    ob = torch.load(_ckpt(b2_dir, "Optimizer_MagFace_Epoch_2_Batch_12_"), map_location="cpu")
-    for key in oa["state"]:
-        assert torch.equal(oa["state"][key]["momentum_buffer"], ob["state"][key]["momentum_buffer"]), key

@@ -11,9 +11,10 @@ import re
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
+import head_support as HS
 from frhip import synth
+from head_support import float64_reference, maxrel, relerr, run
 
 pytestmark = pytest.mark.gpu
 
@@ -50,29 +51,6 @@ def make(kind, D, N, w, it=10000, **kw):
     with torch.no_grad():
         param_of(head).copy_(w)
     return head
-
-
-def run(head, x, label, gout):
-    """(logits, gx, gw) of one forward + backward, on whatever device x is on."""
-    x = x.clone().requires_grad_(True)
-    param_of(head).grad = None
-    y = head(x, label.to(x.device))
-    y.backward(gout.to(device=x.device, dtype=y.dtype))
-    return y.detach().cpu(), x.grad.cpu(), param_of(head).grad.cpu()
-
-
-def float64_reference(head, x, label, gout):
-    """The host restatement in float64 on a copy of the module (same iter: the copy's forward counts for itself)."""
-    h = copy.deepcopy(head).cpu().double()
-    return run(h, x.double().cpu(), label.cpu(), gout.double().cpu())
-
-
-def maxrel(got, ref):
-    return float((got.double() - ref.double()).abs().max() / ref.double().abs().max())
-
-
-def relerr(got, ref):
-    return float((got.double() - ref.double()).norm() / ref.double().norm())
 
 
 @pytest.fixture(scope="module")
@@ -158,12 +136,7 @@ def test_no_aten_gemm_on_the_device_path(monkeypatch):
              make("am", D, N, synth.uniform(43, "mm.k", (D, N))).cuda()]
     x = synth.normal(43, "mm.x", (B, D)).cuda()
     label = synth.labels(43, "mm.y", B, N).cuda()
-
-    def boom(*a, **k):
-        raise AssertionError("ATen GEMM called on the HIP path")
-
-    for mod, name in ((torch, "mm"), (torch, "matmul"), (F, "linear"), (torch.Tensor, "mm"), (torch.Tensor, "__matmul__")):
-        monkeypatch.setattr(mod, name, boom)
+    HS.forbid_aten_gemm(monkeypatch)
     for head in heads:
         xx = x.clone().requires_grad_(True)
         y = head(xx, label)
@@ -209,65 +182,24 @@ def test_reproducible_labels_checked_and_empty_batch(kind, monkeypatch):
 # ------------------------------------------------------------------------------------------------ train.py
 
 
-def _run_train(tmp, tag, extra_cfg, max_steps=0):
-    import subprocess
-    import sys
-    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "stylegan-for-facerec_amd")
-    env = dict(os.environ, PYTHONPATH=root)
-    argv = ["train.py", "--config", "configs/config_synthetic_smoke.py", "--synthetic", "12x10"]
-    if max_steps:
-        argv += ["--max-steps", str(max_steps)]
-    model_dir = tmp / tag
-    cfg_patch = ("import configs.config_synthetic_smoke as c; c.configurations[1].update(BATCH_SIZE=20, NUM_EPOCH=2, "
-                 "MODEL_ROOT=r'%s', LOG_ROOT=r'%s', **%r)" % (model_dir, tmp / "log", extra_cfg))
-    code = "import sys, runpy; sys.argv=%r; %s; runpy.run_path('train.py', run_name='__main__')" % (argv, cfg_patch)
-    out = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    return model_dir, out.stdout
-
-
-def _ckpt(model_dir, prefix):
-    hits = sorted(f for f in os.listdir(model_dir) if f.startswith(prefix))
-    assert len(hits) == 1, (prefix, os.listdir(model_dir))
-    return os.path.join(model_dir, hits[0])
-
-
 @pytest.mark.parametrize("name,key,shape", [("SphereFace", "weight", (12, 512)), ("Am_softmax", "kernel", (512, 12))])
 def test_train_py_runs_with_the_head(tmp_path, name, key, shape):
     """HEAD_NAME = SphereFace / Am_softmax on the synthetic config: finite loss, precision reported, checkpoint in the
     reference's layout."""
-    d, out = _run_train(tmp_path, name, dict(HEAD_NAME=name), max_steps=3)
+    d, out = HS.run_train(tmp_path, name, dict(HEAD_NAME=name), max_steps=3)
     losses = [float(m.group(1)) for m in re.finditer(r"Training Loss ([0-9.eE+-]+|nan|inf) \(", out)]
     assert losses and all(np.isfinite(losses)), out[-2000:]
     assert "Prec@1" in out and "nan" not in out.lower()
-    sd = torch.load(_ckpt(d, "Head_%s_Epoch_1_Batch_3_" % name), map_location="cpu")
+    sd = torch.load(HS.ckpt(d, "Head_%s_Epoch_1_Batch_3_" % name), map_location="cpu")
     assert list(sd) == [key] and tuple(sd[key].shape) == shape and bool(torch.isfinite(sd[key]).all())
 
 
 def test_resume_continues_bit_for_bit_with_sphereface(tmp_path):
     """test_gpu_model.py::test_resume_continues_bit_for_bit with HEAD_NAME = 'SphereFace': 12 steps straight == 6 steps,
     stop, resume for 6.  SphereFace's lambda follows its forward counter, which the State_* file carries (head_iter)."""
-    cfg = dict(HEAD_NAME="SphereFace")
-    a_dir, a_log = _run_train(tmp_path, "straight", cfg)
-    assert "Training Loss" in a_log and "nan" not in a_log.lower()
-    b1_dir, _ = _run_train(tmp_path, "first", cfg, max_steps=6)
-    assert torch.load(_ckpt(b1_dir, "State_SphereFace_Epoch_1_Batch_6_"))["head_iter"] == 6
-    resume = dict(cfg, BACKBONE_RESUME_ROOT=_ckpt(b1_dir, "Backbone_IR_50_ReStyle_Epoch_1_Batch_6_"),
-                  HEAD_RESUME_ROOT=_ckpt(b1_dir, "Head_SphereFace_Epoch_1_Batch_6_"),
-                  OPTIMIZER_RESUME_ROOT=_ckpt(b1_dir, "Optimizer_SphereFace_Epoch_1_Batch_6_"),
-                  STATE_RESUME_ROOT=_ckpt(b1_dir, "State_SphereFace_Epoch_1_Batch_6_"))
-    b2_dir, log = _run_train(tmp_path, "second", resume)
-    assert "Resuming at epoch 1 batch 6" in log and "Loading Optimizer Checkpoint" in log
-    for prefix in ("Backbone_IR_50_ReStyle_Epoch_2_Batch_12_", "Head_SphereFace_Epoch_2_Batch_12_"):
-        sa = torch.load(_ckpt(a_dir, prefix), map_location="cpu")
-        sb = torch.load(_ckpt(b2_dir, prefix), map_location="cpu")
-        assert list(sa.keys()) == list(sb.keys())
-        for k in sa:
-            assert torch.equal(sa[k], sb[k]), (prefix, k, float((sa[k].float() - sb[k].float()).abs().max()))
-    oa = torch.load(_ckpt(a_dir, "Optimizer_SphereFace_Epoch_2_Batch_12_"), map_location="cpu")
-    ob = torch.load(_ckpt(b2_dir, "Optimizer_SphereFace_Epoch_2_Batch_12_"), map_location="cpu")
-    for k in oa["state"]:
-        assert torch.equal(oa["state"][k]["momentum_buffer"], ob["state"][k]["momentum_buffer"]), k
-    sa = torch.load(_ckpt(a_dir, "State_SphereFace_Epoch_2_Batch_12_"))
-    sb = torch.load(_ckpt(b2_dir, "State_SphereFace_Epoch_2_Batch_12_"))
+    r = HS.resumed(tmp_path, dict(HEAD_NAME="SphereFace"), "SphereFace")
+    assert "Training Loss" in r.a_log and "nan" not in r.a_log.lower()
+    assert torch.load(HS.ckpt(r.b1_dir, "State_SphereFace_Epoch_1_Batch_6_"))["head_iter"] == 6
+    sa = torch.load(HS.ckpt(r.a_dir, "State_SphereFace_Epoch_2_Batch_12_"))
+    sb = torch.load(HS.ckpt(r.b2_dir, "State_SphereFace_Epoch_2_Batch_12_"))
     assert sa["head_iter"] == sb["head_iter"] == 12

@@ -10,22 +10,21 @@ rows with planted ones, rows with 0 < gt < margin and rows in the ``gt <= 0`` br
 import copy
 import math
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+import head_support as HS
 import mv_softmax_data as MD
 from frhip import synth
+from head_support import Guarded, float64_reference, maxrel, relerr, run
 
 pytestmark = pytest.mark.gpu
 
 CASES = ("rand_am", "rand_arc", "built_am", "built_arc", "built_am_m05", "built_arc_m05")
 D = 512
-SENTINEL = -12345.0
-BAND = 4096  # floats on either side of a buffer (a multiple of 4: the interior keeps its 16-byte alignment)
 FORMS = [pytest.param(True, id="am"), pytest.param(False, id="arc")]
 
 
@@ -46,20 +45,6 @@ def make(N, k, is_am, margin=0.35, mv_weight=1.12, scale=32):
     with torch.no_grad():
         head.weight.copy_(k)
     return head
-
-
-def run(head, x, label, gout):
-    """(logits, gx, gweight) of one forward + backward, on whatever device x is on."""
-    x = x.clone().requires_grad_(True)
-    head.weight.grad = None
-    y = head(x, label.to(x.device))
-    y.backward(gout.to(device=x.device, dtype=y.dtype))
-    return y.detach().cpu(), x.grad.cpu(), head.weight.grad.cpu()
-
-
-def float64_reference(head, x, label, gout):
-    h = copy.deepcopy(head).cpu().double()
-    return run(h, x.double().cpu(), label.cpu(), gout.double().cpu())
 
 
 def device_rows(head, x, label):
@@ -89,14 +74,6 @@ def assert_rows(rowv, cos, x, k, label, is_am, margin, st):
     assert torch.equal(MD.from_cos(cos.double(), label, is_am, margin)[1]["count"], st["count"])
     hot = torch.zeros_like(cos, dtype=torch.bool).scatter_(1, label.view(-1, 1), True)
     assert torch.equal(((cos > rowv[1].view(-1, 1)) & ~hot).sum(1), st["count"])
-
-
-def maxrel(got, ref):
-    return float((got.double() - ref.double()).abs().max() / ref.double().abs().max())
-
-
-def relerr(got, ref):
-    return float((got.double() - ref.double()).norm() / ref.double().norm())
 
 
 @pytest.mark.parametrize("tag", CASES)
@@ -172,18 +149,6 @@ def test_baseline_size_logits_against_float64(is_am):
 
 
 # ------------------------------------------------------------------------------------------------ C ABI, guarded
-
-
-class Guarded(object):
-    """A sentinel-filled device buffer of ``shape`` between two sentinel-filled guard bands."""
-
-    def __init__(self, *shape):
-        n = int(np.prod(shape))
-        self.flat = torch.full((2 * BAND + n,), SENTINEL, device="cuda")
-        self.t = self.flat[BAND:BAND + n].view(*shape)
-
-    def assert_guards(self, what):
-        assert bool((self.flat[:BAND] == SENTINEL).all()) and bool((self.flat[-BAND:] == SENTINEL).all()), what
 
 
 ROWS = 9
@@ -293,18 +258,6 @@ def test_entry_points_on_hand_made_cosines(N, ld, is_am):
 # ------------------------------------------------------------------------------------------------ the pipeline
 
 
-def _profiled_names(fn):
-    from torch.profiler import ProfilerActivity, profile
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        fn()
-        torch.cuda.synchronize()
-    return [e.name for e in prof.events()]
-
-
-HOST_READS = ("aten::item", "aten::_local_scalar_dense")
-ATEN_GEMMS = ("aten::mm", "aten::addmm", "aten::matmul", "aten::bmm", "aten::linear")
-
-
 def test_forward_waits_for_no_host_read_and_calls_no_aten_gemm(monkeypatch):
     """torch.profiler over the forward pass (labels validated by the caller, as in train.py): no device-to-host copy, no
     scalar read, no ATen GEMM, and one row kernel (``mv_softmax_apply``; no rows launch); the same over forward + backward
@@ -316,27 +269,9 @@ def test_forward_waits_for_no_host_read_and_calls_no_aten_gemm(monkeypatch):
     head = make(N, k, True).cuda()
     xc, lc = x.cuda().requires_grad_(True), label.cuda()
     monkeypatch.setattr(FRF, "CHECK_LABELS", False)
-    head(xc, lc)  # first call: streams, allocator
-    torch.cuda.synchronize()
-    one = torch.ones(1, device="cuda")
-    control = _profiled_names(lambda: (one.item(), one.cpu(), torch.mm(xc.detach(), head.weight.detach())))
-    assert any(n in HOST_READS for n in control) and any("DtoH" in n for n in control), sorted(set(control))
-    assert "aten::mm" in control
-    names = _profiled_names(lambda: head(xc, lc))
-    bad = [n for n in names if n in HOST_READS or n in ATEN_GEMMS or "DtoH" in n or n.startswith("Cijk_")]
-    assert not bad, sorted(set(bad))
+    names = HS.assert_forward_stays_on_device(monkeypatch, head, xc, lc, head.weight)
     assert sum("mv_softmax_apply" in n for n in names) == 1, sorted(set(names))
     assert not any(r + "_rows" in n for n in names for r in ("npcface", "curricular", "magface", "adacos", "mv_softmax"))
-
-    def boom(*a, **kw):
-        raise AssertionError("ATen GEMM called on the HIP path")
-
-    for mod, name in ((torch, "mm"), (torch, "matmul"), (F, "linear"), (torch.Tensor, "mm"), (torch.Tensor, "__matmul__")):
-        monkeypatch.setattr(mod, name, boom)
-    y = head(xc, lc)
-    y.backward(torch.ones_like(y))
-    torch.cuda.synchronize()
-    assert torch.isfinite(xc.grad).all() and torch.isfinite(head.weight.grad).all()
 
 
 @pytest.mark.parametrize("is_am", FORMS)
@@ -400,59 +335,13 @@ def test_attributes_are_read_at_call_time():
 EPOCHS = 2  # of 6 steps each: the 12 steps of the sibling heads' tests
 
 
-def _run_train(tmp, tag, extra_cfg, max_steps=0):
-    import subprocess
-    import sys
-    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "stylegan-for-facerec_amd")
-    env = dict(os.environ, PYTHONPATH=root)
-    argv = ["train.py", "--config", "configs/config_synthetic_smoke.py", "--synthetic", "12x10"]
-    if max_steps:
-        argv += ["--max-steps", str(max_steps)]
-    model_dir = tmp / tag
-    cfg_patch = ("import configs.config_synthetic_smoke as c; c.configurations[1].update(BATCH_SIZE=20, NUM_EPOCH=%d, "
-                 "MODEL_ROOT=r'%s', LOG_ROOT=r'%s', **%r)" % (EPOCHS, model_dir, tmp / "log", extra_cfg))
-    code = "import sys, runpy; sys.argv=%r; %s; runpy.run_path('train.py', run_name='__main__')" % (argv, cfg_patch)
-    out = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    return model_dir, out.stdout
-
-
-def _ckpt(model_dir, prefix):
-    hits = sorted(f for f in os.listdir(model_dir) if f.startswith(prefix))
-    assert len(hits) == 1, (prefix, os.listdir(model_dir))
-    return os.path.join(model_dir, hits[0])
-
-
 @pytest.mark.parametrize("is_am", FORMS)
 def test_train_py_learns_and_resumes_bit_for_bit_with_mv_softmax(tmp_path, is_am):
     """HEAD_NAME = 'MV_Softmax' on the synthetic config (MV_IS_AM left at its default, or False): 12 steps with finite loss
     that decreases (the mean of the last three steps below the mean of the first three), the Head_* file with the key
     ``weight`` alone; and 12 steps straight == 6 steps, stop at the epoch boundary, resume for 6, bit for bit."""
     cfg = dict(HEAD_NAME="MV_Softmax") if is_am else dict(HEAD_NAME="MV_Softmax", MV_IS_AM=False)
-    a_dir, a_log = _run_train(tmp_path, "straight", cfg)
-    losses = [float(m.group(1)) for m in re.finditer(r"Training Loss ([0-9.eE+-]+|nan|inf) \(", a_log)]
-    print("losses per step:", is_am, losses)
-    assert len(losses) == 6 * EPOCHS and all(np.isfinite(losses)), a_log[-2000:]
+    losses, sd, sa, _ = HS.straight_and_resumed(tmp_path, cfg, "MV_Softmax", EPOCHS)
     assert sum(losses[-3:]) < sum(losses[:3]), losses
-    assert "Prec@1" in a_log and "nan" not in a_log.lower()
-    b1_dir, _ = _run_train(tmp_path, "first", cfg, max_steps=6)
-    sd = torch.load(_ckpt(b1_dir, "Head_MV_Softmax_Epoch_1_Batch_6_"), map_location="cpu")
     assert list(sd) == ["weight"] and tuple(sd["weight"].shape) == (512, 12) and bool(torch.isfinite(sd["weight"]).all())
-    resume = dict(cfg, BACKBONE_RESUME_ROOT=_ckpt(b1_dir, "Backbone_IR_50_ReStyle_Epoch_1_Batch_6_"),
-                  HEAD_RESUME_ROOT=_ckpt(b1_dir, "Head_MV_Softmax_Epoch_1_Batch_6_"),
-                  OPTIMIZER_RESUME_ROOT=_ckpt(b1_dir, "Optimizer_MV_Softmax_Epoch_1_Batch_6_"),
-                  STATE_RESUME_ROOT=_ckpt(b1_dir, "State_MV_Softmax_Epoch_1_Batch_6_"))
-    b2_dir, log = _run_train(tmp_path, "second", resume)
-    assert "Resuming at epoch 1 batch 6" in log and "Loading Optimizer Checkpoint" in log
-    last = "Epoch_%d_Batch_%d_" % (EPOCHS, 6 * EPOCHS)
-    for prefix in ("Backbone_IR_50_ReStyle_" + last, "Head_MV_Softmax_" + last):
-        sa = torch.load(_ckpt(a_dir, prefix), map_location="cpu")
-        sb = torch.load(_ckpt(b2_dir, prefix), map_location="cpu")
-        assert list(sa.keys()) == list(sb.keys())
-        for key in sa:
-            assert torch.equal(sa[key], sb[key]), (prefix, key, float((sa[key].float() - sb[key].float()).abs().max()))
     assert not torch.equal(sa["weight"], sd["weight"])  # the head went on moving after the resume
-    oa = torch.load(_ckpt(a_dir, "Optimizer_MV_Softmax_" + last), map_location="cpu")
-    ob = torch.load(_ckpt(b2_dir, "Optimizer_MV_Softmax_" + last), map_location="cpu")
-    for key in oa["state"]:
-        assert torch.equal(oa["state"][key]["momentum_buffer"], ob["state"][key]["momentum_buffer"]), key

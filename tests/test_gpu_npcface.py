@@ -9,23 +9,22 @@ copy of the module.  The batches are the constructed ones of tests/npcface_data.
 without a hard negative and rows with planted ones, none of them near a decision boundary."""
 import copy
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+import head_support as HS
 import npcface_data as ND
 from frhip import synth
+from head_support import Guarded, float64_reference, maxrel, relerr, run
 
 pytestmark = pytest.mark.gpu
 
 CASES = ("rand", "built", "built_m03", "built_t12")
 ATTRS = ("m0", "m1", "t", "a")
 D = 512
-SENTINEL = -12345.0
-BAND = 4096  # floats on either side of a buffer (a multiple of 4: the interior keeps its 16-byte alignment)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -49,20 +48,6 @@ def make(N, k, margin=0.5, scale=64, **attrs):
     return head
 
 
-def run(head, x, label, gout):
-    """(logits, gx, gkernel) of one forward + backward, on whatever device x is on."""
-    x = x.clone().requires_grad_(True)
-    head.kernel.grad = None
-    y = head(x, label.to(x.device))
-    y.backward(gout.to(device=x.device, dtype=y.dtype))
-    return y.detach().cpu(), x.grad.cpu(), head.kernel.grad.cpu()
-
-
-def float64_reference(head, x, label, gout):
-    h = copy.deepcopy(head).cpu().double()
-    return run(h, x.double().cpu(), label.cpu(), gout.double().cpu())
-
-
 def device_rows(head, x, label):
     """rowv [6, B] (gt, ctm, final, d final / d gt, avg, count) of the device forward pass, on the host."""
     from frhip import functional as FRF
@@ -76,14 +61,6 @@ def fp32_avg(x, k, label, margin):
     """avg of the hard negatives per row from fp32 cosines: the host fp32 path's value."""
     c = torch.mm(F.normalize(x), F.normalize(k, dim=0))
     return ND.from_cos(c, label, margin)[1]["avg"]
-
-
-def maxrel(got, ref):
-    return float((got.double() - ref.double()).abs().max() / ref.double().abs().max())
-
-
-def relerr(got, ref):
-    return float((got.double() - ref.double()).norm() / ref.double().norm())
 
 
 @pytest.mark.parametrize("tag", CASES)
@@ -160,18 +137,6 @@ def test_baseline_size_logits_and_counts_against_float64():
 
 
 # ------------------------------------------------------------------------------------------------ C ABI, guarded
-
-
-class Guarded(object):
-    """A sentinel-filled device buffer of ``shape`` between two sentinel-filled guard bands."""
-
-    def __init__(self, *shape):
-        n = int(np.prod(shape))
-        self.flat = torch.full((2 * BAND + n,), SENTINEL, device="cuda")
-        self.t = self.flat[BAND:BAND + n].view(*shape)
-
-    def assert_guards(self, what):
-        assert bool((self.flat[:BAND] == SENTINEL).all()) and bool((self.flat[-BAND:] == SENTINEL).all()), what
 
 
 def hand_made(N):
@@ -251,18 +216,6 @@ def test_entry_points_on_hand_made_cosines(N, ld):
 # ------------------------------------------------------------------------------------------------ the pipeline
 
 
-def _profiled_names(fn):
-    from torch.profiler import ProfilerActivity, profile
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        fn()
-        torch.cuda.synchronize()
-    return [e.name for e in prof.events()]
-
-
-HOST_READS = ("aten::item", "aten::_local_scalar_dense")
-ATEN_GEMMS = ("aten::mm", "aten::addmm", "aten::matmul", "aten::bmm", "aten::linear")
-
-
 def test_forward_waits_for_no_host_read_and_calls_no_aten_gemm(monkeypatch):
     """torch.profiler over the forward pass (labels validated by the caller, as in train.py): no device-to-host copy, no
     scalar read, no ATen GEMM; the same over forward + backward with torch.mm / matmul / F.linear raising.  The profiler
@@ -273,26 +226,8 @@ def test_forward_waits_for_no_host_read_and_calls_no_aten_gemm(monkeypatch):
     head = make(N, k).cuda()
     xc, lc = x.cuda().requires_grad_(True), label.cuda()
     monkeypatch.setattr(FRF, "CHECK_LABELS", False)
-    head(xc, lc)  # first call: streams, allocator
-    torch.cuda.synchronize()
-    one = torch.ones(1, device="cuda")
-    control = _profiled_names(lambda: (one.item(), one.cpu(), torch.mm(xc.detach(), head.kernel.detach())))
-    assert any(n in HOST_READS for n in control) and any("DtoH" in n for n in control), sorted(set(control))
-    assert "aten::mm" in control
-    names = _profiled_names(lambda: head(xc, lc))
-    bad = [n for n in names if n in HOST_READS or n in ATEN_GEMMS or "DtoH" in n or n.startswith("Cijk_")]
-    assert not bad, sorted(set(bad))
+    names = HS.assert_forward_stays_on_device(monkeypatch, head, xc, lc, head.kernel)
     assert any("npcface_rows" in n for n in names), sorted(set(names))
-
-    def boom(*a, **kw):
-        raise AssertionError("ATen GEMM called on the HIP path")
-
-    for mod, name in ((torch, "mm"), (torch, "matmul"), (F, "linear"), (torch.Tensor, "mm"), (torch.Tensor, "__matmul__")):
-        monkeypatch.setattr(mod, name, boom)
-    y = head(xc, lc)
-    y.backward(torch.ones_like(y))
-    torch.cuda.synchronize()
-    assert torch.isfinite(xc.grad).all() and torch.isfinite(head.kernel.grad).all()
 
 
 def test_reproducible_labels_checked_and_empty_batch(monkeypatch):
@@ -350,29 +285,6 @@ def test_attributes_are_read_at_call_time():
 EPOCHS = 4  # of 6 steps each; see test_train_py_learns_and_resumes_bit_for_bit_with_npcface
 
 
-def _run_train(tmp, tag, extra_cfg, max_steps=0):
-    import subprocess
-    import sys
-    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "stylegan-for-facerec_amd")
-    env = dict(os.environ, PYTHONPATH=root)
-    argv = ["train.py", "--config", "configs/config_synthetic_smoke.py", "--synthetic", "12x10"]
-    if max_steps:
-        argv += ["--max-steps", str(max_steps)]
-    model_dir = tmp / tag
-    cfg_patch = ("import configs.config_synthetic_smoke as c; c.configurations[1].update(BATCH_SIZE=20, NUM_EPOCH=%d, "
-                 "MODEL_ROOT=r'%s', LOG_ROOT=r'%s', **%r)" % (EPOCHS, model_dir, tmp / "log", extra_cfg))
-    code = "import sys, runpy; sys.argv=%r; %s; runpy.run_path('train.py', run_name='__main__')" % (argv, cfg_patch)
-    out = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    return model_dir, out.stdout
-
-
-def _ckpt(model_dir, prefix):
-    hits = sorted(f for f in os.listdir(model_dir) if f.startswith(prefix))
-    assert len(hits) == 1, (prefix, os.listdir(model_dir))
-    return os.path.join(model_dir, hits[0])
-
-
 def test_train_py_learns_and_resumes_bit_for_bit_with_npcface(tmp_path):
     """HEAD_NAME = 'NPCFace' on the synthetic config: 24 steps with finite loss that decreases (the mean of the last three
     steps below the mean of the first three), the Head_* file with the key ``kernel`` alone; and 24 steps straight == 6
@@ -384,30 +296,7 @@ def test_train_py_learns_and_resumes_bit_for_bit_with_npcface(tmp_path):
     33.5 over steps 1 .. 12, then 19.5 .. 21.1 over steps 13 .. 18 and 5.6 .. 11.9 over steps 19 .. 24 (Prec@1 45 .. 60 %);
     the head's plain-PyTorch arithmetic on the device in place of the HIP path gives the same curve (33.7 at step 12), so
     the rise is the head's, not the kernels'."""
-    cfg = dict(HEAD_NAME="NPCFace")
-    a_dir, a_log = _run_train(tmp_path, "straight", cfg)
-    losses = [float(m.group(1)) for m in re.finditer(r"Training Loss ([0-9.eE+-]+|nan|inf) \(", a_log)]
-    print("losses per step:", losses)
-    assert len(losses) == 6 * EPOCHS and all(np.isfinite(losses)), a_log[-2000:]
+    losses, sd, sa, _ = HS.straight_and_resumed(tmp_path, dict(HEAD_NAME="NPCFace"), "NPCFace", EPOCHS)
     assert sum(losses[-3:]) < sum(losses[:3]), losses
-    assert "Prec@1" in a_log and "nan" not in a_log.lower()
-    b1_dir, _ = _run_train(tmp_path, "first", cfg, max_steps=6)
-    sd = torch.load(_ckpt(b1_dir, "Head_NPCFace_Epoch_1_Batch_6_"), map_location="cpu")
     assert list(sd) == ["kernel"] and tuple(sd["kernel"].shape) == (512, 12) and bool(torch.isfinite(sd["kernel"]).all())
-    resume = dict(cfg, BACKBONE_RESUME_ROOT=_ckpt(b1_dir, "Backbone_IR_50_ReStyle_Epoch_1_Batch_6_"),
-                  HEAD_RESUME_ROOT=_ckpt(b1_dir, "Head_NPCFace_Epoch_1_Batch_6_"),
-                  OPTIMIZER_RESUME_ROOT=_ckpt(b1_dir, "Optimizer_NPCFace_Epoch_1_Batch_6_"),
-                  STATE_RESUME_ROOT=_ckpt(b1_dir, "State_NPCFace_Epoch_1_Batch_6_"))
-    b2_dir, log = _run_train(tmp_path, "second", resume)
-    assert "Resuming at epoch 1 batch 6" in log and "Loading Optimizer Checkpoint" in log
-    for prefix in ("Backbone_IR_50_ReStyle_Epoch_4_Batch_24_", "Head_NPCFace_Epoch_4_Batch_24_"):
-        sa = torch.load(_ckpt(a_dir, prefix), map_location="cpu")
-        sb = torch.load(_ckpt(b2_dir, prefix), map_location="cpu")
-        assert list(sa.keys()) == list(sb.keys())
-        for key in sa:
-            assert torch.equal(sa[key], sb[key]), (prefix, key, float((sa[key].float() - sb[key].float()).abs().max()))
     assert not torch.equal(sa["kernel"], sd["kernel"])  # the head went on moving after the resume
-    oa = torch.load(_ckpt(a_dir, "Optimizer_NPCFace_Epoch_4_Batch_24_"), map_location="cpu")
-    ob = torch.load(_ckpt(b2_dir, "Optimizer_NPCFace_Epoch_4_Batch_24_"), map_location="cpu")
-    for key in oa["state"]:
-        assert torch.equal(oa["state"][key]["momentum_buffer"], ob["state"][key]["momentum_buffer"]), key

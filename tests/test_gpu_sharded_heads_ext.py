@@ -3,7 +3,6 @@ torch, label -1 in the apply kernels, the one-rank module against the replicated
 sharing GPU 0, and train.py with SHARDED_HEAD=True for each head."""
 import math
 import os
-import subprocess
 import sys
 
 import pytest
@@ -12,11 +11,12 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import curricular_data as CD  # noqa: E402
+import head_support as HS  # noqa: E402
 from frhip import ops, synth  # noqa: E402
+from head_support import ckpt as _ckpt  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
-PRODUCT = os.path.join(REPO, "stylegan-for-facerec_amd")
 SHAPES = [(7, 33, 36), (64, 1001, 1004), (5, 1, 4)]
 HEADS = ("SphereFace", "Am_softmax", "CurricularFace")
 M = 0.5
@@ -223,51 +223,22 @@ def test_eval_mode_leaves_t_alone():
     assert float(crit.t) != float(torch.tensor(0.2))
 
 
-def _child(cmd, cwd, env, limit):
-    """A child process under its own ``timeout`` and a subprocess limit just above it."""
-    return subprocess.run(["timeout", "-k", "10", str(limit)] + cmd, cwd=cwd, env=env, capture_output=True, text=True,
-                          timeout=limit + 30)
-
-
 def test_two_ranks_sharing_one_gpu():
     _need_gpu()
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", "29583", os.path.join(HERE, "shard_ext_worker.py")]
-    out = _child(cmd, REPO, env, 300)
+    out = HS.child(cmd, REPO, env, 300)
     assert out.returncode == 0 and "SHARD_EXT_WORKER_OK" in out.stdout, out.stdout[-4000:] + out.stderr[-1500:]
 
 
 # ------------------------------------------------------------------------------------------------ train.py
 
 
-def _run_train(tmp, tag, extra_cfg, max_steps=0):
-    env = dict(os.environ, PYTHONPATH=PRODUCT)
-    argv = ["train.py", "--config", "configs/config_synthetic_smoke.py", "--synthetic", "12x10"]
-    if max_steps:
-        argv += ["--max-steps", str(max_steps)]
-    model_dir = tmp / tag
-    cfg_patch = ("import configs.config_synthetic_smoke as c; c.configurations[1].update(BATCH_SIZE=20, NUM_EPOCH=2, "
-                 "SHARDED_HEAD=True, MODEL_ROOT=r'%s', LOG_ROOT=r'%s', **%r)" % (model_dir, tmp / "log", extra_cfg))
-    code = "import sys, runpy; sys.argv=%r; %s; runpy.run_path('train.py', run_name='__main__')" % (argv, cfg_patch)
-    out = _child([sys.executable, "-c", code], PRODUCT, env, 300)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    assert "Training Loss" in out.stdout and "nan" not in out.stdout.lower()
-    return model_dir, out.stdout
-
-
-def _ckpt(model_dir, prefix):
-    hits = sorted(f for f in os.listdir(model_dir) if f.startswith(prefix))
-    assert len(hits) == 1, (prefix, os.listdir(model_dir))
-    return os.path.join(model_dir, hits[0])
-
-
-def _resume_cfg(name, d, batch):
-    tag = "Epoch_1_Batch_%d_" % batch
-    return dict(HEAD_NAME=name, BACKBONE_RESUME_ROOT=_ckpt(d, "Backbone_IR_50_ReStyle_" + tag),
-                HEAD_RESUME_ROOT=_ckpt(d, "Head_%s_%s" % (name, tag)),
-                OPTIMIZER_RESUME_ROOT=_ckpt(d, "Optimizer_%s_%s" % (name, tag)),
-                STATE_RESUME_ROOT=_ckpt(d, "State_%s_%s" % (name, tag)))
+def _sharded_train(tmp, tag, extra_cfg, max_steps=0):
+    model_dir, stdout = HS.run_train(tmp, tag, dict(extra_cfg, SHARDED_HEAD=True), max_steps=max_steps, limit=300)
+    assert "Training Loss" in stdout and "nan" not in stdout.lower()
+    return model_dir, stdout
 
 
 def _check_head_file(path, name):
@@ -284,7 +255,7 @@ def _check_head_file(path, name):
 
 def test_train_py_am_softmax(tmp_path):
     _need_gpu()
-    d, _ = _run_train(tmp_path, "am", dict(HEAD_NAME="Am_softmax"), max_steps=3)
+    d, _ = _sharded_train(tmp_path, "am", dict(HEAD_NAME="Am_softmax"), max_steps=3)
     sd = _check_head_file(_ckpt(d, "Head_Am_softmax_Epoch_1_Batch_3_"), "Am_softmax")
     assert list(sd) == ["kernel"] and tuple(sd["kernel"].shape) == (512, 12)
     osd = torch.load(_ckpt(d, "Optimizer_Am_softmax_Epoch_1_Batch_3_"), map_location="cpu")
@@ -293,11 +264,11 @@ def test_train_py_am_softmax(tmp_path):
 
 def test_train_py_sphereface_resume_restores_iter(tmp_path):
     _need_gpu()
-    d, _ = _run_train(tmp_path, "first", dict(HEAD_NAME="SphereFace"), max_steps=6)
+    d, _ = _sharded_train(tmp_path, "first", dict(HEAD_NAME="SphereFace"), max_steps=6)
     sd = _check_head_file(_ckpt(d, "Head_SphereFace_Epoch_1_Batch_6_"), "SphereFace")
     assert list(sd) == ["weight"] and tuple(sd["weight"].shape) == (12, 512)
     assert torch.load(_ckpt(d, "State_SphereFace_Epoch_1_Batch_6_"))["head_iter"] == 6
-    d2, log = _run_train(tmp_path, "second", _resume_cfg("SphereFace", d, 6))
+    d2, log = _sharded_train(tmp_path, "second", HS.resume_cfg(dict(HEAD_NAME="SphereFace"), d, "SphereFace"))
     assert "Resuming at epoch 1 batch 6" in log
     assert torch.load(_ckpt(d2, "State_SphereFace_Epoch_2_Batch_12_"))["head_iter"] == 12
 
@@ -307,19 +278,10 @@ def test_train_py_curricularface_resume_continues_bit_for_bit(tmp_path):
     straight == 6 steps, stop, resume for 6 -- backbone, kernel, t and momentum."""
     _need_gpu()
     cfg = dict(HEAD_NAME="CurricularFace")
-    a_dir, _ = _run_train(tmp_path, "straight", cfg)
-    b1_dir, _ = _run_train(tmp_path, "first", cfg, max_steps=6)
+    a_dir, _ = _sharded_train(tmp_path, "straight", cfg)
+    b1_dir, _ = _sharded_train(tmp_path, "first", cfg, max_steps=6)
     sd = _check_head_file(_ckpt(b1_dir, "Head_CurricularFace_Epoch_1_Batch_6_"), "CurricularFace")
     assert sorted(sd) == ["kernel", "t"] and tuple(sd["kernel"].shape) == (512, 12) and float(sd["t"]) != 0.0
-    b2_dir, log = _run_train(tmp_path, "second", _resume_cfg("CurricularFace", b1_dir, 6))
+    b2_dir, log = _sharded_train(tmp_path, "second", HS.resume_cfg(cfg, b1_dir, "CurricularFace"))
     assert "Resuming at epoch 1 batch 6" in log and "Loading Optimizer Checkpoint" in log
-    for prefix in ("Backbone_IR_50_ReStyle_Epoch_2_Batch_12_", "Head_CurricularFace_Epoch_2_Batch_12_"):
-        sa = torch.load(_ckpt(a_dir, prefix), map_location="cpu")
-        sb = torch.load(_ckpt(b2_dir, prefix), map_location="cpu")
-        assert list(sa.keys()) == list(sb.keys())
-        for k in sa:
-            assert torch.equal(sa[k], sb[k]), (prefix, k, float((sa[k].float() - sb[k].float()).abs().max()))
-    oa = torch.load(_ckpt(a_dir, "Optimizer_CurricularFace_Epoch_2_Batch_12_"), map_location="cpu")
-    ob = torch.load(_ckpt(b2_dir, "Optimizer_CurricularFace_Epoch_2_Batch_12_"), map_location="cpu")
-    for k in oa["state"]:
-        assert torch.equal(oa["state"][k]["momentum_buffer"], ob["state"][k]["momentum_buffer"]), k
+    HS.assert_same_checkpoints(a_dir, b2_dir, "CurricularFace", "Epoch_2_Batch_12_")
