@@ -60,7 +60,11 @@ enum {
   FR_EPI_STATS_X = 8,   /* FR_EPI_STATS + part[.][2][n] = sum_rows out*aux: the cross moment with the residual input (aux), from
                            which fr_bn_finalize_res derives the statistics of a*out + b + aux; part rows are [3][N] */
   FR_EPI_SLAB = 6       /* split-K slice z stores its fp32 partial (+bias in slice 0) to out[z][rows][ldc]: the caller
-                           adds the splitk slabs with fr_reduce_parts(out, splitk, 1, rows*ldc, ...) -- reproducible */
+                           adds the splitk slabs with fr_reduce_parts(out, splitk, 1, rows*ldc, ...) -- reproducible.
+                           The cut: with nk = KH*KW*SC/32 K steps of 32 channels (tap-major, then channels), slice z sums the
+                           steps [nk*z/splitk, nk*(z+1)/splitk) in integer division -- uneven where splitk does not divide nk
+                           (nk = 7, splitk = 3: 2, 2 and 3 steps).  splitk <= 1: one slab, all steps, with the bias.  The
+                           columns N..ldc of a slab row are not written (tests/test_gpu_exact_output.py pins all of this) */
 };
 
 /* The BatchNorm arguments of fr_bn_finalize as a struct (fr_bn_finalize_res takes two of them). */
@@ -181,7 +185,8 @@ typedef struct FrWgradArgs {
   const float* pro_b;
   float* slab;     /* [nsplit][Cout][taps][SC] fp32 partial gradients: required by fr_conv_wgrad_strip; optional for
                       fr_conv_wgrad (NULL: pixel slices are combined with fp32 atomics onto a zeroed dw; non-NULL: each
-                      slice stores its slab and a second launch adds them in a fixed order -- reproducible) */
+                      slice stores its slab and a second launch adds them in a fixed order -- reproducible; dw is then
+                      OVERWRITTEN with the sum of the slabs, whatever it held) */
   /* Deferred slab sum (fr_conv_wgrad_strip only; fr_conv_wgrad ignores these fields).  defer != 0:
    * this launch only writes its slabs; the caller owes them a sum -- either as the prev_* of a later deferring launch
    * on the same stream (whose workgroups add them while their first tiles are in flight: no launch of their own) or

@@ -12,8 +12,11 @@ squeeze-excite squeezes and backward) are chains of fmaf and sums of the same ki
 intermediate is an fp32 number and every sum is exact in any order, so they are pinned the same way (second half of the
 references below; the recipes assert their own preconditions before anything is compared).
 
-A plain helper module (like shard_ref.py), used by test_exact_operands_host.py (no GPU), test_gpu_exact_conv.py and
-test_gpu_exact_elementwise.py.
+The GEMMs of the output layer (Linear forward in K slices, data and weight gradient on the fp32 master weight, the split-K
+slab epilogue) and the Flatten-order hand-over in front of them are the third group (last section; test_gpu_exact_output.py).
+
+A plain helper module (like shard_ref.py), used by test_exact_operands_host.py (no GPU), test_gpu_exact_conv.py,
+test_gpu_exact_elementwise.py and test_gpu_exact_output.py.
 Layout: activations NHWC ``[B, H, W, C]``, weights packed ``[O][kh*kw][I]`` -- what the C ABI takes.
 """
 import math
@@ -302,7 +305,11 @@ EW_SHAPES = [(3, 5, 7, 64, 7),       # 105 rows: below one block trip, idle bloc
              (37, 2, 6, 512, 5),     # many 12-row images
              (1, 2, 2, 64, 1),       # fewer rows than row-threads
              (2, 4, 4, 1024, 4),     # one row-thread per trip
-             (2, 3, 3, 2048, 2)]     # bf16 only, not lean-eligible: the general kernel
+             (2, 3, 3, 2048, 2),     # bf16 only, not lean-eligible: the general kernel
+             # BatchNorm1d of the output layer: [B][512] rows with H = W = 1, nblocks = ops.grid_blocks(B, 512, FR_F32)
+             (2, 1, 1, 512, 1),      # the smallest training batch: one block, two of its rows live
+             (5, 1, 1, 512, 3),      # two rows per fp32 block: a ragged last block
+             (256, 1, 1, 512, 128)]  # the benchmark's batch
 SCATTER_SHAPES = [(3, 6, 10, 64), (2, 4, 2, 128), (5, 14, 14, 256)]   # add_kind 2, stride 2 (lean bf16 / general fp32)
 SCATTER_S3 = (2, 9, 6, 64)                                            # add_kind 2, stride 3: the general kernel
 STATS_LONG = (2, 56, 56, 64, 5)                                       # HW = 3136: many trips per thread
@@ -544,3 +551,184 @@ def se_bwd_case(B, H, C, zero_w1=False, seed=239):
         (bn[:, 1], (sd * GX).abs() + (gpooled * XH).abs(), qp / 2)])
     assert float((gh != 0).double().mean()) > 0.2 and float((o["hidden"] == 0).double().mean()) > 0.3, what + ": the ReLU mask"
     return o, dict(gs=gs, gz=gz, gh=gh, gpooled=gpooled, dw1=dw1, dw2=dw2, parts=parts, bn=bn)
+
+
+# ------------------------------------------------------------------------------------------------------------ output-layer GEMMs
+# Linear(25088, 512) of the output layer (include/frhip.h: fr_linear_fwd / fr_linear_dgrad on the fp32 master weight, the dense
+# fr_conv_wgrad with taps = 1, FR_EPI_SLAB of fr_conv_igemm) and the Flatten-order hand-over from fr_bn_dropout_cm: operand recipes
+# and float64 references of test_gpu_exact_output.py.  a [B][K] and g [B][O] are ternary, W [O][K] is the fp32 master: half of it
+# zero, the rest small integers -- or, with frac, values around 1 that sit on and next to the ties of the fp32 -> bf16 rounding the
+# kernels do in registers.  The references round W with torch (W.to(torch.bfloat16): round to nearest even IS the specification).
+_T = 2.0 ** -8                       # half a bf16 step in [1, 2): 1 + _T is a tie
+FRAC_POS = [1.0 + _T,                # tie, down to the even neighbour 1
+            1.0 + 3 * _T,            # tie, up to the even neighbour 1 + 2^-6
+            1.0 + _T + 2.0 ** -16,   # just above a tie: 1 + 2^-7
+            1.0 + _T - 2.0 ** -16,   # just below it: 1
+            1.0 - _T / 2 - 2.0 ** -17,   # just below the tie under 1 (steps of 2^-8 there): 1 - 2^-8
+            1.0 - _T / 2]            # that tie: up to the even neighbour 1
+FRAC_ROUNDED = [1.0, 1.0 + 2.0 ** -6, 1.0 + 2.0 ** -7, 1.0, 1.0 - _T, 1.0]   # what bf16 makes of FRAC_POS: multiples of 2^-8
+FRAC_WEIGHTS = FRAC_POS + [-v for v in FRAC_POS]
+INT_WEIGHTS = [-2.0, -1.0, 1.0, 2.0]
+
+# (B, O, K, slices) of fr_linear_fwd: a workgroup owns 64 features x 256 rows x one K slice, a wave 64 rows, a K step is 32 wide,
+# a loop trip takes two steps (two register slots) and an odd step count ends in a tail; ksteps = K / 32 / slices
+LINEAR_REAL = (5, 512, 25088)        # the output layer's K and O; the batch is small: the reference is formed on the CPU
+LINEAR_FWD = [(1, 64, 32, 1),        # one step (the tail alone), one row: 255 clamped rows
+              (65, 64, 192, 2),      # ksteps = 3: one trip + the odd tail; one row into the second wave
+              (257, 128, 320, 2),    # ksteps = 5; a second 256-row block with one live row; two feature tiles
+              (256, 64, 128, 4),     # ksteps = 1 in four slices; exactly one full row block
+              (63, 512, 256, 1),     # ksteps = 8: trips only; all eight feature tiles; one row short of a wave
+              LINEAR_REAL + (16,),   # the real K at a slice count the library does not recommend: ksteps = 49, odd
+              LINEAR_REAL + (None,)]  # ... and at fr_linear_slices(512, 25088) (None: asked of the library; 28 -> ksteps = 28)
+LINEAR_FWD_ONE_HOT = [(64, 128, 256, 1), (64, 128, 256, 4), (257, 64, 192, 2)]
+# (B, O, K) of fr_linear_dgrad: a workgroup owns 128 columns of K x 128 rows, a wave 32 rows; the reduction runs over O in steps of
+# 32, four steps (ring slots) per trip
+LINEAR_DGRAD = [(1, 128, 128),       # one trip, one row
+                (33, 128, 384),      # one row into the second wave; three column blocks
+                (129, 256, 128),     # a second 128-row block with one live row; two trips
+                (128, 512, 256),     # exactly one full row block; four trips
+                LINEAR_REAL]         # the real shape: 196 column blocks
+LINEAR_DGRAD_ONE_HOT = [(129, 128, 256), (33, 512, 128)]
+# (B, Cout, SC, dtype) of the dense fr_conv_wgrad (taps = 1, GH = GW = 1): the batch is the reduction, 32 rows per step, rows past
+# it are masked; tiles Cout x SC: 128 x 128, 128 x 64 (SC < 128), 64 x 64 (Cout < 128), 64 x 32 (SC < 64)
+LINEAR_WGRAD = [s + (d,) for s in [(1, 64, 32),       # one row, 31 masked; the 64 x 32 tile
+                                   (31, 128, 64),     # one row short of a step; 128 x 64
+                                   (33, 64, 64),      # one row into a second step; 64 x 64
+                                   (256, 128, 128),   # eight full steps; 128 x 128
+                                   (40, 200, 512)]    # the head's dW = g^T a: Cout = 200 ends 56 rows short of its second tile
+                for d in ("bf16", "f32")] + [LINEAR_REAL + ("bf16",)]   # the output layer's own: 4 x 196 tiles
+# (M, N, SC, splitk, dtype) of fr_conv_igemm with FR_EPI_SLAB (1x1, RH = RW = 1): 128-row tiles, 64 columns wide at N <= 64, else
+# 128; ldc = N rounded up to 16
+SLAB_GEMM = [s + (d,) for s in [(37, 64, 224, 3),     # nk = 7 cut 2 + 2 + 3; the 64-wide tile; a ragged row tile
+                                (130, 200, 224, 3),   # the same cut; two row tiles; N = 200 in rows of ldc = 208
+                                (128, 512, 96, 1),    # splitk = 1: one slab with the bias; four column tiles, a full row tile
+                                (5, 200, 160, 5)]     # one step per slice
+             for d in ("bf16", "f32")] + [LINEAR_REAL + (49, "f32")]   # the engine's own launch on the fp32 path: 16 steps each
+FLATTEN_CASE = (3, 128, 49, 128)     # (B, C, HW, O): K = 6272
+
+
+def one_hot_rows(B, n, pick):
+    """[B][n] float32: row b holds a single 1 at column pick(b)."""
+    t = torch.zeros(B, n)
+    t[torch.arange(B), torch.tensor([pick(b) for b in range(B)])] = 1.0
+    return t
+
+
+def stride_pick(n, mult=37):
+    """pick(b) = mult * b mod n.  mult is odd: any 32 consecutive rows hit all 32 positions of a step of 32; which steps and
+    slots the rows of a geometry reach is asserted where the geometry is listed (test_exact_operands_host.py)."""
+    return lambda b: (mult * b) % n
+
+
+def normal_weight(O, K, seed=257):
+    """Weights for the one-hot tests, where nothing is summed and any finite, normal fp32 value is exact: N(0, 0.02^2) -- the
+    real weight scale -- with the frac list planted at every 7th element.  No subnormals, infinities or NaN (what the bf16 MFMA
+    makes of a subnormal is the hardware's business, and 0 * inf would poison a row)."""
+    W = (synth.normal(seed, "l.wn", (O, K)) * 0.02).reshape(-1)
+    W[W.abs() < 2.0 ** -100] = 0.02
+    n = W[::7].numel()
+    W[::7] = torch.tensor(FRAC_WEIGHTS, dtype=torch.float32).repeat(-(-n // len(FRAC_WEIGHTS)))[:n]
+    assert bool(torch.isfinite(W).all()) and float(W.abs().min()) >= 2.0 ** -100
+    return W.view(O, K).contiguous()
+
+
+def round_bf16(W):
+    """float64 values of the weight as the kernels use it."""
+    return W.to(torch.bfloat16).double()
+
+
+def linear_case(B, O, K, seed=251, frac=False, density=0.5, wdensity=0.5):
+    """Operands of Linear(K, O) at batch B: a [B][K] and g [B][O] ternary with `density` non-zeros, W [O][K] fp32 with `wdensity`
+    non-zeros from {-2, -1, 1, 2} (frac: from FRAC_WEIGHTS), bias integers in [-3, 3]; Wq = bf16(W) in float64.  Asserted here:
+    every forward output is a multiple of the quantum (1; frac: 2^-8) whose sum of magnitudes over ALL of K -- and with it every
+    partial sum of every slice, in any order -- is at most 2^23 quanta, and every weight-gradient element is an integer of at
+    most B."""
+    a, g = ternary(seed, "l.a", (B, K), density), ternary(seed, "l.g", (B, O), density)
+    W = pick(seed, "l.w", O * K, FRAC_WEIGHTS if frac else INT_WEIGHTS).view(O, K)
+    W = (W * (synth.uniform(seed, "l.wz", (O, K), 0.0, 1.0) < wdensity)).contiguous()
+    bias = small_ints(seed, "l.bias", (O,))
+    c = dict(B=B, O=O, K=K, a=a, g=g, W=W, bias=bias, Wq=round_bf16(W), frac=frac, quantum=_T if frac else 1.0)
+    what = "linear %s%s" % ((B, O, K), " frac" if frac else "")
+    full = linear_forward(c, 1)[0]
+    assert_exact_range(fp32=[(full, a.double().abs() @ c["Wq"].abs().t() + bias.double().abs(), c["quantum"])], what=what + " forward")
+    dw = linear_wgrad(c)
+    assert_exact_range(fp32=[(dw, g.double().abs().t() @ a.double().abs(), 1.0)], what=what + " weight gradient")
+    assert float(dw.abs().max()) <= B, what + ": a weight-gradient element beyond the batch"
+    assert K < 64 or float((full != 0).double().mean()) > 0.5, what + ": mostly zeros"
+    return c
+
+
+def k_slices(K, slices):
+    """fr_linear_fwd: `slices` equal K ranges."""
+    assert K % slices == 0
+    return [(s * (K // slices), (s + 1) * (K // slices)) for s in range(slices)]
+
+
+def splitk_cut(nk, splitk):
+    """FR_EPI_SLAB (include/frhip.h): slice z sums the K steps [nk*z/splitk, nk*(z+1)/splitk) -- as channel ranges of 32 per step."""
+    n = max(splitk, 1)
+    return [(32 * (nk * z // n), 32 * (nk * (z + 1) // n)) for z in range(n)]
+
+
+def linear_forward(c, slices=1, bias=True, cuts=None):
+    """[slices][B][O] float64: slab s = a[:, ks:ke] @ Wq[:, ks:ke].T, plus the bias in slab 0 ONLY.  cuts: the K ranges (default:
+    `slices` equal ones)."""
+    a, Wq = c["a"].double(), c["Wq"]
+    out = torch.stack([a[:, ks:ke] @ Wq[:, ks:ke].t() for ks, ke in (cuts or k_slices(c["K"], slices))], 0)
+    if bias:
+        out[0] += c["bias"].double()
+    return out
+
+
+def linear_dgrad(c):
+    """ga = g @ Wq [B][K], which the kernel stores as bf16: integers of at most 256 (so not with frac weights)."""
+    ga = c["g"].double() @ c["Wq"]
+    what = "linear %s data gradient" % ((c["B"], c["O"], c["K"]),)
+    assert_exact_range(stored=[ga], fp32=[(ga, c["g"].double().abs() @ c["Wq"].abs(), 1.0)], what=what)
+    return ga
+
+
+def linear_wgrad(c):
+    """dW = g^T a [O][K]."""
+    return c["g"].double().t() @ c["a"].double()
+
+
+def one_hot_forward(W, bias, picks, slices):
+    """[slices][B][O] float64 of fr_linear_fwd on one-hot rows: bf16(W[o][pick(b)]) in the slice that owns pick(b), 0 elsewhere,
+    the bias on top in slice 0 -- ONE fp32 add there (exact in float64, rounded once as the kernel's add is)."""
+    O, K = W.shape
+    Wq = round_bf16(W)
+    out = torch.zeros(slices, len(picks), O, dtype=torch.float64)
+    for b, k in enumerate(picks):
+        out[k // (K // slices), b] = Wq[:, k]
+    if bias is not None:
+        out[0] = (out[0] + bias.double()).float().double()
+    return out
+
+
+def flatten_case(B, C, HW, O, keep, p, seed=263):
+    """The hand-over BatchNorm2d -> Dropout -> Flatten -> Linear (backbone/model_irse.py:143-147) as a float64 torch module on NCHW
+    tensors: x [B, HW, C] ternary (NHWC), scale from {1, 2, -1} and shift from {-1, 0, 1}, keep [B][C*HW] the dropout mask in
+    Flatten order, W / g of linear_case(B, O, C*HW).  Returns the operands, a [B][C*HW] (what fr_bn_dropout_cm must write), f = a @
+    Wq^T, and autograd's gradients: gy [B, HW, C] (NHWC) for the BatchNorm output and dW.  Asserted: a holds integers -3 .. 3 times
+    1 / (1 - p) (p = 1/2: {0, +-2, +-4, +-6}), and what is stored as bf16 -- a, ga and gy -- keeps to integers of at most 256."""
+    K = C * HW
+    c = linear_case(B, O, K, seed)
+    x = ternary(seed, "f.x", (B, HW, C), 0.5)
+    scale, shift = prologue_coeffs(seed, "f.bn", C, "bn")
+    inv_keep = 1.0 / (1.0 - p)
+    y = (x.double() * scale.double() + shift.double()).permute(0, 2, 1).contiguous().requires_grad_(True)   # NCHW with H*W = HW
+    lin = torch.nn.Linear(K, O, bias=False, dtype=torch.float64)
+    with torch.no_grad():
+        lin.weight.copy_(c["Wq"])
+    a = torch.flatten(y * keep.view(B, C, HW).double() * inv_keep, 1)
+    f = lin(a)
+    gy, dW = torch.autograd.grad(f, [y, lin.weight], c["g"].double())
+    a, f, gy = a.detach(), f.detach(), gy.permute(0, 2, 1).contiguous()
+    what = "flatten hand-over %s p=%g" % ((B, C, HW, O), p)
+    allowed = torch.arange(-3, 4, dtype=torch.float64) * inv_keep
+    assert bool(torch.isin(a, allowed).all()) and float(a.abs().max()) == 3 * inv_keep, what + ": a outside its value set"
+    ga = c["g"].double() @ c["Wq"]
+    assert_exact_range(stored=[a, ga, gy], fp32=[(f, a.abs() @ c["Wq"].abs().t(), 1.0), (dW, c["g"].double().abs().t() @ a.abs(), 1.0)],
+                       what=what)
+    return dict(c, x=x, scale=scale, shift=shift), a, f, gy, dW

@@ -428,3 +428,200 @@ def test_elementwise_comparators_catch_planted_differences():
                   torch.stack([rows(0, 100), rows(99, 180)])):                 # one row counted twice
         with pytest.raises(AssertionError):
             X.assert_sums_equal(parts, want, "control")
+
+
+# ------------------------------------------------------------------------------------------------------------ output-layer GEMMs
+# The recipes of test_gpu_exact_output.py.  linear_case / linear_dgrad / flatten_case assert their own preconditions, so building
+# them at every listed geometry is the range check.  The real-K operands are built once for all tests of this file.
+import functools  # noqa: E402
+
+from test_gpu_dropout import host_keep_mask  # noqa: E402
+
+linear_case = functools.lru_cache(maxsize=None)(X.linear_case)
+
+
+def _fwd_shapes():
+    return sorted({s[:3] for s in X.LINEAR_FWD})
+
+
+def test_frac_weights_sit_on_the_ties_of_the_bf16_rounding():
+    """torch's cast is the specification: the list holds ties to either side and their neighbours, every value is an fp32 number,
+    and truncation would get three of the six wrong."""
+    w = torch.tensor(X.FRAC_POS, dtype=torch.float64)
+    assert torch.equal(w.float().double(), w)
+    assert X.round_bf16(w.float()).tolist() == X.FRAC_ROUNDED
+    assert X.round_bf16(-w.float()).tolist() == [-v for v in X.FRAC_ROUNDED]
+    trunc = (w.float().view(torch.int32) & -65536).view(torch.float32).double()
+    assert int((trunc != X.round_bf16(w.float())).sum()) == 3
+    assert 1.0 + 2.0 ** -8 in X.FRAC_WEIGHTS and 1.0 + 3 * 2.0 ** -8 in X.FRAC_WEIGHTS
+    assert 1.0 + 2.0 ** -8 + 2.0 ** -16 in X.FRAC_WEIGHTS and -(1.0 - 2.0 ** -9 - 2.0 ** -17) in X.FRAC_WEIGHTS
+
+
+def test_linear_operands_are_in_the_exact_range():
+    """Every geometry of the four lists: the forward sums (with frac too: quanta of 2^-8), the data gradient as bf16 integers,
+    the weight gradient; the cut of FR_EPI_SLAB covers all K steps once."""
+    for B, O, K in _fwd_shapes():
+        for frac in (False, True):
+            c = linear_case(B, O, K, frac=frac)
+            assert float((c["W"] == 0).double().mean()) == pytest.approx(0.5, abs=0.05) or K < 64
+            if frac:
+                assert set(c["W"].unique().tolist()) <= set(torch.tensor(X.FRAC_WEIGHTS + [0.0]).tolist())
+                assert not torch.equal(c["Wq"], c["W"].double()), "the cast changes nothing: test data"
+    for B, O, K in X.LINEAR_DGRAD:
+        ga = X.linear_dgrad(linear_case(B, O, K))
+        assert float(ga.abs().max()) >= 8 and float(ga.abs().max()) <= 256
+    for B, O, K, _ in X.LINEAR_WGRAD:
+        assert float(X.linear_wgrad(linear_case(B, O, K)).abs().max()) <= B
+    for M, N, SC, splitk, _ in X.SLAB_GEMM:
+        linear_case(M, N, SC)
+        linear_case(M, N, SC, frac=True)
+        cuts = X.splitk_cut(SC // 32, splitk)
+        assert cuts[0][0] == 0 and cuts[-1][1] == SC and all(a[1] == b[0] for a, b in zip(cuts, cuts[1:]))
+    assert [(e - b) // 32 for b, e in X.splitk_cut(7, 3)] == [2, 2, 3]
+    assert X.splitk_cut(3, 1) == [(0, 96)]
+    assert sum(s[:3] == X.LINEAR_REAL for s in X.LINEAR_FWD) == 2 and X.LINEAR_DGRAD.count(X.LINEAR_REAL) == 1
+    assert sum(s[:3] == X.LINEAR_REAL for s in X.LINEAR_WGRAD) == 1 and sum(s[:3] == X.LINEAR_REAL for s in X.SLAB_GEMM) == 1
+
+
+def test_linear_geometries_reach_the_edges_they_name():
+    """Step counts per slice of the forward list against the source's loop (two steps per trip, an odd tail), row counts against
+    the 256-row block and the 64-row wave; the data gradient against 128-row blocks and 32-row waves; the weight gradient's batches
+    against its 32-row steps and its four tiles."""
+    ksteps = [K // 32 // s for _, _, K, s in X.LINEAR_FWD if s]
+    assert {1, 3, 5, 8, 49} <= set(ksteps) and any(k >= 3 and k & 1 for k in ksteps)
+    assert {1, 65, 256, 257} <= {s[0] for s in X.LINEAR_FWD} and {64, 128, 512} <= {s[1] for s in X.LINEAR_FWD}
+    assert all(O % 64 == 0 and K % 32 == 0 and (s is None or (K // 32) % s == 0) for _, O, K, s in X.LINEAR_FWD)
+    assert {1, 33, 129, 128} <= {s[0] for s in X.LINEAR_DGRAD} and all(O % 128 == 0 and K % 128 == 0 for _, O, K in X.LINEAR_DGRAD)
+    assert {1, 31, 33, 256} <= {s[0] for s in X.LINEAR_WGRAD}
+    tiles = {(128 if co >= 128 else 64, (128 if sc >= 128 else 64) if co >= 128 else (64 if sc >= 64 else 32))
+             for _, co, sc, _ in X.LINEAR_WGRAD}
+    assert tiles == {(128, 128), (128, 64), (64, 64), (64, 32)}
+    assert any(co % 64 for _, co, _, _ in X.LINEAR_WGRAD)
+    assert {d for s in X.LINEAR_WGRAD for d in s[3:]} == {"bf16", "f32"} == {s[4] for s in X.SLAB_GEMM}
+    assert {64, 200, 512} <= {s[1] for s in X.SLAB_GEMM} and any(s[0] % 128 for s in X.SLAB_GEMM)
+    assert any(s[3] == 1 for s in X.SLAB_GEMM) and any((s[2] // 32) % s[3] for s in X.SLAB_GEMM)
+    assert X.LINEAR_REAL + (49, "f32") in X.SLAB_GEMM
+
+
+@pytest.mark.parametrize("B,O,K,slices", X.LINEAR_FWD_ONE_HOT)
+def test_one_hot_rows_of_the_forward_reach_every_position(B, O, K, slices):
+    """Between them the rows hit all 32 positions of a K step, both register slots of the forward kernel, and the first and the
+    last step of the first and of the last slice; the reference holds the rounded weight in the owning slice and the bias or zero
+    elsewhere."""
+    picks = [X.stride_pick(K)(b) for b in range(B)]
+    a = X.one_hot_rows(B, K, X.stride_pick(K))
+    assert torch.equal(a.sum(1), torch.ones(B)) and all(a[b, k] == 1 for b, k in enumerate(picks))
+    ksteps = K // 32 // slices
+    assert {k % 32 for k in picks} == set(range(32))
+    local = {(k // 32 // ksteps, k // 32 % ksteps) for k in picks}   # (slice, step within the slice)
+    assert {(0, 0), (0, ksteps - 1), (slices - 1, 0), (slices - 1, ksteps - 1)} <= local
+    assert {st & 1 for _, st in local} == ({0, 1} if ksteps > 1 else {0})
+    W, bias = X.normal_weight(O, K), X.small_ints(271, "oh.bias", (O,))
+    ref = X.one_hot_forward(W, bias, picks, slices)
+    plain = (a.double() @ X.round_bf16(W).t())
+    assert torch.equal(ref.sum(0).float(), (plain + bias.double()).float())   # added in float64, rounded once: fr_reduce_parts
+    for s in range(slices):
+        own = torch.tensor([k // (K // slices) == s for k in picks])
+        assert torch.equal(ref[s][~own], (bias.double() if s == 0 else torch.zeros(O, dtype=torch.float64)).expand(int((~own).sum()), O))
+    assert torch.equal(X.one_hot_forward(W, None, picks, slices).sum(0), plain)
+
+
+@pytest.mark.parametrize("B,O,K", X.LINEAR_DGRAD_ONE_HOT)
+def test_one_hot_rows_of_the_data_gradient_reach_every_position(B, O, K):
+    """The reduction of the data gradient runs over O: all 32 positions of a step, all four ring slots, the first and last step."""
+    picks = [X.stride_pick(O)(b) for b in range(B)]
+    assert {o % 32 for o in picks} == set(range(32))
+    steps = {o // 32 for o in picks}
+    assert {0, O // 32 - 1} <= steps and {s % 4 for s in steps} == {0, 1, 2, 3}
+
+
+def test_normal_weight_is_finite_and_normal():
+    W = X.normal_weight(128, 256)
+    assert bool(torch.isfinite(W).all()) and float(W.abs().min()) > 2.0 ** -100
+    assert 0.01 < float(W.std()) < 0.6
+    Wq = X.round_bf16(W)
+    assert not torch.equal(Wq, W.double()) and float((Wq - W.double()).abs().max()) <= 2.0 ** -8
+    assert set(X.FRAC_WEIGHTS) <= set(W.double().unique().tolist())
+
+
+@pytest.mark.parametrize("frac", [False, True])
+def test_linear_references_equal_torch_modules(frac):
+    """nn.Linear in float64 on the bf16-rounded weight: forward (the slabs added up), and autograd's input and weight gradients."""
+    B, O, K = 65, 64, 192
+    c = linear_case(B, O, K, frac=frac)
+    lin = torch.nn.Linear(K, O, dtype=torch.float64)
+    with torch.no_grad():
+        lin.weight.copy_(c["W"].to(torch.bfloat16))
+        lin.bias.copy_(c["bias"])
+    a = c["a"].double().requires_grad_(True)
+    out = lin(a)
+    for slices in (1, 2, 3):
+        assert torch.equal(X.linear_forward(c, slices).sum(0), out.detach())
+        assert torch.equal(X.linear_forward(c, slices, bias=False).sum(0) + c["bias"].double(), out.detach())
+        assert torch.equal(X.linear_forward(c, slices)[1:], X.linear_forward(c, slices, bias=False)[1:])   # the bias: slab 0 only
+    assert torch.equal(X.linear_forward(c, cuts=X.splitk_cut(K // 32, 4)).sum(0), out.detach())
+    ga, gw = torch.autograd.grad(out, [a, lin.weight], c["g"].double())
+    assert torch.equal(X.linear_wgrad(c), gw)
+    if not frac:
+        assert torch.equal(X.linear_dgrad(c), ga)
+
+
+def test_flatten_reference_equals_the_reference_module():
+    """flatten_case against nn.Sequential(Flatten, Linear) on the NCHW tensor with the dropout mask applied by hand, for both p;
+    a[b][c*HW + hw] is the BatchNorm output of pixel hw, channel c."""
+    B, C, HW, O = X.FLATTEN_CASE
+    for p in (0.5, 0.0):
+        keep = torch.from_numpy(host_keep_mask(0x5EED, B, C, HW, p))
+        assert float(keep.double().mean()) == pytest.approx(1.0 - p, abs=0.02)
+        o, a, f, gy, dW = X.flatten_case(B, C, HW, O, keep, p)
+        y = o["x"].double() * o["scale"].double() + o["shift"].double()             # [B, HW, C]
+        assert float(a[1, 5 * HW + 7]) == float(y[1, 7, 5]) * float(keep[1, 5 * HW + 7]) / (1.0 - p)
+        nchw = (y.permute(0, 2, 1).reshape(B, C, 7, 7) * keep.view(B, C, 7, 7) / (1.0 - p)).requires_grad_(True)
+        mod = torch.nn.Sequential(torch.nn.Flatten(), torch.nn.Linear(C * HW, O, bias=False, dtype=torch.float64))
+        with torch.no_grad():
+            mod[1].weight.copy_(o["Wq"])
+        out = mod(nchw)
+        assert torch.equal(out.detach(), f)
+        g_in, g_w = torch.autograd.grad(out, [nchw, mod[1].weight], o["g"].double())
+        assert torch.equal(g_w, dW)
+        assert torch.equal((g_in * keep.view(B, C, 7, 7) / (1.0 - p)).reshape(B, C, HW).permute(0, 2, 1), gy)
+
+
+def test_linear_range_checks_refuse_what_is_not_exact():
+    """A frac weight fed to the data-gradient recipe (ga would not be an integer), and a density at which the forward sums leave
+    2^23 quanta: the same shape passes at the default density."""
+    with pytest.raises(AssertionError):
+        X.linear_dgrad(linear_case(65, 64, 192, frac=True))
+    X.linear_case(1, 64, 50176, frac=True)
+    with pytest.raises(AssertionError) as e:
+        X.linear_case(1, 64, 50176, frac=True, density=1.0, wdensity=1.0)
+    assert "quanta" in str(e.value), str(e.value)
+
+
+def test_linear_comparators_catch_planted_differences():
+    """One element of one slab, a bias added to slice 1 as well, a dropped K step, a truncated weight."""
+    c = linear_case(65, 64, 192, frac=True)
+    ref = X.linear_forward(c, 2)
+    X.assert_equal_tensor(ref.float(), ref, "control", ("slice", "row", "feature"))
+    bad = ref.clone()
+    bad[1, 64, 3] += 2.0 ** -8
+    with pytest.raises(AssertionError) as e:
+        X.assert_equal_tensor(bad.float(), ref, "control", ("slice", "row", "feature"))
+    assert "1 of" in str(e.value) and "first at (1, 64, 3)" in str(e.value), str(e.value)
+    bad = ref.clone()
+    bad[1] += c["bias"].double()
+    assert not torch.equal(bad, ref)
+    with pytest.raises(AssertionError) as e:
+        X.assert_equal_tensor(bad.float(), ref, "control", ("slice", "row", "feature"))
+    assert "slice [1]" in str(e.value), str(e.value)
+    nz = int((c["bias"] != 0).sum())
+    assert "%d of" % (65 * nz) in str(e.value), str(e.value)   # every row of every feature with a bias
+    with pytest.raises(AssertionError):   # the sum of the slabs sees it too
+        X.assert_equal_tensor(bad.sum(0).float(), ref.sum(0), "control")
+    dropped = ref.clone()
+    dropped[1] -= c["a"].double()[:, 160:192] @ c["Wq"][:, 160:192].t()   # the odd tail of ksteps = 3
+    with pytest.raises(AssertionError):
+        X.assert_equal_tensor(dropped.float(), ref, "control")
+    trunc = (c["W"].view(torch.int32) & -65536).view(torch.float32).double()
+    with pytest.raises(AssertionError):
+        X.assert_equal_tensor((c["a"].double() @ trunc.t() + c["bias"].double()).float(), ref.sum(0), "control")

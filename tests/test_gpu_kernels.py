@@ -1685,7 +1685,7 @@ def test_dropout_in_flatten_order_equals_the_nhwc_kernels(K, dname, B, C, HW, p)
     assert torch.equal(g0, out)
 
 
-@pytest.mark.parametrize("B,O,Kd", [(256, 512, 25088), (5, 512, 25088), (300, 128, 2048), (17, 128, 128)])
+@pytest.mark.parametrize("B,O,Kd", [(256, 512, 25088), (5, 512, 25088), (300, 128, 2048), (17, 128, 128), (257, 512, 4736)])
 def test_linear_on_the_master_weight(K, B, O, Kd):
     """fr_linear_fwd / fr_linear_dgrad (csrc/linear_gemm.hip): Linear(K, O) with the fp32 master weight as the GEMM operand
     (rounded to bf16 in registers), bf16 activations, fp32 accumulation -- against torch on the same rounded operands.
