@@ -685,6 +685,29 @@ int fr_circle_apply(const float* cos, const int64_t* label, float* out, int rows
 int fr_circle_bwd(const float* g, const float* cos, const int64_t* label, float* gcos, int rows, int N, int ld, int ldg,
                   float o_p, float o_n, float gamma, void* stream);
 
+/* ---- ArcNegFace (head/metrics.py:394-433) on the raw cosines cos [rows][ld] of the FR_EPI_STORE GEMM between
+ *      fr_row_normalize'd embeddings and the fr_row_normalize'd [N][D] weight.  The head never clamps its cosines and has
+ *      no state besides its weight. */
+/* replaces :418-433, the reference's loop over the rows with its two host reads per row.  Per row (every wave derives them
+ * from one load of the target cosine; the wave of column chunk 0 stores them), rowv [3][rows]:  gt = cos[m][label[m]];
+ * gt > thresh (:427-428; thresh is the largest float not above the reference's double cos(pi - margin), so that the
+ * comparison decides as the reference's does for every float gt): a = cos(acos(gt) + margin), d a / d gt =
+ * sin(acos(gt) + margin) / sqrt(1 - gt^2);  otherwise (:430, mm = sin(pi - margin) * margin): a = gt - mm, d a / d gt = 1.
+ * out[m][n] = s * (n == label[m] ? a[m] : t*c + t - 1), t = alpha * exp(-(c - a[m])^2 / sigma), c the raw cosine
+ * (:431-433); ld a multiple of 4, columns N..ld of out are written as 0.  Nothing is guarded: a raw target cosine above 1
+ * (1 + 2^-23 by rounding) makes acos, a and every t of the row NaN, and so the whole row of out, as in the reference; a raw
+ * negative beyond +-1 keeps its value.  A row whose label lies outside [0, N) has no target: rowv = 0, 0, 0, its t is
+ * exactly 1 (the reference's initial a = 0 and t_scale = 1) and out = s * c with the bits of c. */
+int fr_arcneg_apply(const float* cos, const int64_t* label, float* rowv, float* out, int rows, int N, int ld, float thresh,
+                    float margin, float mm, float alpha, float sigma, float s, void* stream);
+/* the backward of :418-433 with t and the branch constant (:431 .item(), :432 detach): gcos[m][n] = g[m][n] * s *
+ * (n == label[m] ? (d a / d gt)[m] : t), t recomputed from the raw cosine and rowv's a (no [rows][N] buffer of t is kept),
+ * whatever the raw cosine (no clamp, no pass mask); 0 in the padding columns N..ldg.  A row whose a is NaN is NaN in all
+ * its columns; a row without a target gets g * s with these bits.  g is [rows][N] contiguous, rowv as fr_arcneg_apply left
+ * it. */
+int fr_arcneg_bwd(const float* g, const float* cos, const int64_t* label, const float* rowv, float* gcos, int rows, int N,
+                  int ld, int ldg, float alpha, float sigma, float s, void* stream);
+
 /* ---- focal loss on the batch-mean cross entropy (loss/focal.py:17-21) + top-k (util/utils.py:343-358) */
 /* per row: lse[m], ce[m] = lse - z[label], rank[m] = #{n: z[n] > z[label]} */
 int fr_ce_rows(const float* logits, const int64_t* label, float* lse, float* ce, int32_t* rank, int rows, int N,

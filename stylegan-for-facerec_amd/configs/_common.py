@@ -20,7 +20,7 @@ def stage3(exp_name, **overrides):
         BACKBONE_NAME="IR_50_ReStyle",   # pSp IR-SE-50 trunk, with or without a Stage-2 encoder checkpoint
         HEAD_NAME="ArcFace",             # ArcFace | CosFace | SphereFace | Am_softmax | CurricularFace | MagFace | AdaCos | NPCFace
                                          # | MV_Softmax (MV_IS_AM=True: additive margin, the default; False: ArcFace-style)
-                                         # | CircleLoss | AM_Softmax (the FaceX-Zoo head; not Am_softmax)
+                                         # | CircleLoss | AM_Softmax (the FaceX-Zoo head; not Am_softmax) | ArcNegFace
         LOSS_NAME="Focal",               # Focal | Softmax
         ENCODER_CHECKPOINT=None,
         ENCODER_AVG_IMAGE="<an arbitrary 112x112 image here>",

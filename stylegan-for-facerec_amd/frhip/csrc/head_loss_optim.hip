@@ -812,6 +812,89 @@ __global__ __launch_bounds__(256) void mv_softmax_bwd_kernel(const float* __rest
   });
 }
 
+// ------------------------------------------------------------------------------------------ ArcNegFace
+// head/metrics.py:413-433 on the raw cosines of the FR_EPI_STORE GEMM; the head never clamps.  The reference fills its
+// logits in a loop over the rows with two host reads per row; each row's values depend on its target cosine alone, so, as
+// for MV_Softmax, there is no rows launch: every wave of arcneg_apply_kernel loads its row's target cosine (one address per
+// wave) and derives the same bits, and the wave of column chunk 0 leaves them in rowv [3][rows] for the backward pass: gt,
+// a, d a / d gt.  gt > thresh: a = cos(acos(gt) + margin), slope sin(acos(gt) + margin) / sqrt(1 - gt^2); otherwise a =
+// gt - mm, slope 1.  Unguarded as in the reference: gt > 1 makes acos, a and with them every t of the row NaN.  A row whose
+// label lies outside [0, N) has no target: 0, 0, 0, and its t is exactly 1 (the reference's initial a and t_scale).
+struct ArcNegRow {
+  float gt, a, da;
+};
+
+__device__ __forceinline__ ArcNegRow arcneg_row(const float* __restrict__ crow, long long lab, int N, float thresh,
+                                                float margin, float mm) {
+  ArcNegRow r = {0.f, 0.f, 0.f};
+  if (lab < 0 || lab >= N) return r;
+  const float gt = crow[lab];
+  r.gt = gt;
+  if (gt > thresh) {
+    const float th = acosf(gt) + margin;
+    r.a = cosf(th);
+    r.da = sinf(th) / sqrtf(1.0f - gt * gt);
+  } else {
+    r.a = gt - mm;
+    r.da = 1.f;
+  }
+  return r;
+}
+
+// t of a raw cosine, detached in the reference (:431-432): alpha * exp(-(c - a)^2 / sigma), nis = -1 / sigma.  At B = 256,
+// N = 28 000 the apply kernel runs at about 5 TB/s, so the arithmetic per element shows in its time: with expf and an fp32
+// division it took 13.4 us against mv_softmax_apply's 10.9 us; one multiply in place of the division (the same bits for
+// sigma = 2) and __expf (the hardware exp2; its argument lies in about [-2.5, 0] for cosines within +-1) bring it to 11.3 us
+// with the same measured errors (profiles/arcnegface_head_b256_n28000.txt).
+__device__ __forceinline__ float arcneg_t(float c, float a, float alpha, float nis) {
+  const float d = c - a;
+  return alpha * __expf(d * d * nis);
+}
+
+// out = s * (label ? a : t c + t - 1), c the raw cosine; a row without a target: out = s * c
+__global__ __launch_bounds__(256) void arcneg_apply_kernel(const float* __restrict__ cos, const long long* __restrict__ label,
+                                                           float* __restrict__ rowv, float* __restrict__ out, int rows,
+                                                           int N, int ld, float thresh, float margin, float mm,
+                                                           float alpha, float sigma, float s) {
+  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const long long lab = label[row];
+  const ArcNegRow r = arcneg_row(cos + (size_t)row * ld, lab, N, thresh, margin, mm);
+  if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) {
+    rowv[row] = r.gt;
+    rowv[rows + row] = r.a;
+    rowv[2 * rows + row] = r.da;
+  }
+  const bool has = lab >= 0 && lab < N;
+  const float a = r.a, nis = -1.0f / sigma;
+  margin_cols_fwd(cos, out, row, N, ld, [&](int n, float c) {
+    float v = c;
+    if (has) {
+      const float t = arcneg_t(c, a, alpha, nis);
+      v = n == lab ? a : t * c + t - 1.0f;
+    }
+    return v * s;
+  });
+}
+
+// gcos = g * s * (label ? d a / d gt : t), t recomputed from the raw cosine and rowv[1] (no [B, N] buffer of t is kept); t
+// and the branch are constants of the graph; no clamp, so no pass mask.  A row without a target: gcos = g * s
+__global__ __launch_bounds__(256) void arcneg_bwd_kernel(const float* __restrict__ g, const float* __restrict__ cos,
+                                                         const long long* __restrict__ label,
+                                                         const float* __restrict__ rowv, float* __restrict__ gcos, int rows,
+                                                         int N, int ld, int ldg, float alpha, float sigma, float s) {
+  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const long long lab = label[row];
+  const bool has = lab >= 0 && lab < N;
+  const float a = rowv[rows + row], dlab = rowv[2 * rows + row], nis = -1.0f / sigma;
+  margin_cols_bwd<false>(g, cos, gcos, row, N, ld, ldg, [&](int n, float c, float gg) {
+    float d = 1.f;
+    if (has) d = n == lab ? dlab : arcneg_t(c, a, alpha, nis);
+    return gg * s * d;
+  });
+}
+
 // ------------------------------------------------------------------------------------------ CircleLoss
 // head/metrics.py:451-473 on the raw cosines of the FR_EPI_STORE GEMM.  Element-wise after the clamp: no row values, no
 // rows launch.  The operations keep the reference's fp32 order, each rounded on its own (O_p - c, the clamp at 0, c - delta_p,
@@ -1317,6 +1400,24 @@ extern "C" int fr_mv_softmax_bwd(const float* g, const float* cos, const int64_t
     FR_UNSUPPORTED("fr_mv_softmax_bwd: shape (rows > 0, ldg >= ld >= N > 0, multiples of 4)");
   hipLaunchKernelGGL(mv_softmax_bwd_kernel, dim3(fr_margin_apply_parts(ldg), (rows + 3) / 4), dim3(256), 0,
                      (hipStream_t)stream, g, cos, (const long long*)label, rowv, gcos, rows, N, ld, ldg, w, s);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_arcneg_apply(const float* cos, const int64_t* label, float* rowv, float* out, int rows, int N, int ld,
+                               float thresh, float margin, float mm, float alpha, float sigma, float s, void* stream) {
+  if (rows <= 0 || N <= 0 || ld < N || ld % 4) FR_UNSUPPORTED("fr_arcneg_apply: shape (rows > 0, ld >= N > 0, ld a multiple of 4)");
+  hipLaunchKernelGGL(arcneg_apply_kernel, dim3(fr_margin_apply_parts(ld), (rows + 3) / 4), dim3(256), 0,
+                     (hipStream_t)stream, cos, (const long long*)label, rowv, out, rows, N, ld, thresh, margin, mm, alpha,
+                     sigma, s);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_arcneg_bwd(const float* g, const float* cos, const int64_t* label, const float* rowv, float* gcos,
+                             int rows, int N, int ld, int ldg, float alpha, float sigma, float s, void* stream) {
+  if (rows <= 0 || N <= 0 || ld < N || ld % 4 || ldg < ld || ldg % 4)
+    FR_UNSUPPORTED("fr_arcneg_bwd: shape (rows > 0, ldg >= ld >= N > 0, multiples of 4)");
+  hipLaunchKernelGGL(arcneg_bwd_kernel, dim3(fr_margin_apply_parts(ldg), (rows + 3) / 4), dim3(256), 0,
+                     (hipStream_t)stream, g, cos, (const long long*)label, rowv, gcos, rows, N, ld, ldg, alpha, sigma, s);
   FR_LAUNCH_CHECK();
 }
 

@@ -8,6 +8,7 @@ BASELINE.json is an fp32 bar (bf16 operands drift the logit
 import collections
 import math
 import os
+import struct
 
 import torch
 
@@ -30,7 +31,7 @@ def _pad(n, m):
 # One cosine-head pipeline under the heads.  Forward: ``_cosine_operands`` (normalised operands), the cosine GEMM
 # (``_raw_cosines``, or ArcFace / CosFace's fused margin epilogue), the head's row kernels.  Backward: the head's gcos
 # kernel, then ``_cosine_backward`` (both GEMMs and the normalisation backwards).
-ARCFACE, COSFACE, SPHEREFACE, AM_SOFTMAX, CURRICULAR, MAGFACE, ADACOS, NPCFACE, MV_SOFTMAX, CIRCLE, AM_SOFTMAX_N = range(11)
+ARCFACE, COSFACE, SPHEREFACE, AM_SOFTMAX, CURRICULAR, MAGFACE, ADACOS, NPCFACE, MV_SOFTMAX, CIRCLE, AM_SOFTMAX_N, ARCNEG = range(12)
 # 0..3: the kernels' margin kinds.  AM_SOFTMAX_N is the FaceX-Zoo AM_Softmax (normalised embeddings) on the kernels' kind 3.
 
 # What a forward call keeps for its backward call; a head leaves what it does not use at None.  xn / wn [Np, D] / wt
@@ -38,7 +39,8 @@ ARCFACE, COSFACE, SPHEREFACE, AM_SOFTMAX, CURRICULAR, MAGFACE, ADACOS, NPCFACE, 
 # cosines of the fused epilogue, cos the raw cosines [B, ld], rowv and t CurricularFace's row values and the t it used
 # (rowv: MagFace's and NPCFace's six row values and MV_Softmax's four too; t: the scale an AdaCos call used).  HeadCfg.mag:
 # MagFace's (margin_am, l_a, u_a, l_margin, u_margin, lamda); HeadCfg.p0 / p1: NPCFace's t / a; p0: MV_Softmax's mv_weight;
-# p0 / p1 / s: CircleLoss's O_p / O_n / gamma; p0 / p1: AM_Softmax's margin / scale, as Am_softmax's.
+# p0 / p1 / s: CircleLoss's O_p / O_n / gamma; p0 / p1: AM_Softmax's margin / scale, as Am_softmax's; p0 / p1 / s: ArcNegFace's
+# alpha / sigma / scale (rowv: its three row values).
 HeadSaved = collections.namedtuple("HeadSaved", "x w label xn wn wt inv_x inv_w cos_t cos rowv t", defaults=(None,) * 12)
 HeadCfg = collections.namedtuple("HeadCfg", "kind Np ld s cos_m sin_m th easy mi p0 p1 mag", defaults=(None,) * 9)
 
@@ -420,6 +422,47 @@ def am_softmax_n_backward(saved, cfg, g, need_x, need_w, raw_x_grad=False):
     return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, None if raw_x_grad else "normalize", col_weight=True)
 
 
+def arcneg_thresh32(thresh):
+    """The largest fp32 value not above the double ``thresh``.  The reference compares the fp32 target cosine with the
+    double cos(pi - margin) (head/metrics.py:427); for every fp32 ``gt``, ``gt > thresh`` in double and ``gt >`` this value in
+    fp32 decide alike."""
+    t32 = struct.unpack("f", struct.pack("f", float(thresh)))[0]  # rounded to nearest, on the host: no tensor is involved
+    if t32 > float(thresh):  # one ulp down: the integer before it in the order of the bit patterns, by sign
+        bits = struct.unpack("I", struct.pack("f", t32))[0]
+        bits = bits - 1 if t32 > 0 else (0x80000001 if t32 == 0 else bits + 1)
+        t32 = struct.unpack("f", struct.pack("I", bits))[0]
+    return t32
+
+
+def arcneg_forward(x, weight, label, s, arc):
+    """ArcNegFace logits (head/metrics.py:413-433) for fp32 device tensors; ``weight`` is [N, D], ``arc`` the head's
+    (thresh, margin, mm, alpha, sigma).  The reference's loop over the rows, with two host reads per row, is one row kernel:
+    every wave reads its row's target cosine gt, derives a (cos(acos(gt) + margin) where gt > thresh, else gt - mm) and
+    d a / d gt, writes s * a on the label column and s * (t c + t - 1), t = alpha * exp(-(c - a)^2 / sigma), off it, and
+    leaves rowv [3, B] (gt, a, d a / d gt) for the backward pass.  The cosines are never clamped.  Nothing waits on the
+    host.  A label outside [0, N) leaves its row at s * c.  Returns (logits, saved, cfg) for ``arcneg_backward``."""
+    sv, N, Np, ld = _cosine_operands(x, weight, label, norm_x=True, col_weight=False)
+    B = x.shape[0]
+    thresh, margin, mm, alpha, sigma = (float(v) for v in arc)
+    cos = _raw_cosines(sv, N, ld)
+    rowv = torch.empty(3, B, device=x.device)  # gt, a, d a / d gt
+    store, logits = _logit_store(sv, N, ld)
+    ops.call("fr_arcneg_apply", cos, sv.label, rowv, store, B, N, ld, arcneg_thresh32(thresh), margin, mm, alpha, sigma,
+             float(s), ops.current_stream_ptr())()
+    return logits, sv._replace(cos=cos, rowv=rowv), HeadCfg(ARCNEG, Np, ld, s=float(s), p0=alpha, p1=sigma)
+
+
+def arcneg_backward(saved, cfg, g, need_x, need_w, raw_x_grad=False):
+    """(gx, gweight) of ``arcneg_forward``; gweight is [N, D].  t and the branch are constants of the graph (:431-432); t is
+    recomputed from the saved raw cosines and the row's a; no cosine is masked out (the head never clamps).
+    ``raw_x_grad``: as in ``margin_backward``."""
+    B, N = saved.x.shape[0], saved.inv_w.shape[0]
+    gcos = torch.empty(B, cfg.Np, device=saved.x.device)
+    ops.call("fr_arcneg_bwd", g.contiguous().float(), saved.cos, saved.label, saved.rowv, gcos, B, N, cfg.ld, cfg.Np, cfg.p0,
+             cfg.p1, cfg.s, ops.current_stream_ptr())()
+    return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, None if raw_x_grad else "normalize", col_weight=False)
+
+
 def _head_fn(name, fwd, bwd, doc):
     """The autograd.Function of a head from its forward / backward pair; it takes the forward function's arguments (x,
     weight, label and up to four head-specific values)."""
@@ -487,6 +530,9 @@ CircleHeadFn = _head_fn("CircleHeadFn", circle_forward, circle_backward, """
 AMSoftmaxNHeadFn = _head_fn("AMSoftmaxNHeadFn", am_softmax_n_forward, am_softmax_n_backward, """
     The FaceX-Zoo AM_Softmax (head/metrics.py:371-392) on the HIP path; see ``am_softmax_n_forward``.""")
 
+ArcNegHeadFn = _head_fn("ArcNegHeadFn", arcneg_forward, arcneg_backward, """
+    ArcNegFace (head/metrics.py:394-433) on the HIP path; see ``arcneg_forward``.""")
+
 MagFaceHeadFn = _head_fn2("MagFaceHeadFn", magface_forward, magface_backward, """
     MagFace (head/metrics.py:512-553) on the HIP path: (logits, loss_g); see ``magface_forward``.""")
 
@@ -552,6 +598,11 @@ def circle_head(x, weight, label, o_p, o_n, delta_p, delta_n, gamma):
 def am_softmax_n_head(x, weight, label, m, s):
     """The FaceX-Zoo AM_Softmax logits; the empty batch and label check of ``margin_head``."""
     return _head_entry(AMSoftmaxNHeadFn, weight.shape[1], x, weight, label, m, s)
+
+
+def arcneg_head(x, weight, label, s, thresh, margin, mm, alpha, sigma):
+    """ArcNegFace logits; the empty batch and label check of ``margin_head``.  ``weight`` is [N, D]."""
+    return _head_entry(ArcNegHeadFn, weight.shape[0], x, weight, label, s, (thresh, margin, mm, alpha, sigma))
 
 
 def magface_head(x, kernel, label, s, margin_am, l_a, u_a, l_margin, u_margin, lamda):

@@ -4,9 +4,10 @@
     from head.metrics import CurricularFace, MagFace, AdaCos, NPCFace        (reference head/metrics.py:475, :512, :336, :592)
     from head.metrics import MV_Softmax                                      (reference head/metrics.py:555)
     from head.metrics import CircleLoss, AM_Softmax                          (reference head/metrics.py:435, :371)
+    from head.metrics import ArcNegFace                                      (reference head/metrics.py:394)
 
 The four heads the reference driver can select (``HEAD_NAME``, train.py:56,178-182) and ``CurricularFace`` / ``MagFace`` /
-``AdaCos`` / ``NPCFace`` / ``MV_Softmax`` / ``CircleLoss`` / ``AM_Softmax`` (seven of the FaceX-Zoo heads of the reference's
+``AdaCos`` / ``NPCFace`` / ``MV_Softmax`` / ``CircleLoss`` / ``AM_Softmax`` / ``ArcNegFace`` (eight of the FaceX-Zoo heads of the reference's
 head/metrics.py that its driver never names; train.py here accepts them) run on the HIP kernels when their input is a device tensor:
   * ``ArcFace`` / ``CosFace`` (the two heads the shipped configs and BASELINE.json name): row normalise -> MFMA cosine
     GEMM with the margin / label-select / scale epilogue -> closed-form backward;
@@ -43,9 +44,14 @@ head/metrics.py that its driver never names; train.py here accepts them) run on 
     the same cosines they give its bits.  No state besides ``weight``;
   * ``AM_Softmax`` (the FaceX-Zoo additive-margin head; not ``Am_softmax``): ``Am_softmax``'s row kernels on the cosines of
     NORMALISED embeddings, parameter ``weight``, margin 0.35 and scale 32 by default, and a feature gradient that goes back
-    through the row normalisation.  No state besides ``weight``.
+    through the row normalisation.  No state besides ``weight``;
+  * ``ArcNegFace``: rows of x and of the [num_class, feat_dim] ``weight`` normalised (no eps), raw cosines from the same
+    GEMM, never clamped.  One row kernel: every wave reads its row's target cosine ``gt``, derives ``a`` (cos(theta +
+    margin) where ``gt > thresh``, else ``gt - mm``) and writes ``scale * a`` on the label column and ``scale * (t c + t -
+    1)``, ``t = alpha * exp(-(c - a)^2 / sigma)``, off it; the backward pass recomputes ``t`` and treats it and the branch
+    as constants.  No state besides ``weight``.
 On host tensors ``SphereFace`` / ``Am_softmax`` / ``CurricularFace`` / ``MagFace`` / ``AdaCos`` / ``NPCFace`` / ``MV_Softmax`` /
-``CircleLoss`` / ``AM_Softmax`` run the reference's plain-PyTorch arithmetic (the
+``CircleLoss`` / ``AM_Softmax`` / ``ArcNegFace`` run the reference's plain-PyTorch arithmetic (the
 restatement the tests compare with); ``ArcFace`` / ``CosFace`` refuse host tensors.  ``SphereFace.iter`` counts forward
 calls on either path, as in the reference; train.py carries it across a resume in the State_* file.  ``CurricularFace.t``
 is a buffer: the Head_* file carries it.  ``AdaCos.scale`` is a non-persistent buffer (the reference's Head_* files have the
@@ -85,6 +91,14 @@ Differences from the reference that a caller can observe:
     copy of its cosine matrix through uint8 masks); on the device path a ``weight`` column of norm below 1e-12 is out of
     contract (no eps), as with the siblings.  A NaN cosine gives a NaN logit and gradient 0 on both paths (torch.clamp
     lets NaN through and passes no gradient there).
+  * ``ArcNegFace``: the reference fills its logits in a Python loop over the rows with two ``.item()`` host reads per row;
+    here neither path has a per-row loop or a host read, and the host path is a vectorised, out-of-place restatement that
+    gives the reference's fp32 logits bit for bit.  A label outside [0, N) raises through the shared label check on both
+    paths, where the reference's Python indexing would wrap -1 to the last class.  A ``weight`` row or an embedding of norm
+    below 1e-12 is out of contract (no eps, as in the reference).  The cosines are never clamped, as in the reference: a raw
+    target cosine above 1 by rounding (1 + 2^-23) makes acos NaN, and with it ``a``, every ``t`` of the row and so the
+    whole row of logits and gradients; a target cosine of exactly +1 makes the reference's own gradient infinite, and
+    nothing is done about it here either; a raw negative beyond +-1 keeps its value and its gradient ``scale * t``.
 """
 import math
 
@@ -473,3 +487,54 @@ class AM_Softmax(nn.Module):
         c = torch.mm(F.normalize(feats), F.normalize(weight, dim=0)).clamp(-1, 1)
         hot = torch.zeros_like(c).scatter_(1, labels.view(-1, 1).long(), 1).bool()
         return torch.where(hot, c - self.margin, c) * self.scale
+
+
+class ArcNegFace(nn.Module):
+    """ArcNegFace, "Towards Flops-constrained Face Recognition" (reference head/metrics.py:394-433): HIP kernels on device
+    tensors, plain PyTorch on the host.
+
+    With ``gt`` a row's target cosine (never clamped): the label column becomes ``a = cos(acos(gt) + margin)`` where ``gt >
+    thresh`` (``thresh = cos(pi - margin)``), else ``gt - mm``; every other column becomes ``t * c + t - 1`` with ``t =
+    alpha * exp(-(c - a)^2 / sigma)``, ``t`` and the ``a`` inside it constants of the graph; all times ``scale``.  The
+    reference fills its logits in a Python loop over the rows with two host reads per row; both paths here are vectorised
+    and read nothing on the host.  ``alpha``, ``sigma``, ``thresh``, ``mm``, ``margin`` and ``scale`` are plain attributes
+    read on every call; ``weight`` is [num_class, feat_dim] and the state dict holds that key alone.  Limits: see the module
+    docstring."""
+
+    def __init__(self, feat_dim, num_class, margin=0.5, scale=64):
+        super().__init__()
+        self.feat_dim = feat_dim
+        self.num_class = num_class
+        self.scale = scale
+        self.margin = margin
+        self.weight = Parameter(torch.empty(num_class, feat_dim))
+        self.reset_parameters()
+        self.alpha = 1.2
+        self.sigma = 2
+        self.thresh = math.cos(math.pi - self.margin)
+        self.mm = math.sin(math.pi - self.margin) * self.margin
+
+    def reset_parameters(self):
+        stdv = 1. / math.sqrt(self.weight.size(1))
+        self.weight.data.uniform_(-stdv, stdv)
+
+    def forward(self, feats, labels):
+        if feats.is_cuda:
+            _beside(self, self.weight, feats)
+            return FRF.arcneg_head(feats, self.weight, labels.to(feats.device), self.scale, self.thresh, self.margin,
+                                   self.mm, self.alpha, self.sigma)
+        if labels.numel():
+            FRF._check_labels(labels, self.weight.shape[0])
+        weight = self.weight.to(feats.device)
+        ex = feats / torch.norm(feats, 2, 1, keepdim=True)
+        ew = weight / torch.norm(weight, 2, 1, keepdim=True)
+        c = torch.mm(ex, ew.t())
+        at = labels.view(-1, 1).long()
+        gt = c.gather(1, at)
+        # the reference compares the fp32 value with the double thresh (:427); a tensor comparison would round thresh
+        thresh = FRF.arcneg_thresh32(self.thresh) if c.dtype == torch.float32 else self.thresh
+        branch = gt.detach() > thresh
+        arc = torch.cos(torch.acos(torch.where(branch, gt, torch.zeros_like(gt))) + self.margin)
+        a = torch.where(branch, arc, gt - self.mm)
+        t = (self.alpha * torch.exp(-torch.pow(c - a, 2) / self.sigma)).detach()
+        return self.scale * (t * c + t - 1).scatter(1, at, a)

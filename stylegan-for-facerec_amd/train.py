@@ -35,8 +35,8 @@ from frhip import functional as FRF
 from frhip import set_compute_dtype
 from frhip.optim import SGD, Adam
 from frhip.parallel import DataParallel
-from head.metrics import (AM_Softmax, AdaCos, Am_softmax, ArcFace, CircleLoss, CosFace, CurricularFace, MagFace, MV_Softmax,
-                          NPCFace, SphereFace)
+from head.metrics import (AM_Softmax, AdaCos, Am_softmax, ArcFace, ArcNegFace, CircleLoss, CosFace, CurricularFace, MagFace,
+                          MV_Softmax, NPCFace, SphereFace)
 from loss.focal import FocalLoss
 from util.utils import (AverageMeter, accuracy, buffer_val, collate_fn_ignore_none, get_time, get_val_data, perform_val,
                         schedule_lr, separate_irse_bn_paras, warm_up_lr)
@@ -132,14 +132,19 @@ NOT_SHARDED = {
     "CircleLoss": _ELEMENT_WISE,
     "AM_Softmax": _ELEMENT_WISE,
 }
+# Consulted after NOT_SHARDED: heads whose row values come from the target cosine alone.
+NOT_SHARDED_ROW_VALUE = {
+    "ArcNegFace": "its target cosines need an exchange of their own",
+}
 
 
 def check_head_config(cfg):
     """Refuse, before anything is built, a combination the driver does not serve."""
-    if cfg.get("SHARDED_HEAD", False) and cfg["HEAD_NAME"] in NOT_SHARDED:
-        name = cfg["HEAD_NAME"]
+    name = cfg["HEAD_NAME"]
+    why = NOT_SHARDED.get(name, NOT_SHARDED_ROW_VALUE.get(name))
+    if cfg.get("SHARDED_HEAD", False) and why is not None:
         raise NotImplementedError("SHARDED_HEAD=True with HEAD_NAME '%s': the class-sharded head does not serve %s (%s); run "
-                                  "it replicated, SHARDED_HEAD=False" % (name, name, NOT_SHARDED[name]))
+                                  "it replicated, SHARDED_HEAD=False" % (name, name, why))
 
 
 def main():
@@ -218,6 +223,7 @@ def main():
         # reference's own margin, weight and scale (0.35, 1.12, 32), as MagFace; MV_IS_AM=False: the ArcFace-style form
         heads["CircleLoss"] = CircleLoss(emb, num_class)  # after MV_Softmax, likewise; the reference's own margin 0.25, gamma 256
         heads["AM_Softmax"] = AM_Softmax(emb, num_class)  # after CircleLoss, likewise; the reference's own margin 0.35, scale 32
+        heads["ArcNegFace"] = ArcNegFace(emb, num_class)  # after AM_Softmax, likewise; the reference's own margin 0.5, scale 64
     head = heads[cfg["HEAD_NAME"]]
     if world > 1 and hasattr(head, "process_group") and not cfg.get("SHARDED_HEAD", False):
         # replicated CurricularFace: t follows the mean target cosine of the GLOBAL batch, as under the reference's

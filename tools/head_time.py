@@ -3,13 +3,13 @@ calls (mode fwdbwd) after 3 warm-up calls, event-timed; run it under `rocprofv3 
 kernel times (profiles/margin_heads_b256_n28000.txt).
 
     python tools/head_time.py {ArcFace|CosFace|SphereFace|Am_softmax|CurricularFace|MagFace|AdaCos|NPCFace|MV_Softmax|MV_Softmax-arc
-                               |CircleLoss|AM_Softmax} {fwd|fwdbwd} ITERS
+                               |CircleLoss|AM_Softmax|ArcNegFace} {fwd|fwdbwd} ITERS
 
 Several heads, comma separated, are timed in ONE process in alternating rounds (ROUNDS rounds of ITERS calls per head, the
 median round of each head reported, and the ratio to the first head named), so clocks and allocator state are shared
 (profiles/curricular_head_b256_n28000.txt, profiles/magface_head_b256_n28000.txt,
 profiles/adacos_head_b256_n28000.txt, profiles/npcface_head_b256_n28000.txt, profiles/mv_softmax_head_b256_n28000.txt,
-profiles/circle_heads_b256_n28000.txt; MV_Softmax is the additive-margin form, MV_Softmax-arc the ArcFace-style one):
+profiles/circle_heads_b256_n28000.txt, profiles/arcnegface_head_b256_n28000.txt; MV_Softmax is the additive-margin form, MV_Softmax-arc the ArcFace-style one):
 
     python tools/head_time.py Am_softmax,ArcFace,CurricularFace fwdbwd ITERS [ROUNDS]
 
@@ -36,7 +36,7 @@ gg = torch.full((B, 1), 1.0 / B).cuda()
 
 
 def make(name):
-    zoo = name in ("CurricularFace", "MagFace", "AdaCos", "NPCFace", "CircleLoss", "AM_Softmax")  # FaceX-Zoo heads: no device_id
+    zoo = name in ("CurricularFace", "MagFace", "AdaCos", "NPCFace", "CircleLoss", "AM_Softmax", "ArcNegFace")  # FaceX-Zoo heads: no device_id
     if name in ("MV_Softmax", "MV_Softmax-arc"):  # is_am is a required argument: the AM form, or the ArcFace-style one
         head = H.MV_Softmax(D, N, name == "MV_Softmax").cuda()
     else:
