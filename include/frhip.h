@@ -723,6 +723,29 @@ int fr_focal_finalize(const float* ce, const int32_t* rank, int rows, float gamm
 /* grad[m][n] = gup[0]*scalars[1]/rows * (exp(z-lse[m]) - [n==label[m]]) */
 int fr_focal_bwd(const float* logits, const int64_t* label, const float* lse, const float* scalars,
                  const float* gup, float* grad, int rows, int N, int ld, void* stream);
+/* replaces nn.CrossEntropyLoss() on the logits (train.py:237-238, :300-302; LOSS_NAME 'Softmax'): fr_focal_finalize
+ * without the modulation.  One workgroup; the batch mean l of ce is added as there (double, the same fixed order), so
+ * scalars[4] has the bits fr_focal_finalize leaves on the same ce.  scalars[0] = scalars[4] = l, scalars[1] = 1.0f exactly
+ * (fr_focal_finalize at gamma = 0 gives 0 * inf = NaN there when l is 0), [2] / [3] = prec@1 / @5 as there; slots 5..7 are
+ * not written.  With this layout fr_focal_bwd is the backward kernel.  rows > 0. */
+int fr_ce_finalize(const float* ce, const int32_t* rank, int rows, float* scalars, void* stream);
+
+/* ---- Softmax head (head/metrics.py:12-63): logits = F.linear(x, weight, bias), :33.  The GEMM is fr_conv_igemm (1x1,
+ *      FR_EPI_STORE with bias: the bias is added once, to the accumulated dot product) on the operands fr_pack_rows leaves,
+ *      run over N = pad(N, 4) columns so that the padding columns of the logit store are written as 0. */
+/* replaces nothing of the reference's arithmetic: lays out its operands.  w [rows][D] -> wp [rows_pad][D] (the rows from
+ * `rows` on zero) and wt [D][ldt], wt[d][r] = wp[r][d] for r < rows_pad (fr_row_normalize's two layouts without the normalisation,
+ * one launch); bias [rows] -> biasp [rows_pad] with zeros behind it (both may be NULL).  ldt >= rows_pad >= rows > 0, ldt
+ * a multiple of 4. */
+int fr_pack_rows(const float* w, const float* bias, float* wp, float* wt, float* biasp, int rows, int rows_pad, int D,
+                 int ldt, void* stream);
+/* out[m][n] = n < N ? g[m][n] : 0 for n < ldo: the upstream gradient g [rows][ldg] at the pitch the gradient GEMMs of
+ * F.linear's backward read (gx = g W, gW = g^T x), padding zero.  ldg >= N > 0, ldo >= N, ldo a multiple of 4. */
+int fr_pad_cols(const float* g, float* out, int rows, int N, int ldg, int ldo, void* stream);
+/* replaces the bias gradient of F.linear's backward (g.sum(0)): out[n] = ((g[0][n] + g[1][n]) + g[2][n]) + ... in fp32,
+ * the rows in order, every sum rounded: bit-defined, so a class shard gets the bits of its columns of the whole matrix.
+ * One thread per column.  g is [rows][ldg], ldg >= N > 0. */
+int fr_col_sums(const float* g, int rows, int N, int ldg, float* out, void* stream);
 
 /* ---- class-sharded softmax (the process-per-GPU form of the class-dimension split of
  *      head/metrics.py:104-113,170-179): every rank holds the logits of a contiguous class range [lo, hi) for ALL rows of

@@ -21,7 +21,8 @@ def stage3(exp_name, **overrides):
         HEAD_NAME="ArcFace",             # ArcFace | CosFace | SphereFace | Am_softmax | CurricularFace | MagFace | AdaCos | NPCFace
                                          # | MV_Softmax (MV_IS_AM=True: additive margin, the default; False: ArcFace-style)
                                          # | CircleLoss | AM_Softmax (the FaceX-Zoo head; not Am_softmax) | ArcNegFace
-        LOSS_NAME="Focal",               # Focal | Softmax
+                                         # | Softmax (the plain linear head with a bias)
+        LOSS_NAME="Focal",               # Focal | Softmax (nn.CrossEntropyLoss(): the batch-mean cross entropy, on the HIP path)
         ENCODER_CHECKPOINT=None,
         ENCODER_AVG_IMAGE="<an arbitrary 112x112 image here>",
         ENCODER_INPUT_SIZE=112,

@@ -8,6 +8,8 @@
 //   CurricularFace per-row margin, EMA of t, hard-negative re-weighting head/metrics.py:494-509
 //   MagFace magnitude-dependent margin, loss_g, label-column margin      head/metrics.py:533-552
 //   AdaCos row sums of exp(s cos), median target angle, the scale moved  head/metrics.py:359-368
+//   Softmax head: the operands of F.linear(x, W, b), the bias gradient  head/metrics.py:12-63
+//   nn.CrossEntropyLoss() on the rows of the cross entropy            train.py:237-238, :300-302
 //   FocalLoss on mean CE                                              loss/focal.py:17-21
 //   accuracy top-1/5                                                  util/utils.py:343-358
 //   optim.SGD(momentum, coupled weight decay on group 0)              train.py:196, :313-316
@@ -1024,6 +1026,91 @@ __global__ void focal_bwd_kernel(const float* __restrict__ z, const long long* _
   }
 }
 
+// nn.CrossEntropyLoss() on the rows of ce_rows_kernel (train.py:237-238, :300-302): focal_finalize_kernel without the
+// modulation.  The batch mean is added as there (double, the same fixed order), so scalars[4] has the same bits on the same
+// ce; scalars[1], the slope focal_bwd_kernel multiplies by, is exactly 1 (focal_finalize_kernel at gamma = 0 computes
+// 0 * powf(0, -1) = NaN there when the mean is 0).
+__global__ void ce_finalize_kernel(const float* __restrict__ ce, const int* __restrict__ rank, int rows,
+                                   float* __restrict__ scalars) {
+  __shared__ double dred[4];
+  __shared__ int r1[4], r5[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  double s = 0.0;
+  int c1 = 0, c5 = 0;
+  for (int i = tid; i < rows; i += 256) {
+    s += (double)ce[i];
+    c1 += rank[i] < 1;
+    c5 += rank[i] < 5;
+  }
+  s = wave_sum_d(s);
+  const float f1 = wave_sum((float)c1), f5 = wave_sum((float)c5);
+  if (lane == 0) {
+    dred[wave] = s;
+    r1[wave] = (int)f1;
+    r5[wave] = (int)f5;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const float l = (float)((dred[0] + dred[1] + dred[2] + dred[3]) / rows);
+    scalars[0] = l;
+    scalars[1] = 1.0f;
+    scalars[2] = 100.0f * (float)(r1[0] + r1[1] + r1[2] + r1[3]) / rows;
+    scalars[3] = 100.0f * (float)(r5[0] + r5[1] + r5[2] + r5[3]) / rows;
+    scalars[4] = l;
+  }
+}
+
+// ------------------------------------------------------------------------------------------ Softmax head (linear + bias)
+// head/metrics.py:12-63.  The GEMM operands of an [N][D] weight that is NOT normalised: wp [rows_pad][D] (rows >= N zero)
+// and its transpose wt [D][ldt] (columns >= N zero), both written coalesced from one 64 x 64 LDS tile; biasp [rows_pad] is
+// the bias with zeros behind it, so that the GEMM's bias epilogue may run over the padding columns of the logit store.
+__global__ __launch_bounds__(256) void pack_rows_kernel(const float* __restrict__ w, const float* __restrict__ bias,
+                                                        float* __restrict__ wp, float* __restrict__ wt,
+                                                        float* __restrict__ biasp, int rows, int rows_pad, int D, int ldt) {
+  __shared__ float tt[64][65];
+  const int d0 = blockIdx.x * 64, r0 = blockIdx.y * 64, tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  for (int j = ty; j < 64; j += 4) {
+    const int r = r0 + j, d = d0 + tx;
+    const float v = (r < rows && d < D) ? w[(size_t)r * D + d] : 0.f;
+    tt[j][tx] = v;
+    if (r < rows_pad && d < D) wp[(size_t)r * D + d] = v;
+  }
+  __syncthreads();
+  for (int j = ty; j < 64; j += 4) {
+    const int d = d0 + j, r = r0 + tx;
+    if (d < D && r < rows_pad) wt[(size_t)d * ldt + r] = tt[tx][j];
+  }
+  if (biasp && blockIdx.x == 0 && ty == 0 && r0 + tx < rows_pad)
+    biasp[r0 + tx] = (bias && r0 + tx < rows) ? bias[r0 + tx] : 0.f;
+}
+
+// out[m][n] = n < N ? g[m][n] : 0 for n < ldo: the upstream gradient at the pitch the two gradient GEMMs read
+__global__ __launch_bounds__(256) void pad_cols_kernel(const float* __restrict__ g, float* __restrict__ out, int N, int ldg,
+                                                       int ldo) {
+  const int m = blockIdx.y;
+  for (int n = blockIdx.x * blockDim.x + threadIdx.x; n < ldo; n += gridDim.x * blockDim.x)
+    out[(size_t)m * ldo + n] = n < N ? g[(size_t)m * ldg + n] : 0.f;
+}
+
+// out[n] = ((g[0][n] + g[1][n]) + g[2][n]) + ...: one thread per column, the rows in order, each sum rounded to fp32 (the
+// bias gradient; bit-defined, so a shard of the columns gets the bits the whole matrix gives).  Neighbouring threads read
+// neighbouring columns; four loads are in flight per thread before their four additions.
+__global__ __launch_bounds__(256) void col_sums_kernel(const float* __restrict__ g, int rows, int N, int ldg,
+                                                       float* __restrict__ out) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  const float* p = g + n;
+  float acc = p[0];
+  int m = 1;
+  for (; m + 4 <= rows; m += 4) {
+    const float a = p[(size_t)m * ldg], b = p[(size_t)(m + 1) * ldg], c = p[(size_t)(m + 2) * ldg],
+                d = p[(size_t)(m + 3) * ldg];
+    acc = __fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(acc, a), b), c), d);
+  }
+  for (; m < rows; ++m) acc = __fadd_rn(acc, p[(size_t)m * ldg]);
+  out[n] = acc;
+}
+
 // rank-only (accuracy on arbitrary logits)
 __global__ __launch_bounds__(256) void rank_rows_kernel(const float* __restrict__ z, const long long* __restrict__ label,
                                                         int* __restrict__ rank, int N, int ld) {
@@ -1472,6 +1559,38 @@ extern "C" int fr_focal_bwd(const float* logits, const int64_t* label, const flo
   dim3 grid((N + 1023) / 1024, rows);
   hipLaunchKernelGGL(focal_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, logits, (const long long*)label,
                      lse, scalars, gup, grad, rows, N, ld);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_ce_finalize(const float* ce, const int32_t* rank, int rows, float* scalars, void* stream) {
+  if (rows <= 0 || !ce || !rank || !scalars) FR_UNSUPPORTED("fr_ce_finalize: ce, rank, scalars and rows > 0 are required");
+  hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, ce, rank, rows, scalars);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_pack_rows(const float* w, const float* bias, float* wp, float* wt, float* biasp, int rows, int rows_pad,
+                            int D, int ldt, void* stream) {
+  if (rows <= 0 || D <= 0 || rows_pad < rows || ldt < rows_pad || ldt % 4)
+    FR_UNSUPPORTED("fr_pack_rows: shape (D > 0, ldt >= rows_pad >= rows > 0, ldt a multiple of 4)");
+  if (!w || !wp || !wt) FR_UNSUPPORTED("fr_pack_rows: w, wp and wt are required");
+  hipLaunchKernelGGL(pack_rows_kernel, dim3((D + 63) / 64, (rows_pad + 63) / 64), dim3(256), 0, (hipStream_t)stream, w,
+                     bias, wp, wt, biasp, rows, rows_pad, D, ldt);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_pad_cols(const float* g, float* out, int rows, int N, int ldg, int ldo, void* stream) {
+  if (rows <= 0 || N <= 0 || ldg < N || ldo < N || ldo % 4)
+    FR_UNSUPPORTED("fr_pad_cols: shape (rows > 0, ldg >= N > 0, ldo >= N, ldo a multiple of 4)");
+  if (!g || !out) FR_UNSUPPORTED("fr_pad_cols: g and out are required");
+  hipLaunchKernelGGL(pad_cols_kernel, dim3((ldo + 1023) / 1024, rows), dim3(256), 0, (hipStream_t)stream, g, out, N, ldg,
+                     ldo);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_col_sums(const float* g, int rows, int N, int ldg, float* out, void* stream) {
+  if (rows <= 0 || N <= 0 || ldg < N) FR_UNSUPPORTED("fr_col_sums: shape (rows > 0, ldg >= N > 0)");
+  if (!g || !out) FR_UNSUPPORTED("fr_col_sums: g and out are required");
+  hipLaunchKernelGGL(col_sums_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, g, rows, N, ldg, out);
   FR_LAUNCH_CHECK();
 }
 

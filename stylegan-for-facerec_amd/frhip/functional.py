@@ -1,7 +1,8 @@
-"""autograd.Function wrappers over the HIP kernels for the margin head, the focal loss and top-k accuracy.
+"""autograd.Function wrappers over the HIP kernels for the heads (the margin heads and the plain Softmax head), the focal
+loss, the plain cross entropy and top-k accuracy.
 
-These are what ``head/metrics.py``, ``loss/focal.py`` and ``util/utils.py`` call.  Inputs must be ROCm device
-tensors; a host tensor raises (no CPU fallback -- the CPU restatement is ``oracle/``, test-only).
+These are what ``head/metrics.py``, ``loss/focal.py``, ``loss/softmax.py`` and ``util/utils.py`` call.  Inputs must be
+ROCm device tensors; a host tensor raises (no CPU fallback -- the CPU restatement is ``oracle/``, test-only).
 The head always computes in fp32 (FR_F32): it is <0.3 % of the step's FLOPs and the 1e-3 logits bar of
 BASELINE.json is an fp32 bar (bf16 operands drift the logits by ~0.2).
 """
@@ -31,8 +32,10 @@ def _pad(n, m):
 # One cosine-head pipeline under the heads.  Forward: ``_cosine_operands`` (normalised operands), the cosine GEMM
 # (``_raw_cosines``, or ArcFace / CosFace's fused margin epilogue), the head's row kernels.  Backward: the head's gcos
 # kernel, then ``_cosine_backward`` (both GEMMs and the normalisation backwards).
-ARCFACE, COSFACE, SPHEREFACE, AM_SOFTMAX, CURRICULAR, MAGFACE, ADACOS, NPCFACE, MV_SOFTMAX, CIRCLE, AM_SOFTMAX_N, ARCNEG = range(12)
+(ARCFACE, COSFACE, SPHEREFACE, AM_SOFTMAX, CURRICULAR, MAGFACE, ADACOS, NPCFACE, MV_SOFTMAX, CIRCLE, AM_SOFTMAX_N, ARCNEG,
+ SOFTMAX) = range(13)
 # 0..3: the kernels' margin kinds.  AM_SOFTMAX_N is the FaceX-Zoo AM_Softmax (normalised embeddings) on the kernels' kind 3.
+# SOFTMAX is the plain linear head with a bias: no cosines, the same three GEMMs on operands that are not normalised.
 
 # What a forward call keeps for its backward call; a head leaves what it does not use at None.  xn / wn [Np, D] / wt
 # [D, Np] are the GEMM operands (xn is x itself for Am_softmax), inv_x / inv_w the reciprocal norms, cos_t the target
@@ -93,32 +96,33 @@ def _logit_store(sv, N, ld):
     return store, (store if ld == N else store[:, :N])
 
 
-def _cosine_backward(sv, Np, gcos, need_x, need_w, x_bwd, col_weight, r_part=None):
+def _cosine_backward(sv, Np, gcos, need_x, need_w, x_bwd, col_weight, r_part=None, norm_w=True):
     """(gx, gw) from gcos = d loss / d cos [B, Np] (columns >= N zero): the weight-gradient GEMM, the split-K data-gradient
     GEMM and the normalisation backwards.  ``x_bwd``: "normalize", "radial" (SphereFace: plus the radial term of its row
     scale, from ``r_part``) or None (the reduced G is the result: Am_softmax, and the class-sharded head's raw_x_grad).
-    ``col_weight``: gw in the [D, N] layout of a column-normalised kernel.
+    ``col_weight``: gw in the [D, N] layout of a column-normalised kernel.  ``norm_w=False`` (the Softmax head: an [N, D]
+    weight that is not normalised, ``sv.inv_w`` None): gw is the GEMM's result itself, its first N rows.
 
     Round 6: the two halves (three launches each, 55 us each at 7000 classes, neither fills the chip) run side by side when
     both are wanted: the weight's on the weight-gradient stream, which is idle until the backbone's backward pass starts.
     Every buffer is allocated on the calling stream, which waits for the side stream before this function returns."""
     B, D = sv.xn.shape
-    N = sv.inv_w.shape[0]
+    N = sv.inv_w.shape[0] if norm_w else sv.w.shape[0]
     dev = sv.x.device
     st = ops.current_stream_ptr()
     gx = gw = None
     if need_w:
         N4 = _pad(N, 4)  # the weight-gradient GEMM wants 16-byte channel counts; gcos columns >= N are zero
         GW = torch.empty(N4, D, device=dev)
-        gw = torch.empty_like(sv.w)
+        gw = torch.empty_like(sv.w) if norm_w else GW[:N]
 
     def weight_half(stream):
         ops.call("fr_fill_rows", GW, None, N4, D, stream)()
         ops.wgrad(stream, FR_F32, g=gcos, src=sv.xn, dw=GW, B=B, GH=1, GW=1, Cout=N4, SH=1, SW=1, SC=D, KH=1, KW=1,
                   stride=1, pad=0, ldg=Np, lda=D, pro=0, nsplit=1)()
-        if col_weight:
+        if norm_w and col_weight:
             ops.call("fr_col_normalize_bwd", GW, sv.wn, sv.inv_w, gw, D, N, stream)()
-        else:
+        elif norm_w:
             ops.call("fr_normalize_bwd", GW, sv.w, sv.inv_w, gw, N, D, stream)()
 
     side = _head_side_stream(dev) if (need_x and need_w) else None
@@ -463,6 +467,79 @@ def arcneg_backward(saved, cfg, g, need_x, need_w, raw_x_grad=False):
     return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, None if raw_x_grad else "normalize", col_weight=False)
 
 
+def _row_pitch(t):
+    """Floats between the rows of a [B, N] tensor whose rows are dense (one row: its stride says nothing)."""
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+def softmax_linear_forward(x, weight, bias):
+    """Softmax head logits (head/metrics.py:33, F.linear(x, weight, bias)) for fp32 device tensors; ``weight`` is [N, D],
+    ``bias`` [N].  fr_pack_rows lays out the weight as the GEMM's operands ([Np, D], its transpose, the bias with zeros
+    behind it) and the fp32 GEMM of the cosine heads adds the bias in its epilogue, once, to the accumulated dot product: no
+    pass over [B, N] besides the GEMM's own store.  The GEMM runs over ld = pad(N, 4) columns (zero weight rows, zero bias),
+    so the padding columns of the store are written as 0.  Nothing is normalised and nothing waits on the host.  Returns
+    (logits, saved, cfg) for ``softmax_linear_backward``."""
+    B, D = x.shape
+    N = weight.shape[0]
+    dev = x.device
+    x = x.contiguous().float()
+    w = weight.contiguous().float()
+    Np, ld = _pad(N, 32), _pad(N, 4)
+    wp = torch.empty(Np, D, device=dev)
+    wt = torch.empty(D, Np, device=dev)
+    bp = torch.empty(Np, device=dev)
+    ops.call("fr_pack_rows", w, bias.contiguous().float(), wp, wt, bp, N, Np, D, Np, ops.current_stream_ptr())()
+    sv = HeadSaved(x=x, w=w, xn=x, wn=wp, wt=wt)
+    store, logits = _logit_store(sv, N, ld)
+    _cosine_gemm(sv, store, ld, ld, ops.EPI_STORE, bias=bp)
+    return logits, sv._replace(wn=None), HeadCfg(SOFTMAX, Np, ld)
+
+
+def softmax_linear_backward(saved, cfg, g, need_x, need_w, raw_x_grad=False):
+    """(gx, gweight, gbias) of ``softmax_linear_forward``: gx = g W (split-K, the slices added in a fixed order), gweight =
+    g^T x, gbias[n] = ((g[0, n] + g[1, n]) + g[2, n]) + ... (fr_col_sums: fp32, the rows in order); ``need_w`` asks for
+    both parameter gradients.  ``raw_x_grad`` means what it means elsewhere; nothing is normalised here, so G is gx."""
+    B, N = saved.x.shape[0], saved.w.shape[0]
+    dev = saved.x.device
+    st = ops.current_stream_ptr()
+    g = g.float()
+    if g.stride(1) != 1 or g.stride(0) < N:  # rows at any pitch are read where they lie (the loss leaves them at ld)
+        g = g.contiguous()
+    ldg = _row_pitch(g)
+    gb = None
+    if need_w:
+        gb = torch.empty(N, device=dev)
+        ops.call("fr_col_sums", g, B, N, ldg, gb, st)()
+    gp = torch.empty(B, cfg.Np, device=dev)  # the pitch both gradient GEMMs read, columns N .. Np zero
+    ops.call("fr_pad_cols", g, gp, B, N, ldg, cfg.Np, st)()
+    return _cosine_backward(saved, cfg.Np, gp, need_x, need_w, None, col_weight=False, norm_w=False) + (gb,)
+
+
+class SoftmaxHeadFn(torch.autograd.Function):
+    """logits = x W^T + b (head/metrics.py:12-63) on the HIP path; see ``softmax_linear_forward``."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        logits, saved, cfg = softmax_linear_forward(x, weight, bias)
+        ctx.save_for_backward(*saved)
+        ctx.cfg = cfg
+        return logits
+
+    @staticmethod
+    def backward(ctx, g):
+        need = ctx.needs_input_grad
+        gx, gw, gb = softmax_linear_backward(HeadSaved(*ctx.saved_tensors), ctx.cfg, g, need[0], need[1] or need[2])
+        return gx, (gw if need[1] else None), (gb if need[2] else None)
+
+
+def softmax_head(x, weight, bias):
+    """Softmax head logits; the empty batch of ``margin_head`` ([0, N] logits; host tensors still raise)."""
+    ops.ptr(x)  # host tensors fail loudly, before anything asks for a device
+    if x.shape[0] == 0:
+        return x.new_zeros((0, weight.shape[0]), dtype=torch.float32) + 0.0 * (x.sum() + weight.sum() + bias.sum())
+    return SoftmaxHeadFn.apply(x, weight, bias)
+
+
 def _head_fn(name, fwd, bwd, doc):
     """The autograd.Function of a head from its forward / backward pair; it takes the forward function's arguments (x,
     weight, label and up to four head-specific values)."""
@@ -648,6 +725,52 @@ def focal_loss(logits, target, gamma=2.0):
         ops.ptr(logits)
         return logits.sum() * float("nan")
     return FocalLossFn.apply(logits, target, gamma)
+
+
+class CrossEntropyFn(torch.autograd.Function):
+    """loss = mean_i CE(logits_i, y_i)   -- nn.CrossEntropyLoss() as the reference's LOSS_NAME 'Softmax' builds it
+    (train.py:237-238, :300-302).  ``FocalLossFn`` with fr_ce_finalize in place of fr_focal_finalize: the slope it leaves is
+    exactly 1, and fr_focal_bwd is the backward kernel unchanged.  Logits that are the [B, N] view of a head's [B, ld] store
+    are read at that pitch, and the gradient is laid out alike: no copy of [B, N] on either side."""
+
+    @staticmethod
+    def forward(ctx, logits, target):
+        B, N = logits.shape
+        dev = logits.device
+        st = ops.current_stream_ptr()
+        logits = logits.float()
+        if logits.stride(1) != 1 or logits.stride(0) < N:
+            logits = logits.contiguous()
+        ld = _row_pitch(logits)
+        target = target.contiguous().long()
+        lse = torch.empty(B, device=dev)
+        ce = torch.empty(B, device=dev)
+        rank = torch.empty(B, device=dev, dtype=torch.int32)
+        scalars = torch.empty(8, device=dev)
+        ops.call("fr_ce_rows", logits, target, lse, ce, rank, B, N, ld, st)()
+        ops.call("fr_ce_finalize", ce, rank, B, scalars, st)()
+        ctx.save_for_backward(logits, target, lse, scalars)
+        return scalars[0].clone()
+
+    @staticmethod
+    def backward(ctx, gup):
+        logits, target, lse, scalars = ctx.saved_tensors
+        B, N = logits.shape
+        ld = _row_pitch(logits)
+        store = torch.empty(B, ld, device=logits.device)
+        gup = gup.contiguous().float().reshape(1)
+        ops.call("fr_focal_bwd", logits, target, lse, scalars, gup, store, B, N, ld, ops.current_stream_ptr())()
+        return (store if ld == N else store[:, :N]), None
+
+
+def cross_entropy(logits, target):
+    """Batch-mean cross entropy of fp32 device logits.  An empty batch gives NaN, as ``focal_loss`` (the reference's mean
+    over no rows); the labels are range-checked under ``CHECK_LABELS``."""
+    ops.ptr(logits)  # host tensors fail loudly, before the label check reads anything
+    if logits.shape[0] == 0:
+        return logits.sum() * float("nan")
+    _check_labels(target, logits.shape[1])
+    return CrossEntropyFn.apply(logits, target)
 
 
 def topk_precision(rank, topk):

@@ -30,6 +30,15 @@ SphereFace, Am_softmax and CurricularFace run the same choreography with one dif
                   global batch, identically on every rank, in a device buffer
 Both extra exchanges are [Bg]-sized.
 
+``loss="Softmax"`` (any head): the plain batch-mean cross entropy of the global batch, nn.CrossEntropyLoss() as the
+reference's LOSS_NAME 'Softmax' builds it.  The choreography is the same up to the last step, where fr_ce_finalize stands in
+for fr_focal_finalize; the slope it leaves is exactly 1, so the backward pass is unchanged.
+
+Head ``Softmax`` (head/metrics.py:12-63, a linear layer with a bias): ``weight`` [N, D] sharded by rows, and a second
+parameter ``bias`` [N] sharded alike.  The local logits are x_all W_shard^T + bias_shard; x is not normalised and the
+labels play no part in them.  G = g W_shard, reduce-scattered, is gx itself; the gradients of the weight shard and of the
+bias shard (the column sums of g over the global batch, the rows in order) are complete on their owner.
+
 The device arithmetic sits behind ``HipKernels`` (the only implementation in the package: HIP through the C ABI; no
 CPU fallback).  tests/ substitutes an oracle-backed stand-in to run the collective choreography at world_size 2 on
 ``gloo``.
@@ -44,11 +53,14 @@ from . import ops
 
 KINDS = {"ArcFace": FRF.ARCFACE, "CosFace": FRF.COSFACE, "SphereFace": FRF.SPHEREFACE, "Am_softmax": FRF.AM_SOFTMAX,
          "CurricularFace": FRF.CURRICULAR}
+# Consulted after KINDS: the head that is no margin head, a linear layer with a bias (two parameters).
+LINEAR_KINDS = {"Softmax": FRF.SOFTMAX}
 # the dimension of the parameter that runs over the classes: ``weight`` [N, D] or ``kernel`` [D, N] (head/metrics.py)
-CLASS_DIM = {"ArcFace": 0, "CosFace": 0, "SphereFace": 0, "Am_softmax": 1, "CurricularFace": 1}
-# (s, m) of each head's own constructor (head/metrics.py); SphereFace has no s
+CLASS_DIM = {"ArcFace": 0, "CosFace": 0, "SphereFace": 0, "Am_softmax": 1, "CurricularFace": 1, "Softmax": 0}
+# (s, m) of each head's own constructor (head/metrics.py); SphereFace has no s, Softmax neither
 DEFAULTS = {"ArcFace": (64.0, 0.50), "CosFace": (64.0, 0.50), "SphereFace": (0.0, 4), "Am_softmax": (30.0, 0.35),
-            "CurricularFace": (64.0, 0.5)}
+            "CurricularFace": (64.0, 0.5), "Softmax": (0.0, 0.0)}
+LOSSES = ("Focal", "Softmax")
 
 
 def class_range(num_classes, world, rank):
@@ -145,6 +157,12 @@ class HipKernels(object):
         ops.call("fr_focal_finalize", ce, rank, ce.shape[0], float(gamma), scalars, ops.current_stream_ptr())()
         return scalars
 
+    def ce(self, ce, rank):
+        """``focal`` for loss "Softmax": the batch-mean cross entropy, slope exactly 1."""
+        scalars = torch.empty(8, device=ce.device)
+        ops.call("fr_ce_finalize", ce, rank, ce.shape[0], scalars, ops.current_stream_ptr())()
+        return scalars
+
     def dlogits(self, logits, label_local, lse, scalars, gup):
         rows, n = logits.shape
         ld = logits.stride(0)  # the logits keep a 16-byte row pitch; the gradient uses the same one
@@ -187,6 +205,14 @@ class HipKernels(object):
             return FRF.curricular_backward(saved, cfg, g, need_x, need_w, raw_x_grad=True) + (None,)
         return FRF.margin_ext_backward(saved, cfg, g, need_x, need_w, raw_x_grad=True)
 
+    # Softmax
+    def linear_logits(self, x_all, w, bias):
+        return FRF.softmax_linear_forward(x_all, w, bias)
+
+    def linear_bwd(self, saved, cfg, g, need_x, need_w):
+        """(G = g W_shard, gradient of the weight shard, gradient of the bias shard)."""
+        return FRF.softmax_linear_backward(saved, cfg, g, need_x, need_w, raw_x_grad=True)
+
     def sum_r(self, r_part):
         """[rows, 1]: the row's parts added in the order fr_normalize_bwd_radial adds them."""
         rows, nparts = r_part.shape
@@ -204,7 +230,7 @@ class ShardedHeadLossFn(torch.autograd.Function):
     """(loss, prec@1, prec@5) of the global batch from this rank's features, labels and weight shard."""
 
     @staticmethod
-    def forward(ctx, x, w, label, head):
+    def forward(ctx, x, w, label, head, bias):
         K, C = head.kernels, head.comm
         B = x.shape[0]
         x_loc = x.detach().contiguous().float()
@@ -218,13 +244,15 @@ class ShardedHeadLossFn(torch.autograd.Function):
             logits, saved, cfg = K.ext_logits(x_all, w.detach(), lab_loc, head.kind, head.m, 1 + head.lamb, 0.0)
         elif head.kind == FRF.AM_SOFTMAX:
             logits, saved, cfg = K.ext_logits(x_all, w.detach(), lab_loc, head.kind, 0, head.m, head.s)
+        elif head.kind == FRF.SOFTMAX:
+            logits, saved, cfg = K.linear_logits(x_all, w.detach(), bias.detach())
         else:  # one [Bg] all-reduce: every rank gets every row's target cosine, and with them the same t
             logits, saved, cfg = K.curricular_logits(x_all, w.detach(), lab_loc, head.t, head.s, head.m, C.all_reduce_sum,
                                                      head.training)
         stats_all = C.all_gather(K.row_stats(logits, lab_loc).view(1, 3, rows))
         lse, ce, tlogit = K.combine(stats_all, C.world, rows)
         rank = C.all_reduce_sum(K.shard_rank(logits, tlogit))
-        scalars = K.focal(ce, rank, head.gamma)
+        scalars = K.focal(ce, rank, head.gamma) if head.loss == "Focal" else K.ce(ce, rank)
         ctx.head, ctx.saved, ctx.cfg = head, saved, cfg
         ctx.rows_of_rank = (C.rank * B, (C.rank + 1) * B)
         ctx.save_for_backward(logits, lab_loc, lse, scalars, x_loc)
@@ -238,16 +266,19 @@ class ShardedHeadLossFn(torch.autograd.Function):
         K, C = head.kernels, head.comm
         logits, lab_loc, lse, scalars, x_loc = ctx.saved_tensors
         grad = K.dlogits(logits, lab_loc, lse, scalars, gloss)
-        r_part = None
+        r_part = gb = None
         if head.kind in (FRF.ARCFACE, FRF.COSFACE):
             G_all, gw = K.head_bwd(ctx.saved, ctx.cfg, grad, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        elif head.kind == FRF.SOFTMAX:
+            G_all, gw, gb = K.linear_bwd(ctx.saved, ctx.cfg, grad, ctx.needs_input_grad[0],
+                                         ctx.needs_input_grad[1] or ctx.needs_input_grad[4])
         else:
             G_all, gw, r_part = K.ext_bwd(ctx.saved, ctx.cfg, grad, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         gx = None
         if G_all is not None:
             G = C.reduce_scatter_rows(G_all)
             lo, hi = ctx.rows_of_rank
-            if head.kind == FRF.AM_SOFTMAX:  # x is not normalised: G is the gradient
+            if head.kind in (FRF.AM_SOFTMAX, FRF.SOFTMAX):  # x is not normalised: G is the gradient
                 gx = G
             else:
                 inv_x = ctx.saved.inv_x[lo:hi].contiguous()
@@ -258,18 +289,19 @@ class ShardedHeadLossFn(torch.autograd.Function):
                     gx = K.normalize_bwd(G, x_loc, inv_x)
             if head.grad_scale != 1.0:
                 gx = gx * head.grad_scale
-        return gx, gw, None, None
+        return gx, gw, None, None, gb
 
 
 class ShardedMarginLoss(nn.Module):
-    """A margin head + FocalLoss + accuracy with the class dimension sharded over the ranks of ``group``.
+    """A head + FocalLoss (or the plain cross entropy) + accuracy, the class dimension sharded over the ranks of ``group``.
 
         crit = ShardedMarginLoss(512, 28000, "ArcFace", s=64.0, m=0.5, gamma=2)      # after init_process_group
         loss, prec1, prec5 = crit(features, labels)                                   # per-rank features / labels
         loss.backward()                        # crit.weight.grad is final (no all-reduce), features get their gradient
 
-    ``head``: ArcFace, CosFace, SphereFace, Am_softmax or CurricularFace; ``s`` / ``m`` default to that head's own
-    (head/metrics.py; SphereFace takes ``m`` only, ``easy_margin`` is ArcFace's).
+    ``head``: ArcFace, CosFace, SphereFace, Am_softmax, CurricularFace or Softmax; ``s`` / ``m`` default to that head's own
+    (head/metrics.py; SphereFace takes ``m`` only, ``easy_margin`` is ArcFace's, Softmax takes neither).  ``loss``: "Focal"
+    (``gamma``) or "Softmax", the batch-mean cross entropy of the global batch.
 
     ``weight`` is this rank's slice of the head's parameter in the head's own layout, ``class_dim`` telling which dimension
     runs over the classes: [hi - lo, in_features] of ``weight`` (ArcFace, CosFace, SphereFace: ``class_dim`` 0) or
@@ -278,7 +310,9 @@ class ShardedMarginLoss(nn.Module):
     interchangeable; ``gather_weight()`` returns the reference's parameter (checkpoint key ``weight`` / ``kernel``), and
     ``gather_full`` / ``slice_full`` do the same for any tensor of the parameter's shape (momentum buffers).
     CurricularFace keeps the reference's ``t`` as a one-float buffer (identical on every rank), SphereFace its forward
-    counter ``iter``.
+    counter ``iter``.  Softmax has a second parameter, ``bias``: this rank's [hi - lo] slice of the head's (``full_bias``
+    given: of that tensor, else zeros as the head draws it); ``slice_full`` / ``gather_full`` take one-dimensional tensors
+    too, and ``gather_bias()`` returns the reference's ``bias``.
 
     The loss is the focal loss of the GLOBAL batch (head/metrics.py + loss/focal.py applied to the concatenated batch,
     what the reference's single head sees under nn.DataParallel).  ``average_over_ranks=True`` (default) scales the
@@ -287,12 +321,16 @@ class ShardedMarginLoss(nn.Module):
     """
 
     def __init__(self, in_features, out_features, head="ArcFace", s=None, m=None, easy_margin=False, gamma=2.0,
-                 group=None, full_weight=None, average_over_ranks=True, kernels=None):
+                 group=None, full_weight=None, average_over_ranks=True, kernels=None, loss="Focal", full_bias=None):
         super().__init__()
-        if head not in KINDS:
-            raise ValueError("ShardedMarginLoss: head must be one of %s, got %r" % (", ".join(KINDS), head))
+        if head not in KINDS and head not in LINEAR_KINDS:
+            raise ValueError("ShardedMarginLoss: head must be one of %s, got %r"
+                             % (", ".join(list(KINDS) + list(LINEAR_KINDS)), head))
+        if loss not in LOSSES:
+            raise ValueError("ShardedMarginLoss: loss must be one of %s, got %r" % (", ".join(LOSSES), loss))
+        self.loss = loss
         self.in_features, self.out_features = in_features, out_features
-        self.head_name, self.kind, self.class_dim = head, KINDS[head], CLASS_DIM[head]
+        self.head_name, self.kind, self.class_dim = head, KINDS.get(head, LINEAR_KINDS.get(head)), CLASS_DIM[head]
         s = DEFAULTS[head][0] if s is None else s
         m = DEFAULTS[head][1] if m is None else m
         self.s, self.easy_margin, self.gamma = float(s), bool(easy_margin), float(gamma)
@@ -313,6 +351,12 @@ class ShardedMarginLoss(nn.Module):
         if tuple(full_weight.shape) != self.full_shape:
             raise ValueError("ShardedMarginLoss: full_weight must be [%d, %d]" % self.full_shape)
         self.weight = Parameter(self.slice_full(full_weight.detach()).float())
+        if self.kind == FRF.SOFTMAX:
+            if full_bias is None:
+                full_bias = torch.zeros(out_features)
+            if tuple(full_bias.shape) != (out_features,):
+                raise ValueError("ShardedMarginLoss: full_bias must be [%d]" % out_features)
+            self.bias = Parameter(self.slice_full(full_bias.detach()).float())
         if self.kind == FRF.CURRICULAR:
             self.register_buffer("t", torch.zeros(1))
         if self.kind == FRF.SPHEREFACE:  # the lambda schedule of head/metrics.py SphereFace
@@ -320,12 +364,14 @@ class ShardedMarginLoss(nn.Module):
 
     @classmethod
     def from_head(cls, head, gamma=2.0, group=None, **kw):
-        """Shard an existing head of head/metrics.py (same parameter on every rank); CurricularFace's ``t`` and
-        SphereFace's ``iter`` come along."""
+        """Shard an existing head of head/metrics.py (same parameter on every rank); CurricularFace's ``t``,
+        SphereFace's ``iter`` and Softmax's ``bias`` come along."""
         name = head.__class__.__name__
         full = head.kernel if hasattr(head, "kernel") else head.weight
         dims = (full.shape[0], full.shape[1]) if CLASS_DIM.get(name, 0) == 1 else (full.shape[1], full.shape[0])
-        crit = cls(dims[0], dims[1], name, s=getattr(head, "s", None), m=head.m,
+        if name == "Softmax":
+            kw = dict(kw, full_bias=head.bias.detach().cpu())
+        crit = cls(dims[0], dims[1], name, s=getattr(head, "s", None), m=getattr(head, "m", None),
                    easy_margin=getattr(head, "easy_margin", False), gamma=gamma, group=group,
                    full_weight=full.detach().cpu(), **kw)
         if hasattr(crit, "t"):
@@ -339,13 +385,13 @@ class ShardedMarginLoss(nn.Module):
                                        for r in range(self.comm.world))]
 
     def slice_full(self, full):
-        """This rank's class range of a tensor of the full parameter's shape (a copy)."""
-        return (full[self.lo:self.hi] if self.class_dim == 0 else full[:, self.lo:self.hi]).clone()
+        """This rank's class range of a tensor of the full parameter's shape, or of the bias's [N] (a copy)."""
+        return (full[self.lo:self.hi] if self.class_dim == 0 or full.dim() == 1 else full[:, self.lo:self.hi]).clone()
 
     def gather_full(self, part):
         """Inverse of ``slice_full`` on every rank (collective).  Column shards travel transposed: the ragged gather stacks
         row blocks."""
-        if self.class_dim == 0:
+        if self.class_dim == 0 or part.dim() == 1:
             return self.comm.gather_ragged_rows(part, self.shard_sizes())
         return self.comm.gather_ragged_rows(part.t().contiguous(), self.shard_sizes()).t().contiguous()
 
@@ -353,9 +399,15 @@ class ShardedMarginLoss(nn.Module):
         """The full parameter on every rank (checkpoints keep the reference's layout)."""
         return self.gather_full(self.weight.detach())
 
-    def load_full_weight(self, full_weight):
+    def gather_bias(self):
+        """Softmax: the full ``bias`` on every rank (collective)."""
+        return self.gather_full(self.bias.detach())
+
+    def load_full_weight(self, full_weight, full_bias=None):
         with torch.no_grad():
             self.weight.copy_(self.slice_full(full_weight))
+            if full_bias is not None:
+                self.bias.copy_(self.slice_full(full_bias))
 
     def forward(self, input, label):
         if self.weight.device != input.device:
@@ -367,8 +419,9 @@ class ShardedMarginLoss(nn.Module):
         if self.kind == FRF.SPHEREFACE:  # head/metrics.py:238-239: every forward call counts
             self.iter += 1
             self.lamb = max(self.LambdaMin, self.base * (1 + self.lambda_gamma * self.iter) ** (-1 * self.power))
-        return ShardedHeadLossFn.apply(input, self.weight, label, self)
+        return ShardedHeadLossFn.apply(input, self.weight, label, self, getattr(self, "bias", None))
 
     def __repr__(self):
-        return "ShardedMarginLoss(%s, in_features = %d, classes [%d, %d) of %d, s = %s, m = %s, gamma = %s)" % (
-            self.head_name, self.in_features, self.lo, self.hi, self.out_features, self.s, self.m, self.gamma)
+        return "ShardedMarginLoss(%s, in_features = %d, classes [%d, %d) of %d, s = %s, m = %s, %s)" % (
+            self.head_name, self.in_features, self.lo, self.hi, self.out_features, self.s, self.m,
+            "gamma = %s" % self.gamma if self.loss == "Focal" else "loss = Softmax")

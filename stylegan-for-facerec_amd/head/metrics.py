@@ -5,6 +5,7 @@
     from head.metrics import MV_Softmax                                      (reference head/metrics.py:555)
     from head.metrics import CircleLoss, AM_Softmax                          (reference head/metrics.py:435, :371)
     from head.metrics import ArcNegFace                                      (reference head/metrics.py:394)
+    from head.metrics import Softmax                                         (reference head/metrics.py:12)
 
 The four heads the reference driver can select (``HEAD_NAME``, train.py:56,178-182) and ``CurricularFace`` / ``MagFace`` /
 ``AdaCos`` / ``NPCFace`` / ``MV_Softmax`` / ``CircleLoss`` / ``AM_Softmax`` / ``ArcNegFace`` (eight of the FaceX-Zoo heads of the reference's
@@ -50,6 +51,11 @@ head/metrics.py that its driver never names; train.py here accepts them) run on 
     margin) where ``gt > thresh``, else ``gt - mm``) and writes ``scale * a`` on the label column and ``scale * (t c + t -
     1)``, ``t = alpha * exp(-(c - a)^2 / sigma)``, off it; the backward pass recomputes ``t`` and treats it and the branch
     as constants.  No state besides ``weight``.
+  * ``Softmax`` (the plain classification head, ``F.linear(x, weight, bias)``): nothing is normalised.  One kernel lays out
+    the weight and the bias as the GEMM's operands, the same fp32 GEMM adds the bias in its epilogue, once, to the
+    accumulated dot product; the backward pass is the two gradient GEMMs of the cosine heads without their normalisation
+    backwards, and a column-sum kernel that adds the bias gradient over the rows in order.  On host tensors it is
+    ``F.linear``.  Parameters ``weight`` and ``bias``.
 On host tensors ``SphereFace`` / ``Am_softmax`` / ``CurricularFace`` / ``MagFace`` / ``AdaCos`` / ``NPCFace`` / ``MV_Softmax`` /
 ``CircleLoss`` / ``AM_Softmax`` / ``ArcNegFace`` run the reference's plain-PyTorch arithmetic (the
 restatement the tests compare with); ``ArcFace`` / ``CosFace`` refuse host tensors.  ``SphereFace.iter`` counts forward
@@ -138,6 +144,29 @@ class _MarginHead(nn.Module):
     def __repr__(self):
         return "%s(in_features = %d, out_features = %d, s = %s, m = %s)" % (
             self.__class__.__name__, self.in_features, self.out_features, self.s, self.m)
+
+
+class Softmax(nn.Module):
+    """The plain classification head, a linear layer with a bias (reference head/metrics.py:12-63): HIP kernels on device
+    tensors, ``F.linear`` on the host.  The reference's ``forward(x)`` cannot be called by its own train.py, which passes the
+    labels too (train.py:300); they are accepted and ignored."""
+
+    def __init__(self, in_features, out_features, device_id):
+        super().__init__()
+        self.in_features, self.out_features, self.device_id = in_features, out_features, device_id
+        self.weight = Parameter(torch.empty(out_features, in_features))
+        self.bias = Parameter(torch.empty(out_features))
+        nn.init.xavier_uniform_(self.weight)  # metrics.py:28-29
+        nn.init.zeros_(self.bias)
+
+    def forward(self, x, label=None):
+        if x.is_cuda:
+            _beside(self, self.weight, x)
+            return FRF.softmax_head(x, self.weight, self.bias)
+        return F.linear(x, self.weight.to(x.device), self.bias.to(x.device))
+
+    def __repr__(self):
+        return "Softmax(in_features = %d, out_features = %d)" % (self.in_features, self.out_features)
 
 
 class ArcFace(_MarginHead):

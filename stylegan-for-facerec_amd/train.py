@@ -36,8 +36,9 @@ from frhip import set_compute_dtype
 from frhip.optim import SGD, Adam
 from frhip.parallel import DataParallel
 from head.metrics import (AM_Softmax, AdaCos, Am_softmax, ArcFace, ArcNegFace, CircleLoss, CosFace, CurricularFace, MagFace,
-                          MV_Softmax, NPCFace, SphereFace)
+                          MV_Softmax, NPCFace, Softmax, SphereFace)
 from loss.focal import FocalLoss
+from loss.softmax import CrossEntropyLoss
 from util.utils import (AverageMeter, accuracy, buffer_val, collate_fn_ignore_none, get_time, get_val_data, perform_val,
                         schedule_lr, separate_irse_bn_paras, warm_up_lr)
 
@@ -74,31 +75,38 @@ def build_backbone(cfg):
     raise ValueError("unsupported BACKBONE_NAME %r" % name)
 
 
-def _head_state_index(optimizer, crit):
-    """Index of the sharded head weight in the optimizer's flat parameter numbering (state_dict keys)."""
-    i = 0
+def _head_state_indices(optimizer, crit):
+    """[(index in the optimizer's flat parameter numbering (state_dict keys), shard shape, full shape)] of the sharded
+    head's parameters: the weight, and the Softmax head's bias."""
+    want = {id(crit.weight): tuple(crit.full_shape)}
+    if getattr(crit, "bias", None) is not None:
+        want[id(crit.bias)] = (crit.out_features,)
+    found, i = [], 0
     for group in optimizer.param_groups:
         for p in group["params"]:
-            if p is crit.weight:
-                return i
+            if id(p) in want:
+                found.append((i, tuple(p.shape), want[id(p)]))
             i += 1
-    raise RuntimeError("the sharded head weight is not in the optimizer")
+    if len(found) != len(want):
+        raise RuntimeError("the sharded head weight is not in the optimizer")
+    return found
 
 
 def optimizer_state_for_checkpoint(optimizer, crit):
     """``optimizer.state_dict()`` in the reference's layout.  With a class-sharded head the momentum buffer of the head
     parameter is gathered to the head's full shape, [classes, 512] or [512, classes] (collective: every rank calls this),
-    so optimizer checkpoints are interchangeable between replicated and sharded runs and between world sizes."""
+    so optimizer checkpoints are interchangeable between replicated and sharded runs and between world sizes.  The Softmax
+    head's bias is a second head parameter, gathered to [classes] likewise."""
     sd = optimizer.state_dict()
     if crit is None:
         return sd
-    idx = _head_state_index(optimizer, crit)
-    st = sd["state"].get(idx)
-    if st is not None:
-        full = {k: crit.gather_full(v) for k, v in st.items()
-                if torch.is_tensor(v) and v.shape == crit.weight.shape}  # momentum_buffer / exp_avg / exp_avg_sq
-        sd = dict(sd, state=dict(sd["state"]))
-        sd["state"][idx] = dict(st, **full)
+    for idx, shard_shape, _full_shape in _head_state_indices(optimizer, crit):
+        st = sd["state"].get(idx)
+        if st is not None:
+            full = {k: crit.gather_full(v) for k, v in st.items()
+                    if torch.is_tensor(v) and tuple(v.shape) == shard_shape}  # momentum_buffer / exp_avg / exp_avg_sq
+            sd = dict(sd, state=dict(sd["state"]))
+            sd["state"][idx] = dict(st, **full)
     return sd
 
 
@@ -111,13 +119,13 @@ def _np_state_plain(st):
 def load_optimizer_checkpoint(optimizer, crit, sd):
     """Inverse of ``optimizer_state_for_checkpoint``: this rank keeps its class range of the head's optimizer state."""
     if crit is not None:
-        idx = _head_state_index(optimizer, crit)
-        st = sd["state"].get(idx)
-        if st is not None:
-            part = {k: crit.slice_full(v) for k, v in st.items()
-                    if torch.is_tensor(v) and tuple(v.shape) == crit.full_shape}
-            sd = dict(sd, state=dict(sd["state"]))
-            sd["state"][idx] = dict(st, **part)
+        for idx, _shard_shape, full_shape in _head_state_indices(optimizer, crit):
+            st = sd["state"].get(idx)
+            if st is not None:
+                part = {k: crit.slice_full(v) for k, v in st.items()
+                        if torch.is_tensor(v) and tuple(v.shape) == full_shape}
+                sd = dict(sd, state=dict(sd["state"]))
+                sd["state"][idx] = dict(st, **part)
     optimizer.load_state_dict(sd)
 
 
@@ -223,6 +231,8 @@ def main():
         # reference's own margin, weight and scale (0.35, 1.12, 32), as MagFace; MV_IS_AM=False: the ArcFace-style form
         heads["CircleLoss"] = CircleLoss(emb, num_class)  # after MV_Softmax, likewise; the reference's own margin 0.25, gamma 256
         heads["AM_Softmax"] = AM_Softmax(emb, num_class)  # after CircleLoss, likewise; the reference's own margin 0.35, scale 32
+        with torch.random.fork_rng(devices=[]):  # the plain linear head (weight and bias), off this generator too: the
+            heads["Softmax"] = Softmax(emb, num_class, None)  # heads around it keep their initial weights
         heads["ArcNegFace"] = ArcNegFace(emb, num_class)  # after AM_Softmax, likewise; the reference's own margin 0.5, scale 64
     head = heads[cfg["HEAD_NAME"]]
     if world > 1 and hasattr(head, "process_group") and not cfg.get("SHARDED_HEAD", False):
@@ -258,14 +268,17 @@ def main():
         # [B, N] logits are split by class range; the loss is the focal loss of the GLOBAL batch, as under the
         # reference's nn.DataParallel.  Checkpoints keep the reference's layout: the gathered ``weight`` / ``kernel``,
         # CurricularFace's ``t`` and SphereFace's forward counter go back into ``head`` before it is saved.
-        if loss_fn is None:
+        # LOSS_NAME 'Softmax': the batch-mean cross entropy of the global batch instead (any of the sharded heads).
+        if loss_fn is None and cfg["LOSS_NAME"] != "Softmax":
             raise NotImplementedError("SHARDED_HEAD needs LOSS_NAME 'Focal'")
         from frhip.sharded_head import ShardedMarginLoss
-        crit = ShardedMarginLoss.from_head(head, gamma=loss_fn.gamma).to(device)  # takes the resumed weight and t along
-        optimizer = make_optimizer([crit.weight])
+        crit = ShardedMarginLoss.from_head(head, gamma=loss_fn.gamma if loss_fn is not None else 2.0,
+                                           loss=cfg["LOSS_NAME"]).to(device)  # takes the resumed weight and t along
+        optimizer = make_optimizer(list(crit.parameters()))  # the weight shard; the Softmax head's bias shard behind it
     # exposes .module like nn.DataParallel; all-reduce only when world > 1 (a weight shard is complete on its owner)
     BACKBONE = DataParallel(backbone, None if crit is not None else head)
-    ce = torch.nn.CrossEntropyLoss()
+    # LOSS_NAME 'Softmax' (reference train.py:237-238): the batch-mean cross entropy on the HIP row-softmax kernels
+    ce = CrossEntropyLoss() if cfg["LOSS_NAME"] == "Softmax" else torch.nn.CrossEntropyLoss()
 
     optimizer_loaded = False
     if opt_resume:  # reference train.py:227-232: before the first step (momentum buffers and the groups' LR come back)
@@ -402,6 +415,8 @@ def main():
             with torch.no_grad():
                 # collective: every rank takes part, rank 0 writes the file
                 (head.kernel if hasattr(head, "kernel") else head.weight).copy_(crit.gather_weight())
+                if cfg["HEAD_NAME"] == "Softmax":
+                    head.bias.copy_(crit.gather_bias())
                 if cfg["HEAD_NAME"] not in ("ArcFace", "CosFace"):  # heads with state besides the parameter
                     if hasattr(crit, "t"):  # CurricularFace
                         head.t.copy_(crit.t)

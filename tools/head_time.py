@@ -1,15 +1,16 @@
-"""Time one margin head at batch 256, 28 000 classes, 512 features: `iters` forward calls (mode fwd) or forward + backward
+"""Time one head at batch 256, 28 000 classes, 512 features: `iters` forward calls (mode fwd) or forward + backward
 calls (mode fwdbwd) after 3 warm-up calls, event-timed; run it under `rocprofv3 --kernel-trace --stats -- ...` for the
 kernel times (profiles/margin_heads_b256_n28000.txt).
 
     python tools/head_time.py {ArcFace|CosFace|SphereFace|Am_softmax|CurricularFace|MagFace|AdaCos|NPCFace|MV_Softmax|MV_Softmax-arc
-                               |CircleLoss|AM_Softmax|ArcNegFace} {fwd|fwdbwd} ITERS
+                               |CircleLoss|AM_Softmax|ArcNegFace|Softmax} {fwd|fwdbwd} ITERS
 
 Several heads, comma separated, are timed in ONE process in alternating rounds (ROUNDS rounds of ITERS calls per head, the
 median round of each head reported, and the ratio to the first head named), so clocks and allocator state are shared
 (profiles/curricular_head_b256_n28000.txt, profiles/magface_head_b256_n28000.txt,
 profiles/adacos_head_b256_n28000.txt, profiles/npcface_head_b256_n28000.txt, profiles/mv_softmax_head_b256_n28000.txt,
-profiles/circle_heads_b256_n28000.txt, profiles/arcnegface_head_b256_n28000.txt; MV_Softmax is the additive-margin form, MV_Softmax-arc the ArcFace-style one):
+profiles/circle_heads_b256_n28000.txt, profiles/arcnegface_head_b256_n28000.txt, profiles/softmax_head_b256_n28000.txt;
+MV_Softmax is the additive-margin form, MV_Softmax-arc the ArcFace-style one; Softmax is the plain linear head with a bias):
 
     python tools/head_time.py Am_softmax,ArcFace,CurricularFace fwdbwd ITERS [ROUNDS]
 
@@ -42,13 +43,14 @@ def make(name):
     else:
         cls = getattr(H, name)
         head = (cls(D, N) if zoo else cls(D, N, None)).cuda()
-    p = list(head.parameters())[0]
+    params = list(head.parameters())  # one parameter; the Softmax head's bias is a second
 
     def step():
         y = head(x, label)
         if mode == "fwdbwd":
             x.grad = None
-            p.grad = None
+            for p in params:
+                p.grad = None
             if isinstance(y, tuple):
                 torch.autograd.backward(y, [g, gg])
             else:
