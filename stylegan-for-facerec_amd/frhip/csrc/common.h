@@ -199,6 +199,29 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   return v;
 }
 
+// Block-reduction tail over the waves' results (float, double or int): block_put(red_a, a, red_b, b, ...) has lane 0 of each
+// wave leave the wave's values in its slot of their LDS arrays, then one barrier; waves_sum<NW>(red) adds the NW slots in
+// wave order, (red[0] + red[1]) + red[2] + ...: the order is part of the result's bits.  waves_max4: the max of four waves.
+__device__ __forceinline__ void waves_store(int) {}
+template <typename T, typename... R>
+__device__ __forceinline__ void waves_store(int wave, T* red, T v, R... rest) {
+  red[wave] = v;
+  waves_store(wave, rest...);
+}
+template <typename... A>
+__device__ __forceinline__ void block_put(A... slots_and_values) {
+  if ((threadIdx.x & 63) == 0) waves_store(threadIdx.x >> 6, slots_and_values...);
+  __syncthreads();
+}
+template <int NW, typename T>
+__device__ __forceinline__ T waves_sum(const T* red) {
+  T acc = red[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) acc += red[w];
+  return acc;
+}
+__device__ __forceinline__ float waves_max4(const float* red) { return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])); }
+
 // exact-enough unsigned divide for n < 2^24 by a runtime divisor (inv = 1.0f/d): q = n / d, r = n % d
 __device__ __forceinline__ void fast_divmod(uint32_t n, uint32_t d, float inv, uint32_t& q, uint32_t& r) {
   q = (uint32_t)((float)n * inv);

@@ -13,6 +13,8 @@
 //   FocalLoss on mean CE                                              loss/focal.py:17-21
 //   accuracy top-1/5                                                  util/utils.py:343-358
 //   optim.SGD(momentum, coupled weight decay on group 0)              train.py:196, :313-316
+#include <stdio.h>
+
 #include "common.h"
 #include "frhip_internal.h"
 
@@ -179,22 +181,40 @@ __device__ __forceinline__ void margin_cols_bwd(const float* __restrict__ g, con
   }
 }
 
+// The opening of every walker kernel: wave w of block y has row 4 y + w; the waves past the last row leave at once, the
+// others run body(row, its label, has: the label selects a column of the row).
+template <typename Body>
+__device__ __forceinline__ void walk_row(const long long* __restrict__ label, int rows, int N, Body body) {
+  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const long long lab = label[row];
+  body(row, lab, lab >= 0 && lab < N);
+}
+
+// Every wave of a row derives the same K row values; the wave of column chunk 0 leaves them in rowv [K][rows].
+template <int K>
+__device__ __forceinline__ void chunk0_store(float* __restrict__ rowv, int rows, int row, const float (&v)[K]) {
+  if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) rowv[k * rows + row] = v[k];
+  }
+}
+
 // kind 2: out = nrm * (label ? sphere : c), nrm = ||x_m|| (p0 = 1 + lambda);  kind 3: out = p1 * (label ? c - p0 : c)
 __global__ __launch_bounds__(256) void margin_apply_kernel(const float* __restrict__ cos, const long long* __restrict__ label,
                                                            const float* __restrict__ inv_x, float* __restrict__ out,
                                                            int rows, int N, int ld, int kind, int mi, float p0, float p1) {
-  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const long long lab = label[row];
-  const float scale = kind == 2 ? 1.f / inv_x[row] : p1;
-  margin_cols_fwd(cos, out, row, N, ld, [&](int n, float raw) {
-    const float c = clamp1(raw);
-    float v = c;
-    if (n == lab) {
-      float unused;
-      v = kind == 2 ? sphere_label(c, mi, p0, &unused) : c - p0;
-    }
-    return v * scale;
+  walk_row(label, rows, N, [&](int row, long long lab, bool) {
+    const float scale = kind == 2 ? 1.f / inv_x[row] : p1;
+    margin_cols_fwd(cos, out, row, N, ld, [&](int n, float raw) {
+      const float c = clamp1(raw);
+      float v = c;
+      if (n == lab) {
+        float unused;
+        v = kind == 2 ? sphere_label(c, mi, p0, &unused) : c - p0;
+      }
+      return v * scale;
+    });
   });
 }
 
@@ -204,22 +224,21 @@ __global__ __launch_bounds__(256) void margin_apply_bwd_kernel(const float* __re
                                                                const float* __restrict__ inv_x, float* __restrict__ gcos,
                                                                float* __restrict__ r_part, int rows, int N, int ld, int ldg,
                                                                int kind, int mi, float p0, float p1) {
-  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const long long lab = label[row];
-  const float scale = kind == 2 ? 1.f / inv_x[row] : p1;
-  float r = 0.f;
-  margin_cols_bwd(g, cos, gcos, row, N, ld, ldg, [&](int n, float raw, float gg) {
-    const float c = clamp1(raw);
-    float a = c, d = 1.f;
-    if (kind == 2 && n == lab) a = sphere_label(c, mi, p0, &d);
-    if (kind == 2) r = fmaf(gg, a, r);
-    return gg * scale * d;
+  walk_row(label, rows, N, [&](int row, long long lab, bool) {
+    const float scale = kind == 2 ? 1.f / inv_x[row] : p1;
+    float r = 0.f;
+    margin_cols_bwd(g, cos, gcos, row, N, ld, ldg, [&](int n, float raw, float gg) {
+      const float c = clamp1(raw);
+      float a = c, d = 1.f;
+      if (kind == 2 && n == lab) a = sphere_label(c, mi, p0, &d);
+      if (kind == 2) r = fmaf(gg, a, r);
+      return gg * scale * d;
+    });
+    if (kind == 2) {
+      r = wave_sum(r);
+      if ((threadIdx.x & 63) == 0) r_part[(size_t)row * gridDim.x + blockIdx.x] = r;
+    }
   });
-  if (kind == 2) {
-    r = wave_sum(r);
-    if ((threadIdx.x & 63) == 0) r_part[(size_t)row * gridDim.x + blockIdx.x] = r;
-  }
 }
 
 // normalise backward plus the radial term of a row scale ||x|| (SphereFace's NormOfFeature, head/metrics.py:255,268):
@@ -328,12 +347,9 @@ __device__ __forceinline__ void curricular_row_values(float tl, int i, int rows,
 // batch mean of tl from the threads' double sums (256 threads, fixed order) and the update of t; both row kernels end here
 __device__ __forceinline__ void curricular_mean_update(double s, double* dred, float* __restrict__ mean,
                                                        float* __restrict__ t, int rows, int train) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  s = wave_sum_d(s);
-  if (lane == 0) dred[wave] = s;
-  __syncthreads();
-  if (tid == 0) {
-    const float mu = (float)((dred[0] + dred[1] + dred[2] + dred[3]) / rows);
+  block_put(dred, wave_sum_d(s));
+  if (threadIdx.x == 0) {
+    const float mu = (float)(waves_sum<4>(dred) / rows);
     mean[0] = mu;
     if (train) t[0] = __fadd_rn(__fmul_rn(mu, CURR_MOMENTUM), __fmul_rn(1.0f - CURR_MOMENTUM, t[0]));
   }
@@ -394,15 +410,14 @@ __global__ __launch_bounds__(256) void curricular_apply_kernel(const float* __re
                                                                const long long* __restrict__ label,
                                                                const float* __restrict__ rowv, const float* __restrict__ t,
                                                                float* __restrict__ out, int rows, int N, int ld, float s) {
-  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const long long lab = label[row];
-  const float ctm = rowv[rows + row], fin = rowv[2 * rows + row], tt = t[0];
-  margin_cols_fwd(cos, out, row, N, ld, [&](int n, float raw) {
-    const float c = clamp1(raw);
-    float v = c > ctm ? c * (tt + c) : c;
-    if (n == lab) v = fin;
-    return v * s;
+  walk_row(label, rows, N, [&](int row, long long lab, bool) {
+    const float ctm = rowv[rows + row], fin = rowv[2 * rows + row], tt = t[0];
+    margin_cols_fwd(cos, out, row, N, ld, [&](int n, float raw) {
+      const float c = clamp1(raw);
+      float v = c > ctm ? c * (tt + c) : c;
+      if (n == lab) v = fin;
+      return v * s;
+    });
   });
 }
 
@@ -413,16 +428,15 @@ __global__ __launch_bounds__(256) void curricular_bwd_kernel(const float* __rest
                                                              const float* __restrict__ rowv, const float* __restrict__ t,
                                                              float* __restrict__ gcos, int rows, int N, int ld, int ldg,
                                                              float cos_m, float sin_m, float s) {
-  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const long long lab = label[row];
-  const float tl = rowv[row], ctm = rowv[rows + row], tt = t[0];
-  const float dlab = rowv[3 * rows + row] != 0.f ? cos_m + sin_m * tl / sqrtf(1.0f - tl * tl) : 1.f;
-  margin_cols_bwd(g, cos, gcos, row, N, ld, ldg, [&](int n, float raw, float gg) {
-    const float c = clamp1(raw);
-    float d = c > ctm ? tt + 2.f * c : 1.f;
-    if (n == lab) d = dlab;
-    return gg * s * d;
+  walk_row(label, rows, N, [&](int row, long long lab, bool) {
+    const float tl = rowv[row], ctm = rowv[rows + row], tt = t[0];
+    const float dlab = rowv[3 * rows + row] != 0.f ? cos_m + sin_m * tl / sqrtf(1.0f - tl * tl) : 1.f;
+    margin_cols_bwd(g, cos, gcos, row, N, ld, ldg, [&](int n, float raw, float gg) {
+      const float c = clamp1(raw);
+      float d = c > ctm ? tt + 2.f * c : 1.f;
+      if (n == lab) d = dlab;
+      return gg * s * d;
+    });
   });
 }
 
@@ -466,15 +480,14 @@ __global__ __launch_bounds__(256) void magface_apply_kernel(const float* __restr
                                                             const long long* __restrict__ label,
                                                             const float* __restrict__ rowv, float* __restrict__ out,
                                                             int rows, int N, int ld, float s, float margin_am) {
-  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const long long lab = label[row];
-  const float cos_m = rowv[rows + row], sin_m = rowv[2 * rows + row], min_cos = rowv[3 * rows + row];
-  margin_cols_fwd(cos, out, row, N, ld, [&](int n, float raw) {
-    const float c = clamp1(raw);
-    float v = c;
-    if (n == lab) v = c > min_cos ? c * cos_m - sqrtf(1.0f - c * c) * sin_m : c - margin_am;
-    return v * s;
+  walk_row(label, rows, N, [&](int row, long long lab, bool) {
+    const float cos_m = rowv[rows + row], sin_m = rowv[2 * rows + row], min_cos = rowv[3 * rows + row];
+    margin_cols_fwd(cos, out, row, N, ld, [&](int n, float raw) {
+      const float c = clamp1(raw);
+      float v = c;
+      if (n == lab) v = c > min_cos ? c * cos_m - sqrtf(1.0f - c * c) * sin_m : c - margin_am;
+      return v * s;
+    });
   });
 }
 
@@ -487,28 +500,26 @@ __global__ __launch_bounds__(256) void magface_bwd_kernel(const float* __restric
                                                           const float* __restrict__ rowv, float* __restrict__ gcos,
                                                           float* __restrict__ r, int rows, int N, int ld, int ldg, float s,
                                                           float slope, double inv_ua2, float lamda) {
-  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const long long lab = label[row];
-  const bool has = lab >= 0 && lab < N;
-  const float cos_m = rowv[rows + row], sin_m = rowv[2 * rows + row], min_cos = rowv[3 * rows + row];
-  margin_cols_bwd(g, cos, gcos, row, N, ld, ldg, [&](int n, float raw, float gg) {
-    const float c = clamp1(raw);
-    float d = 1.f;
-    if (n == lab && c > min_cos) d = cos_m + sin_m * c / sqrtf(1.0f - c * c);
-    return gg * s * d;
-  });
-  const int owner = has ? (int)(lab / MARGIN_COLS) : 0;
-  if ((int)blockIdx.x == owner && (threadIdx.x & 63) == 0) {
-    const float a = rowv[row];
-    float v = 0.f;
-    if (has) {
-      const float c = clamp1(cos[(size_t)row * ld + lab]);
-      if (c > min_cos) v = g[(size_t)row * N + lab] * s * (-(sqrtf(1.0f - c * c) * cos_m + c * sin_m)) * slope;
+  walk_row(label, rows, N, [&](int row, long long lab, bool has) {
+    const float cos_m = rowv[rows + row], sin_m = rowv[2 * rows + row], min_cos = rowv[3 * rows + row];
+    margin_cols_bwd(g, cos, gcos, row, N, ld, ldg, [&](int n, float raw, float gg) {
+      const float c = clamp1(raw);
+      float d = 1.f;
+      if (n == lab && c > min_cos) d = cos_m + sin_m * c / sqrtf(1.0f - c * c);
+      return gg * s * d;
+    });
+    const int owner = has ? (int)((unsigned)lab / MARGIN_COLS) : 0;  // has: 0 <= lab < N, an int
+    if ((int)blockIdx.x == owner && (threadIdx.x & 63) == 0) {
+      const float a = rowv[row];
+      float v = 0.f;
+      if (has) {
+        const float c = clamp1(cos[(size_t)row * ld + lab]);
+        if (c > min_cos) v = g[(size_t)row * N + lab] * s * (-(sqrtf(1.0f - c * c) * cos_m + c * sin_m)) * slope;
+      }
+      if (glossg) v += glossg[row] * lamda * (float)(inv_ua2 - 1.0 / ((double)a * a));
+      r[row] = rowv[5 * rows + row] != 0.f ? v : 0.f;
     }
-    if (glossg) v += glossg[row] * lamda * (float)(inv_ua2 - 1.0 / ((double)a * a));
-    r[row] = rowv[5 * rows + row] != 0.f ? v : 0.f;
-  }
+  });
 }
 
 // ------------------------------------------------------------------------------------------ AdaCos
@@ -539,13 +550,9 @@ __global__ __launch_bounds__(ADACOS_ROW_THREADS) void adacos_rows_kernel(const f
     for (int j = 0; j < 4; ++j)
       if (n + j < N && n + j != lab) acc += (double)expf(s * ch[j]);  // the raw cosine, no clamp (:363)
   }
-  acc = wave_sum_d(acc);
-  if ((tid & 63) == 0) dred[tid >> 6] = acc;
-  __syncthreads();
+  block_put(dred, wave_sum_d(acc));
   if (tid == 0) {
-    double sum = 0.0;
-    for (int w = 0; w < ADACOS_ROW_THREADS / 64; ++w) sum += dred[w];
-    rowv[row] = (float)sum;
+    rowv[row] = (float)waves_sum<ADACOS_ROW_THREADS / 64>(dred);
     rowv[rows + row] = (lab >= 0 && lab < N) ? crow[lab] : ADACOS_NO_TARGET;
   }
 }
@@ -562,7 +569,7 @@ __global__ __launch_bounds__(256) void adacos_scale_kernel(const float* __restri
   __shared__ float tile[256];
   __shared__ int nred[4], bad[4];
   __shared__ float sel;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const float* tc = rowv + rows;
   double acc = 0.0;
   int cnt = 0, isn = 0;
@@ -575,13 +582,8 @@ __global__ __launch_bounds__(256) void adacos_scale_kernel(const float* __restri
   acc = wave_sum_d(acc);
   const int wcnt = (int)wave_sum((float)cnt);  // cnt <= rows / 256 + 1 per thread: exact in fp32 below 2^24 rows
   const int wnan = __any(isn);
-  if (lane == 0) {
-    dred[wave] = acc;
-    nred[wave] = wcnt;
-    bad[wave] = wnan;
-  }
-  __syncthreads();
-  const int n = nred[0] + nred[1] + nred[2] + nred[3];
+  block_put(dred, acc, nred, wcnt, bad, wnan);
+  const int n = waves_sum<4>(nred);
   if (n == 0) return;  // no row has a target: the scale stays (uniform over the workgroup)
   const int want = (n - 1) / 2;
   for (int base = 0; base < rows; base += 256) {
@@ -602,7 +604,7 @@ __global__ __launch_bounds__(256) void adacos_scale_kernel(const float* __restri
   }
   __syncthreads();
   if (tid == 0) {
-    const double b_avg = (dred[0] + dred[1] + dred[2] + dred[3]) / rows;
+    const double b_avg = waves_sum<4>(dred) / rows;
     const float lo = (float)(-1.0 + 1e-7), hi = (float)(1.0 - 1e-7);  // the clamp of :359 on fp32 cosines
     const float c = sel < lo ? lo : (sel > hi ? hi : sel);
     // cos(min(pi/4, acos(c))) = max(cos(pi/4), c): cos falls on [0, pi], so neither the angle nor its cosine is formed
@@ -682,18 +684,10 @@ __global__ __launch_bounds__(NPCFACE_ROW_THREADS) void npcface_rows_kernel(const
   acc = wave_sum_d(acc);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-  if ((tid & 63) == 0) {
-    dred[tid >> 6] = acc;
-    nred[tid >> 6] = cnt;
-  }
-  __syncthreads();
+  block_put(dred, acc, nred, cnt);
   if (tid == 0) {
-    double sum = 0.0;
-    int count = 0;
-    for (int w = 0; w < NPCFACE_ROW_THREADS / 64; ++w) {
-      sum += dred[w];
-      count += nred[w];
-    }
+    const double sum = waves_sum<NPCFACE_ROW_THREADS / 64>(dred);
+    const int count = waves_sum<NPCFACE_ROW_THREADS / 64>(nred);
     const float avg = (float)(sum / (double)max(count, 1));  // clamp(count, 1, num_class) (:627): count <= N - 1
     const float newm = m0 + m1 * avg;
     const float cn = cosf(newm), sm = sinf(newm);
@@ -712,15 +706,14 @@ __global__ __launch_bounds__(256) void npcface_apply_kernel(const float* __restr
                                                             const long long* __restrict__ label,
                                                             const float* __restrict__ rowv, float* __restrict__ out,
                                                             int rows, int N, int ld, float t, float a, float s) {
-  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const long long lab = label[row];
-  const float ctm = rowv[rows + row], fin = rowv[2 * rows + row];
-  margin_cols_fwd(cos, out, row, N, ld, [&](int n, float raw) {
-    const float c = clamp1(raw);
-    float v = c > ctm ? t * c + a : c;
-    if (n == lab) v = fin;
-    return v * s;
+  walk_row(label, rows, N, [&](int row, long long lab, bool) {
+    const float ctm = rowv[rows + row], fin = rowv[2 * rows + row];
+    margin_cols_fwd(cos, out, row, N, ld, [&](int n, float raw) {
+      const float c = clamp1(raw);
+      float v = c > ctm ? t * c + a : c;
+      if (n == lab) v = fin;
+      return v * s;
+    });
   });
 }
 
@@ -730,15 +723,14 @@ __global__ __launch_bounds__(256) void npcface_bwd_kernel(const float* __restric
                                                           const long long* __restrict__ label,
                                                           const float* __restrict__ rowv, float* __restrict__ gcos, int rows,
                                                           int N, int ld, int ldg, float t, float s) {
-  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const long long lab = label[row];
-  const float ctm = rowv[rows + row], dlab = rowv[3 * rows + row];
-  margin_cols_bwd(g, cos, gcos, row, N, ld, ldg, [&](int n, float raw, float gg) {
-    const float c = clamp1(raw);
-    float d = c > ctm ? t : 1.f;
-    if (n == lab) d = dlab;
-    return gg * s * d;
+  walk_row(label, rows, N, [&](int row, long long lab, bool) {
+    const float ctm = rowv[rows + row], dlab = rowv[3 * rows + row];
+    margin_cols_bwd(g, cos, gcos, row, N, ld, ldg, [&](int n, float raw, float gg) {
+      const float c = clamp1(raw);
+      float d = c > ctm ? t : 1.f;
+      if (n == lab) d = dlab;
+      return gg * s * d;
+    });
   });
 }
 
@@ -754,10 +746,10 @@ struct MvRow {
   float gt, thr, fin, dfin;
 };
 
-__device__ __forceinline__ MvRow mv_softmax_row(const float* __restrict__ crow, long long lab, int N, int is_am, float p0,
+__device__ __forceinline__ MvRow mv_softmax_row(const float* __restrict__ crow, long long lab, bool has, int is_am, float p0,
                                                 float p1) {
   MvRow r = {0.f, __builtin_inff(), 0.f, 0.f};
-  if (lab < 0 || lab >= N) return r;
+  if (!has) return r;
   const float gt = crow[lab];
   r.gt = gt;
   if (is_am) {
@@ -779,21 +771,15 @@ __global__ __launch_bounds__(256) void mv_softmax_apply_kernel(const float* __re
                                                                float* __restrict__ rowv, float* __restrict__ out, int rows,
                                                                int N, int ld, int is_am, float p0, float p1, float w,
                                                                float s) {
-  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const long long lab = label[row];
-  const MvRow r = mv_softmax_row(cos + (size_t)row * ld, lab, N, is_am, p0, p1);
-  if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) {
-    rowv[row] = r.gt;
-    rowv[rows + row] = r.thr;
-    rowv[2 * rows + row] = r.fin;
-    rowv[3 * rows + row] = r.dfin;
-  }
-  const float thr = r.thr, fin = r.fin, w1 = w - 1.0f;
-  margin_cols_fwd(cos, out, row, N, ld, [&](int n, float c) {
-    float v = c > thr ? w * c + w1 : c;
-    if (n == lab) v = fin;
-    return v * s;
+  walk_row(label, rows, N, [&](int row, long long lab, bool has) {
+    const MvRow r = mv_softmax_row(cos + (size_t)row * ld, lab, has, is_am, p0, p1);
+    chunk0_store(rowv, rows, row, {r.gt, r.thr, r.fin, r.dfin});
+    const float thr = r.thr, fin = r.fin, w1 = w - 1.0f;
+    margin_cols_fwd(cos, out, row, N, ld, [&](int n, float c) {
+      float v = c > thr ? w * c + w1 : c;
+      if (n == lab) v = fin;
+      return v * s;
+    });
   });
 }
 
@@ -803,14 +789,13 @@ __global__ __launch_bounds__(256) void mv_softmax_bwd_kernel(const float* __rest
                                                              const long long* __restrict__ label,
                                                              const float* __restrict__ rowv, float* __restrict__ gcos,
                                                              int rows, int N, int ld, int ldg, float w, float s) {
-  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const long long lab = label[row];
-  const float thr = rowv[rows + row], dlab = rowv[3 * rows + row];
-  margin_cols_bwd<false>(g, cos, gcos, row, N, ld, ldg, [&](int n, float c, float gg) {
-    float d = c > thr ? w : 1.f;
-    if (n == lab) d = dlab;
-    return gg * s * d;
+  walk_row(label, rows, N, [&](int row, long long lab, bool) {
+    const float thr = rowv[rows + row], dlab = rowv[3 * rows + row];
+    margin_cols_bwd<false>(g, cos, gcos, row, N, ld, ldg, [&](int n, float c, float gg) {
+      float d = c > thr ? w : 1.f;
+      if (n == lab) d = dlab;
+      return gg * s * d;
+    });
   });
 }
 
@@ -826,10 +811,10 @@ struct ArcNegRow {
   float gt, a, da;
 };
 
-__device__ __forceinline__ ArcNegRow arcneg_row(const float* __restrict__ crow, long long lab, int N, float thresh,
+__device__ __forceinline__ ArcNegRow arcneg_row(const float* __restrict__ crow, long long lab, bool has, float thresh,
                                                 float margin, float mm) {
   ArcNegRow r = {0.f, 0.f, 0.f};
-  if (lab < 0 || lab >= N) return r;
+  if (!has) return r;
   const float gt = crow[lab];
   r.gt = gt;
   if (gt > thresh) {
@@ -858,24 +843,18 @@ __global__ __launch_bounds__(256) void arcneg_apply_kernel(const float* __restri
                                                            float* __restrict__ rowv, float* __restrict__ out, int rows,
                                                            int N, int ld, float thresh, float margin, float mm,
                                                            float alpha, float sigma, float s) {
-  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const long long lab = label[row];
-  const ArcNegRow r = arcneg_row(cos + (size_t)row * ld, lab, N, thresh, margin, mm);
-  if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) {
-    rowv[row] = r.gt;
-    rowv[rows + row] = r.a;
-    rowv[2 * rows + row] = r.da;
-  }
-  const bool has = lab >= 0 && lab < N;
-  const float a = r.a, nis = -1.0f / sigma;
-  margin_cols_fwd(cos, out, row, N, ld, [&](int n, float c) {
-    float v = c;
-    if (has) {
-      const float t = arcneg_t(c, a, alpha, nis);
-      v = n == lab ? a : t * c + t - 1.0f;
-    }
-    return v * s;
+  walk_row(label, rows, N, [&](int row, long long lab, bool has) {
+    const ArcNegRow r = arcneg_row(cos + (size_t)row * ld, lab, has, thresh, margin, mm);
+    chunk0_store(rowv, rows, row, {r.gt, r.a, r.da});
+    const float a = r.a, nis = -1.0f / sigma;
+    margin_cols_fwd(cos, out, row, N, ld, [&](int n, float c) {
+      float v = c;
+      if (has) {
+        const float t = arcneg_t(c, a, alpha, nis);
+        v = n == lab ? a : t * c + t - 1.0f;
+      }
+      return v * s;
+    });
   });
 }
 
@@ -885,15 +864,13 @@ __global__ __launch_bounds__(256) void arcneg_bwd_kernel(const float* __restrict
                                                          const long long* __restrict__ label,
                                                          const float* __restrict__ rowv, float* __restrict__ gcos, int rows,
                                                          int N, int ld, int ldg, float alpha, float sigma, float s) {
-  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const long long lab = label[row];
-  const bool has = lab >= 0 && lab < N;
-  const float a = rowv[rows + row], dlab = rowv[2 * rows + row], nis = -1.0f / sigma;
-  margin_cols_bwd<false>(g, cos, gcos, row, N, ld, ldg, [&](int n, float c, float gg) {
-    float d = 1.f;
-    if (has) d = n == lab ? dlab : arcneg_t(c, a, alpha, nis);
-    return gg * s * d;
+  walk_row(label, rows, N, [&](int row, long long lab, bool has) {
+    const float a = rowv[rows + row], dlab = rowv[2 * rows + row], nis = -1.0f / sigma;
+    margin_cols_bwd<false>(g, cos, gcos, row, N, ld, ldg, [&](int n, float c, float gg) {
+      float d = 1.f;
+      if (has) d = n == lab ? dlab : arcneg_t(c, a, alpha, nis);
+      return gg * s * d;
+    });
   });
 }
 
@@ -914,14 +891,13 @@ __device__ __forceinline__ float circle_alpha(float c, bool lab, float o_p, floa
 __global__ __launch_bounds__(256) void circle_apply_kernel(const float* __restrict__ cos, const long long* __restrict__ label,
                                                            float* __restrict__ out, int rows, int N, int ld, float o_p,
                                                            float o_n, float delta_p, float delta_n, float gamma) {
-  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const long long lab = label[row];
-  margin_cols_fwd(cos, out, row, N, ld, [&](int n, float raw) {
-    const float c = clamp1(raw);
-    const bool pos = n == lab;
-    const float alpha = circle_alpha(c, pos, o_p, o_n);
-    return __fmul_rn(__fmul_rn(alpha, __fsub_rn(c, pos ? delta_p : delta_n)), gamma);
+  walk_row(label, rows, N, [&](int row, long long lab, bool) {
+    margin_cols_fwd(cos, out, row, N, ld, [&](int n, float raw) {
+      const float c = clamp1(raw);
+      const bool pos = n == lab;
+      const float alpha = circle_alpha(c, pos, o_p, o_n);
+      return __fmul_rn(__fmul_rn(alpha, __fsub_rn(c, pos ? delta_p : delta_n)), gamma);
+    });
   });
 }
 
@@ -931,11 +907,10 @@ __global__ __launch_bounds__(256) void circle_bwd_kernel(const float* __restrict
                                                          const long long* __restrict__ label, float* __restrict__ gcos,
                                                          int rows, int N, int ld, int ldg, float o_p, float o_n,
                                                          float gamma) {
-  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const long long lab = label[row];
-  margin_cols_bwd(g, cos, gcos, row, N, ld, ldg, [&](int n, float raw, float gg) {
-    return __fmul_rn(__fmul_rn(gg, gamma), circle_alpha(clamp1(raw), n == lab, o_p, o_n));
+  walk_row(label, rows, N, [&](int row, long long lab, bool) {
+    margin_cols_bwd(g, cos, gcos, row, N, ld, ldg, [&](int n, float raw, float gg) {
+      return __fmul_rn(__fmul_rn(gg, gamma), circle_alpha(clamp1(raw), n == lab, o_p, o_n));
+    });
   });
 }
 
@@ -945,7 +920,7 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ 
                                                       int* __restrict__ rank, int N, int ld) {
   __shared__ float sred[4];
   __shared__ int ired[4];
-  const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int m = blockIdx.x, tid = threadIdx.x;
   const float* row = z + (size_t)m * ld;
   const long long lab = label[m];
   const float zl = (lab >= 0 && lab < N) ? row[lab] : 0.f;
@@ -956,34 +931,32 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ 
     mx = fmaxf(mx, v);
     cnt += v > zl ? 1 : 0;
   }
-  mx = wave_max(mx);
-  if (lane == 0) sred[wave] = mx;
-  __syncthreads();
-  mx = fmaxf(fmaxf(sred[0], sred[1]), fmaxf(sred[2], sred[3]));
+  block_put(sred, wave_max(mx));
+  mx = waves_max4(sred);
   __syncthreads();
   float se = 0.f;
   for (int n = tid; n < N; n += 256) se += __expf(row[n] - mx);
   se = wave_sum(se);
   float fc = wave_sum((float)cnt);
-  if (lane == 0) {
-    sred[wave] = se;
-    ired[wave] = (int)fc;
-  }
-  __syncthreads();
+  block_put(sred, se, ired, (int)fc);
   if (tid == 0) {
-    const float tot = sred[0] + sred[1] + sred[2] + sred[3];
-    const float l = mx + logf(tot);
+    const float l = mx + logf(waves_sum<4>(sred));
     lse[m] = l;
     ce[m] = l - zl;
-    rank[m] = ired[0] + ired[1] + ired[2] + ired[3];
+    rank[m] = waves_sum<4>(ired);
   }
 }
 
-__global__ void focal_finalize_kernel(const float* __restrict__ ce, const int* __restrict__ rank, int rows,
-                                      float gamma, float* __restrict__ scalars) {
+// What the two finalize kernels share (one workgroup of 256 threads): l = the batch mean of ce, added in double in a fixed
+// order (thread t adds rows t, t + 256, .., the xor butterfly, the four waves in order), and the top-1 / top-5 counts.
+// Thread 0 calls head(l), which writes scalars[0..1] (the loss and the slope focal_bwd_kernel multiplies by), and leaves
+// precision@1, precision@5 and l in scalars[2..4].
+template <typename Head>
+__device__ __forceinline__ void loss_finalize(const float* __restrict__ ce, const int* __restrict__ rank, int rows,
+                                              float* __restrict__ scalars, Head head) {
   __shared__ double dred[4];
   __shared__ int r1[4], r5[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   double s = 0.0;
   int c1 = 0, c5 = 0;
   for (int i = tid; i < rows; i += 256) {
@@ -993,24 +966,26 @@ __global__ void focal_finalize_kernel(const float* __restrict__ ce, const int* _
   }
   s = wave_sum_d(s);
   const float f1 = wave_sum((float)c1), f5 = wave_sum((float)c5);
-  if (lane == 0) {
-    dred[wave] = s;
-    r1[wave] = (int)f1;
-    r5[wave] = (int)f5;
-  }
-  __syncthreads();
+  block_put(dred, s, r1, (int)f1, r5, (int)f5);
   if (tid == 0) {
-    const float l = (float)((dred[0] + dred[1] + dred[2] + dred[3]) / rows);
+    const float l = (float)(waves_sum<4>(dred) / rows);
+    head(l);
+    scalars[2] = 100.0f * (float)waves_sum<4>(r1) / rows;
+    scalars[3] = 100.0f * (float)waves_sum<4>(r5) / rows;
+    scalars[4] = l;
+  }
+}
+
+__global__ void focal_finalize_kernel(const float* __restrict__ ce, const int* __restrict__ rank, int rows,
+                                      float gamma, float* __restrict__ scalars) {
+  loss_finalize(ce, rank, rows, scalars, [&](float l) {
     const float p = expf(-l);
     const float omp = 1.0f - p;
     const float w = powf(omp, gamma);
     scalars[0] = w * l;
     // d/dl [(1-p)^g * l] = g (1-p)^(g-1) p l + (1-p)^g          
     scalars[1] = gamma * powf(omp, gamma - 1.0f) * p * l + w;
-    scalars[2] = 100.0f * (float)(r1[0] + r1[1] + r1[2] + r1[3]) / rows;
-    scalars[3] = 100.0f * (float)(r5[0] + r5[1] + r5[2] + r5[3]) / rows;
-    scalars[4] = l;
-  }
+  });
 }
 
 __global__ void focal_bwd_kernel(const float* __restrict__ z, const long long* __restrict__ label,
@@ -1027,37 +1002,14 @@ __global__ void focal_bwd_kernel(const float* __restrict__ z, const long long* _
 }
 
 // nn.CrossEntropyLoss() on the rows of ce_rows_kernel (train.py:237-238, :300-302): focal_finalize_kernel without the
-// modulation.  The batch mean is added as there (double, the same fixed order), so scalars[4] has the same bits on the same
-// ce; scalars[1], the slope focal_bwd_kernel multiplies by, is exactly 1 (focal_finalize_kernel at gamma = 0 computes
-// 0 * powf(0, -1) = NaN there when the mean is 0).
+// modulation, so scalars[4] has the same bits on the same ce; scalars[1], the slope focal_bwd_kernel multiplies by, is
+// exactly 1 (focal_finalize_kernel at gamma = 0 computes 0 * powf(0, -1) = NaN there when the mean is 0).
 __global__ void ce_finalize_kernel(const float* __restrict__ ce, const int* __restrict__ rank, int rows,
                                    float* __restrict__ scalars) {
-  __shared__ double dred[4];
-  __shared__ int r1[4], r5[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  double s = 0.0;
-  int c1 = 0, c5 = 0;
-  for (int i = tid; i < rows; i += 256) {
-    s += (double)ce[i];
-    c1 += rank[i] < 1;
-    c5 += rank[i] < 5;
-  }
-  s = wave_sum_d(s);
-  const float f1 = wave_sum((float)c1), f5 = wave_sum((float)c5);
-  if (lane == 0) {
-    dred[wave] = s;
-    r1[wave] = (int)f1;
-    r5[wave] = (int)f5;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    const float l = (float)((dred[0] + dred[1] + dred[2] + dred[3]) / rows);
+  loss_finalize(ce, rank, rows, scalars, [&](float l) {
     scalars[0] = l;
     scalars[1] = 1.0f;
-    scalars[2] = 100.0f * (float)(r1[0] + r1[1] + r1[2] + r1[3]) / rows;
-    scalars[3] = 100.0f * (float)(r5[0] + r5[1] + r5[2] + r5[3]) / rows;
-    scalars[4] = l;
-  }
+  });
 }
 
 // ------------------------------------------------------------------------------------------ Softmax head (linear + bias)
@@ -1115,16 +1067,14 @@ __global__ __launch_bounds__(256) void col_sums_kernel(const float* __restrict__
 __global__ __launch_bounds__(256) void rank_rows_kernel(const float* __restrict__ z, const long long* __restrict__ label,
                                                         int* __restrict__ rank, int N, int ld) {
   __shared__ int ired[4];
-  const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int m = blockIdx.x, tid = threadIdx.x;
   const float* row = z + (size_t)m * ld;
   const long long lab = label[m];
   const float zl = (lab >= 0 && lab < N) ? row[lab] : INFINITY;
   int cnt = 0;
   for (int n = tid; n < N; n += 256) cnt += row[n] > zl ? 1 : 0;
-  const float fc = wave_sum((float)cnt);
-  if (lane == 0) ired[wave] = (int)fc;
-  __syncthreads();
-  if (tid == 0) rank[m] = ired[0] + ired[1] + ired[2] + ired[3];
+  block_put(ired, (int)wave_sum((float)cnt));
+  if (tid == 0) rank[m] = waves_sum<4>(ired);
 }
 
 // out[j] = scale * #{m: rank[m] < k_j}: precision@k of util/utils.py:343-358 from the label ranks, one launch instead of
@@ -1132,7 +1082,7 @@ __global__ __launch_bounds__(256) void rank_rows_kernel(const float* __restrict_
 __global__ __launch_bounds__(256) void topk_precision_kernel(const int* __restrict__ rank, int rows, int nk, int4 ks,
                                                              float scale, float* __restrict__ out) {
   __shared__ int ired[4][4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int kk[4] = {ks.x, ks.y, ks.z, ks.w};
   int cnt[4] = {0, 0, 0, 0};
   for (int m = tid; m < rows; m += 256) {
@@ -1141,12 +1091,9 @@ __global__ __launch_bounds__(256) void topk_precision_kernel(const int* __restri
     for (int j = 0; j < 4; ++j) cnt[j] += (j < nk && r < kk[j]) ? 1 : 0;
   }
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float fc = wave_sum((float)cnt[j]);  // exact: counts below 2^24
-    if (lane == 0) ired[j][wave] = (int)fc;
-  }
-  __syncthreads();
-  if (tid < nk) out[tid] = (float)(ired[tid][0] + ired[tid][1] + ired[tid][2] + ired[tid][3]) * scale;
+  for (int j = 0; j < 4; ++j) cnt[j] = (int)wave_sum((float)cnt[j]);  // exact: counts below 2^24
+  block_put(ired[0], cnt[0], ired[1], cnt[1], ired[2], cnt[2], ired[3], cnt[3]);
+  if (tid < nk) out[tid] = (float)waves_sum<4>(ired[tid]) * scale;
 }
 
 // ------------------------------------------------------------------------------------------ class-sharded softmax
@@ -1157,24 +1104,20 @@ __global__ __launch_bounds__(256) void shard_row_stats_kernel(const float* __res
                                                               const long long* __restrict__ label,
                                                               float* __restrict__ stats, int rows, int N, int ld) {
   __shared__ float sred[4];
-  const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int m = blockIdx.x, tid = threadIdx.x;
   const float* row = z + (size_t)m * ld;
   float mx = -INFINITY;
   for (int n = tid; n < N; n += 256) mx = fmaxf(mx, row[n]);
-  mx = wave_max(mx);
-  if (lane == 0) sred[wave] = mx;
-  __syncthreads();
-  mx = fmaxf(fmaxf(sred[0], sred[1]), fmaxf(sred[2], sred[3]));
+  block_put(sred, wave_max(mx));
+  mx = waves_max4(sred);
   __syncthreads();
   float se = 0.f;
   for (int n = tid; n < N; n += 256) se += __expf(row[n] - mx);
-  se = wave_sum(se);
-  if (lane == 0) sred[wave] = se;
-  __syncthreads();
+  block_put(sred, wave_sum(se));
   if (tid == 0) {
     const long long lab = label[m];
     stats[m] = mx;
-    stats[rows + m] = sred[0] + sred[1] + sred[2] + sred[3];
+    stats[rows + m] = waves_sum<4>(sred);
     stats[2 * rows + m] = (lab >= 0 && lab < N) ? row[lab] : 0.f;
   }
 }
@@ -1201,15 +1144,13 @@ __global__ void shard_combine_kernel(const float* __restrict__ stats_all, int wo
 __global__ __launch_bounds__(256) void shard_rank_rows_kernel(const float* __restrict__ z, const float* __restrict__ t,
                                                               int* __restrict__ rank, int N, int ld) {
   __shared__ int ired[4];
-  const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int m = blockIdx.x, tid = threadIdx.x;
   const float* row = z + (size_t)m * ld;
   const float zl = t[m];
   int cnt = 0;
   for (int n = tid; n < N; n += 256) cnt += row[n] > zl ? 1 : 0;
-  const float fc = wave_sum((float)cnt);
-  if (lane == 0) ired[wave] = (int)fc;
-  __syncthreads();
-  if (tid == 0) rank[m] = ired[0] + ired[1] + ired[2] + ired[3];
+  block_put(ired, (int)wave_sum((float)cnt));
+  if (tid == 0) rank[m] = waves_sum<4>(ired);
 }
 
 // ------------------------------------------------------------------------------------------ SGD
@@ -1304,14 +1245,26 @@ extern "C" int fr_margin_bwd(const float* g, const int64_t* label, const float* 
 
 extern "C" int fr_margin_apply_parts(int ldg) { return (ldg + MARGIN_COLS - 1) / MARGIN_COLS; }
 
+// Shape check and launch of a walker kernel for the entry point `entry` (its name opens the error text): four rows per
+// workgroup, MARGIN_COLS columns per blockIdx.x of the pitch `walk` the kernel walks: gcos's ldg >= ld for a backward
+// kernel; an apply kernel walks the cosines' own pitch and passes ld twice.
+template <typename... P, typename... A>
+static int launch_walker(const char* entry, void (*kern)(P...), void* stream, int rows, int N, int ld, int walk, A... args) {
+  if (rows <= 0 || N <= 0 || ld < N || ld % 4 || walk < ld || walk % 4) {
+    char msg[128];
+    snprintf(msg, sizeof(msg), "%s: shape (rows > 0, ld >= N > 0, ldg >= ld if there is one, multiples of 4)", entry);
+    FR_UNSUPPORTED(msg);
+  }
+  hipLaunchKernelGGL(kern, dim3(fr_margin_apply_parts(walk), (rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, args...);
+  FR_LAUNCH_CHECK();
+}
+
 extern "C" int fr_margin_apply(const float* cos, const int64_t* label, const float* inv_x, float* out, int rows, int N,
                                int ld, int kind, int mi, float p0, float p1, void* stream) {
   if (kind != 2 && kind != 3) FR_UNSUPPORTED("fr_margin_apply: kind 2 (SphereFace) or 3 (Am_softmax)");
   if (kind == 2 && (mi < 0 || mi > 5)) FR_UNSUPPORTED("fr_margin_apply: SphereFace m in 0..5");
-  if (rows <= 0 || N <= 0 || ld < N || ld % 4) FR_UNSUPPORTED("fr_margin_apply: shape (ld >= N, multiple of 4)");
-  hipLaunchKernelGGL(margin_apply_kernel, dim3(fr_margin_apply_parts(ld), (rows + 3) / 4), dim3(256), 0,
-                     (hipStream_t)stream, cos, (const long long*)label, inv_x, out, rows, N, ld, kind, mi, p0, p1);
-  FR_LAUNCH_CHECK();
+  return launch_walker("fr_margin_apply", margin_apply_kernel, stream, rows, N, ld, ld, cos, (const long long*)label, inv_x,
+                       out, rows, N, ld, kind, mi, p0, p1);
 }
 
 extern "C" int fr_margin_apply_bwd(const float* g, const float* cos, const int64_t* label, const float* inv_x, float* gcos,
@@ -1319,12 +1272,8 @@ extern "C" int fr_margin_apply_bwd(const float* g, const float* cos, const int64
                                    void* stream) {
   if (kind != 2 && kind != 3) FR_UNSUPPORTED("fr_margin_apply_bwd: kind 2 (SphereFace) or 3 (Am_softmax)");
   if (kind == 2 && (mi < 0 || mi > 5)) FR_UNSUPPORTED("fr_margin_apply_bwd: SphereFace m in 0..5");
-  if (rows <= 0 || N <= 0 || ld < N || ld % 4 || ldg < ld || ldg % 4)
-    FR_UNSUPPORTED("fr_margin_apply_bwd: shape (ldg >= ld >= N, multiples of 4)");
-  hipLaunchKernelGGL(margin_apply_bwd_kernel, dim3(fr_margin_apply_parts(ldg), (rows + 3) / 4), dim3(256), 0,
-                     (hipStream_t)stream, g, cos, (const long long*)label, inv_x, gcos, r_part, rows, N, ld, ldg, kind, mi,
-                     p0, p1);
-  FR_LAUNCH_CHECK();
+  return launch_walker("fr_margin_apply_bwd", margin_apply_bwd_kernel, stream, rows, N, ld, ldg, g, cos,
+                       (const long long*)label, inv_x, gcos, r_part, rows, N, ld, ldg, kind, mi, p0, p1);
 }
 
 extern "C" int fr_normalize_bwd_radial(const float* G, const float* x, const float* inv, const float* r_part, int nparts,
@@ -1379,20 +1328,15 @@ extern "C" int fr_curricular_ema(float* t, const float* mean, float scale, void*
 
 extern "C" int fr_curricular_apply(const float* cos, const int64_t* label, const float* rowv, const float* t, float* out,
                                    int rows, int N, int ld, float s, void* stream) {
-  if (rows <= 0 || N <= 0 || ld < N || ld % 4) FR_UNSUPPORTED("fr_curricular_apply: shape (ld >= N, multiple of 4)");
-  hipLaunchKernelGGL(curricular_apply_kernel, dim3(fr_margin_apply_parts(ld), (rows + 3) / 4), dim3(256), 0,
-                     (hipStream_t)stream, cos, (const long long*)label, rowv, t, out, rows, N, ld, s);
-  FR_LAUNCH_CHECK();
+  return launch_walker("fr_curricular_apply", curricular_apply_kernel, stream, rows, N, ld, ld, cos, (const long long*)label,
+                       rowv, t, out, rows, N, ld, s);
 }
 
 extern "C" int fr_curricular_bwd(const float* g, const float* cos, const int64_t* label, const float* rowv, const float* t,
                                  float* gcos, int rows, int N, int ld, int ldg, float cos_m, float sin_m, float s,
                                  void* stream) {
-  if (rows <= 0 || N <= 0 || ld < N || ld % 4 || ldg < ld || ldg % 4)
-    FR_UNSUPPORTED("fr_curricular_bwd: shape (ldg >= ld >= N, multiples of 4)");
-  hipLaunchKernelGGL(curricular_bwd_kernel, dim3(fr_margin_apply_parts(ldg), (rows + 3) / 4), dim3(256), 0,
-                     (hipStream_t)stream, g, cos, (const long long*)label, rowv, t, gcos, rows, N, ld, ldg, cos_m, sin_m, s);
-  FR_LAUNCH_CHECK();
+  return launch_walker("fr_curricular_bwd", curricular_bwd_kernel, stream, rows, N, ld, ldg, g, cos, (const long long*)label,
+                       rowv, t, gcos, rows, N, ld, ldg, cos_m, sin_m, s);
 }
 
 extern "C" int fr_magface_rows(const float* x, float* rowv, int rows, int D, float l_a, float u_a, float l_margin,
@@ -1406,22 +1350,17 @@ extern "C" int fr_magface_rows(const float* x, float* rowv, int rows, int D, flo
 
 extern "C" int fr_magface_apply(const float* cos, const int64_t* label, const float* rowv, float* out, int rows, int N,
                                 int ld, float s, float margin_am, void* stream) {
-  if (rows <= 0 || N <= 0 || ld < N || ld % 4) FR_UNSUPPORTED("fr_magface_apply: shape (ld >= N, multiple of 4)");
-  hipLaunchKernelGGL(magface_apply_kernel, dim3(fr_margin_apply_parts(ld), (rows + 3) / 4), dim3(256), 0,
-                     (hipStream_t)stream, cos, (const long long*)label, rowv, out, rows, N, ld, s, margin_am);
-  FR_LAUNCH_CHECK();
+  return launch_walker("fr_magface_apply", magface_apply_kernel, stream, rows, N, ld, ld, cos, (const long long*)label, rowv,
+                       out, rows, N, ld, s, margin_am);
 }
 
 extern "C" int fr_magface_bwd(const float* g, const float* glossg, const float* cos, const int64_t* label,
                               const float* rowv, float* gcos, float* r, int rows, int N, int ld, int ldg, float s, float l_a,
                               float u_a, float l_margin, float u_margin, float lamda, void* stream) {
-  if (rows <= 0 || N <= 0 || ld < N || ld % 4 || ldg < ld || ldg % 4)
-    FR_UNSUPPORTED("fr_magface_bwd: shape (ldg >= ld >= N, multiples of 4)");
   if (!(l_a > 0.f && u_a > l_a)) FR_UNSUPPORTED("fr_magface_bwd: 0 < l_a < u_a");
-  hipLaunchKernelGGL(magface_bwd_kernel, dim3(fr_margin_apply_parts(ldg), (rows + 3) / 4), dim3(256), 0,
-                     (hipStream_t)stream, g, glossg, cos, (const long long*)label, rowv, gcos, r, rows, N, ld, ldg, s,
-                     (u_margin - l_margin) / (u_a - l_a), 1.0 / ((double)u_a * u_a), lamda);
-  FR_LAUNCH_CHECK();
+  return launch_walker("fr_magface_bwd", magface_bwd_kernel, stream, rows, N, ld, ldg, g, glossg, cos,
+                       (const long long*)label, rowv, gcos, r, rows, N, ld, ldg, s, (u_margin - l_margin) / (u_a - l_a),
+                       1.0 / ((double)u_a * u_a), lamda);
 }
 
 extern "C" int fr_adacos_rows(const float* cos, const int64_t* label, const float* scale, float* rowv, int rows, int N,
@@ -1458,71 +1397,50 @@ extern "C" int fr_npcface_rows(const float* cos, const int64_t* label, float* ro
 
 extern "C" int fr_npcface_apply(const float* cos, const int64_t* label, const float* rowv, float* out, int rows, int N,
                                 int ld, float t, float a, float s, void* stream) {
-  if (rows <= 0 || N <= 0 || ld < N || ld % 4) FR_UNSUPPORTED("fr_npcface_apply: shape (ld >= N, multiple of 4)");
-  hipLaunchKernelGGL(npcface_apply_kernel, dim3(fr_margin_apply_parts(ld), (rows + 3) / 4), dim3(256), 0,
-                     (hipStream_t)stream, cos, (const long long*)label, rowv, out, rows, N, ld, t, a, s);
-  FR_LAUNCH_CHECK();
+  return launch_walker("fr_npcface_apply", npcface_apply_kernel, stream, rows, N, ld, ld, cos, (const long long*)label, rowv,
+                       out, rows, N, ld, t, a, s);
 }
 
 extern "C" int fr_npcface_bwd(const float* g, const float* cos, const int64_t* label, const float* rowv, float* gcos,
                               int rows, int N, int ld, int ldg, float t, float s, void* stream) {
-  if (rows <= 0 || N <= 0 || ld < N || ld % 4 || ldg < ld || ldg % 4)
-    FR_UNSUPPORTED("fr_npcface_bwd: shape (ldg >= ld >= N, multiples of 4)");
-  hipLaunchKernelGGL(npcface_bwd_kernel, dim3(fr_margin_apply_parts(ldg), (rows + 3) / 4), dim3(256), 0,
-                     (hipStream_t)stream, g, cos, (const long long*)label, rowv, gcos, rows, N, ld, ldg, t, s);
-  FR_LAUNCH_CHECK();
+  return launch_walker("fr_npcface_bwd", npcface_bwd_kernel, stream, rows, N, ld, ldg, g, cos, (const long long*)label, rowv,
+                       gcos, rows, N, ld, ldg, t, s);
 }
 
 extern "C" int fr_mv_softmax_apply(const float* cos, const int64_t* label, float* rowv, float* out, int rows, int N, int ld,
                                    int is_am, float p0, float p1, float w, float s, void* stream) {
-  if (rows <= 0 || N <= 0 || ld < N || ld % 4) FR_UNSUPPORTED("fr_mv_softmax_apply: shape (rows > 0, ld >= N > 0, ld a multiple of 4)");
-  hipLaunchKernelGGL(mv_softmax_apply_kernel, dim3(fr_margin_apply_parts(ld), (rows + 3) / 4), dim3(256), 0,
-                     (hipStream_t)stream, cos, (const long long*)label, rowv, out, rows, N, ld, is_am, p0, p1, w, s);
-  FR_LAUNCH_CHECK();
+  return launch_walker("fr_mv_softmax_apply", mv_softmax_apply_kernel, stream, rows, N, ld, ld, cos, (const long long*)label,
+                       rowv, out, rows, N, ld, is_am, p0, p1, w, s);
 }
 
 extern "C" int fr_mv_softmax_bwd(const float* g, const float* cos, const int64_t* label, const float* rowv, float* gcos,
                                  int rows, int N, int ld, int ldg, float w, float s, void* stream) {
-  if (rows <= 0 || N <= 0 || ld < N || ld % 4 || ldg < ld || ldg % 4)
-    FR_UNSUPPORTED("fr_mv_softmax_bwd: shape (rows > 0, ldg >= ld >= N > 0, multiples of 4)");
-  hipLaunchKernelGGL(mv_softmax_bwd_kernel, dim3(fr_margin_apply_parts(ldg), (rows + 3) / 4), dim3(256), 0,
-                     (hipStream_t)stream, g, cos, (const long long*)label, rowv, gcos, rows, N, ld, ldg, w, s);
-  FR_LAUNCH_CHECK();
+  return launch_walker("fr_mv_softmax_bwd", mv_softmax_bwd_kernel, stream, rows, N, ld, ldg, g, cos, (const long long*)label,
+                       rowv, gcos, rows, N, ld, ldg, w, s);
 }
 
 extern "C" int fr_arcneg_apply(const float* cos, const int64_t* label, float* rowv, float* out, int rows, int N, int ld,
                                float thresh, float margin, float mm, float alpha, float sigma, float s, void* stream) {
-  if (rows <= 0 || N <= 0 || ld < N || ld % 4) FR_UNSUPPORTED("fr_arcneg_apply: shape (rows > 0, ld >= N > 0, ld a multiple of 4)");
-  hipLaunchKernelGGL(arcneg_apply_kernel, dim3(fr_margin_apply_parts(ld), (rows + 3) / 4), dim3(256), 0,
-                     (hipStream_t)stream, cos, (const long long*)label, rowv, out, rows, N, ld, thresh, margin, mm, alpha,
-                     sigma, s);
-  FR_LAUNCH_CHECK();
+  return launch_walker("fr_arcneg_apply", arcneg_apply_kernel, stream, rows, N, ld, ld, cos, (const long long*)label, rowv,
+                       out, rows, N, ld, thresh, margin, mm, alpha, sigma, s);
 }
 
 extern "C" int fr_arcneg_bwd(const float* g, const float* cos, const int64_t* label, const float* rowv, float* gcos,
                              int rows, int N, int ld, int ldg, float alpha, float sigma, float s, void* stream) {
-  if (rows <= 0 || N <= 0 || ld < N || ld % 4 || ldg < ld || ldg % 4)
-    FR_UNSUPPORTED("fr_arcneg_bwd: shape (rows > 0, ldg >= ld >= N > 0, multiples of 4)");
-  hipLaunchKernelGGL(arcneg_bwd_kernel, dim3(fr_margin_apply_parts(ldg), (rows + 3) / 4), dim3(256), 0,
-                     (hipStream_t)stream, g, cos, (const long long*)label, rowv, gcos, rows, N, ld, ldg, alpha, sigma, s);
-  FR_LAUNCH_CHECK();
+  return launch_walker("fr_arcneg_bwd", arcneg_bwd_kernel, stream, rows, N, ld, ldg, g, cos, (const long long*)label, rowv,
+                       gcos, rows, N, ld, ldg, alpha, sigma, s);
 }
 
 extern "C" int fr_circle_apply(const float* cos, const int64_t* label, float* out, int rows, int N, int ld, float o_p,
                                float o_n, float delta_p, float delta_n, float gamma, void* stream) {
-  if (rows <= 0 || N <= 0 || ld < N || ld % 4) FR_UNSUPPORTED("fr_circle_apply: shape (rows > 0, ld >= N > 0, ld a multiple of 4)");
-  hipLaunchKernelGGL(circle_apply_kernel, dim3(fr_margin_apply_parts(ld), (rows + 3) / 4), dim3(256), 0,
-                     (hipStream_t)stream, cos, (const long long*)label, out, rows, N, ld, o_p, o_n, delta_p, delta_n, gamma);
-  FR_LAUNCH_CHECK();
+  return launch_walker("fr_circle_apply", circle_apply_kernel, stream, rows, N, ld, ld, cos, (const long long*)label, out,
+                       rows, N, ld, o_p, o_n, delta_p, delta_n, gamma);
 }
 
 extern "C" int fr_circle_bwd(const float* g, const float* cos, const int64_t* label, float* gcos, int rows, int N, int ld,
                              int ldg, float o_p, float o_n, float gamma, void* stream) {
-  if (rows <= 0 || N <= 0 || ld < N || ld % 4 || ldg < ld || ldg % 4)
-    FR_UNSUPPORTED("fr_circle_bwd: shape (rows > 0, ldg >= ld >= N > 0, multiples of 4)");
-  hipLaunchKernelGGL(circle_bwd_kernel, dim3(fr_margin_apply_parts(ldg), (rows + 3) / 4), dim3(256), 0,
-                     (hipStream_t)stream, g, cos, (const long long*)label, gcos, rows, N, ld, ldg, o_p, o_n, gamma);
-  FR_LAUNCH_CHECK();
+  return launch_walker("fr_circle_bwd", circle_bwd_kernel, stream, rows, N, ld, ldg, g, cos, (const long long*)label, gcos,
+                       rows, N, ld, ldg, o_p, o_n, gamma);
 }
 
 extern "C" int fr_ce_rows(const float* logits, const int64_t* label, float* lse, float* ce, int32_t* rank, int rows,

@@ -29,13 +29,21 @@ def _pad(n, m):
     return (n + m - 1) // m * m
 
 
-# One cosine-head pipeline under the heads.  Forward: ``_cosine_operands`` (normalised operands), the cosine GEMM
-# (``_raw_cosines``, or ArcFace / CosFace's fused margin epilogue), the head's row kernels.  Backward: the head's gcos
-# kernel, then ``_cosine_backward`` (both GEMMs and the normalisation backwards).
+# One cosine-head pipeline under the heads.  Forward: ``_cosine_front`` (``_cosine_operands``: normalised operands; the
+# cosine GEMM, ``_raw_cosines``; the logit store) or ArcFace / CosFace's fused margin epilogue, then the head's row kernels.
+# Backward: the head's gcos kernel (``_gcos_backward``), then ``_cosine_backward`` (both GEMMs and the normalisation
+# backwards).
 (ARCFACE, COSFACE, SPHEREFACE, AM_SOFTMAX, CURRICULAR, MAGFACE, ADACOS, NPCFACE, MV_SOFTMAX, CIRCLE, AM_SOFTMAX_N, ARCNEG,
  SOFTMAX) = range(13)
 # 0..3: the kernels' margin kinds.  AM_SOFTMAX_N is the FaceX-Zoo AM_Softmax (normalised embeddings) on the kernels' kind 3.
 # SOFTMAX is the plain linear head with a bias: no cosines, the same three GEMMs on operands that are not normalised.
+
+# The operand layout of each head, read by both directions: norm_x (the rows of x are normalised; Am_softmax's are not,
+# head/metrics.py:302-304) and col_weight (the weight is a [D, N] kernel normalised by columns, not [N, D] by rows).
+_OPERANDS = {ARCFACE: (True, False), COSFACE: (True, False), SPHEREFACE: (True, False), AM_SOFTMAX: (False, True),
+             CURRICULAR: (True, True), MAGFACE: (True, True), ADACOS: (True, False), NPCFACE: (True, True),
+             MV_SOFTMAX: (True, True), CIRCLE: (True, True), AM_SOFTMAX_N: (True, True), ARCNEG: (True, False),
+             SOFTMAX: (False, False)}
 
 # What a forward call keeps for its backward call; a head leaves what it does not use at None.  xn / wn [Np, D] / wt
 # [D, Np] are the GEMM operands (xn is x itself for Am_softmax), inv_x / inv_w the reciprocal norms, cos_t the target
@@ -48,9 +56,10 @@ HeadSaved = collections.namedtuple("HeadSaved", "x w label xn wn wt inv_x inv_w 
 HeadCfg = collections.namedtuple("HeadCfg", "kind Np ld s cos_m sin_m th easy mi p0 p1 mag", defaults=(None,) * 9)
 
 
-def _cosine_operands(x, weight, label, norm_x, col_weight):
-    """fp32 copies and the normalised GEMM operands of a head: rows of x (``norm_x``) and rows of an [N, D] weight or
-    columns of a [D, N] kernel (``col_weight``).  Returns (HeadSaved with x .. inv_w set, N, Np, ld)."""
+def _cosine_operands(kind, x, weight, label):
+    """fp32 copies and the normalised GEMM operands of a head of ``kind`` (``_OPERANDS``): rows of x, and rows of an [N, D]
+    weight or columns of a [D, N] kernel.  Returns (HeadSaved with x .. inv_w set, N, Np, ld)."""
+    norm_x, col_weight = _OPERANDS[kind]
     B, D = x.shape
     N = weight.shape[1] if col_weight else weight.shape[0]
     dev = x.device
@@ -96,16 +105,27 @@ def _logit_store(sv, N, ld):
     return store, (store if ld == N else store[:, :N])
 
 
-def _cosine_backward(sv, Np, gcos, need_x, need_w, x_bwd, col_weight, r_part=None, norm_w=True):
-    """(gx, gw) from gcos = d loss / d cos [B, Np] (columns >= N zero): the weight-gradient GEMM, the split-K data-gradient
-    GEMM and the normalisation backwards.  ``x_bwd``: "normalize", "radial" (SphereFace: plus the radial term of its row
-    scale, from ``r_part``) or None (the reduced G is the result: Am_softmax, and the class-sharded head's raw_x_grad).
-    ``col_weight``: gw in the [D, N] layout of a column-normalised kernel.  ``norm_w=False`` (the Softmax head: an [N, D]
-    weight that is not normalised, ``sv.inv_w`` None): gw is the GEMM's result itself, its first N rows.
+def _cosine_front(kind, x, weight, label):
+    """The forward front of a head whose row kernels work on the raw cosines: (HeadSaved with x .. inv_w and cos set, N,
+    Np, ld, the logit store [B, ld], its logits view [B, N])."""
+    sv, N, Np, ld = _cosine_operands(kind, x, weight, label)
+    sv = sv._replace(cos=_raw_cosines(sv, N, ld))
+    return (sv, N, Np, ld) + _logit_store(sv, N, ld)
+
+
+def _cosine_backward(sv, cfg, gcos, need_x, need_w, raw_x_grad=False, r_part=None):
+    """(gx, gw) from gcos = d loss / d cos [B, cfg.Np] (columns >= N zero): the weight-gradient GEMM, the split-K
+    data-gradient GEMM and the normalisation backwards.  gx goes through the backward of the row normalisation, with the
+    radial term of a row scale where ``r_part`` is given (SphereFace, MagFace); the reduced G itself is the result where x
+    was not normalised (``_OPERANDS``: Am_softmax, Softmax) and under ``raw_x_grad`` (the class-sharded head).  gw has the
+    weight's own layout; for the Softmax head (an [N, D] weight that is not normalised, ``sv.inv_w`` None) it is the GEMM's
+    result itself, its first N rows.
 
     Round 6: the two halves (three launches each, 55 us each at 7000 classes, neither fills the chip) run side by side when
     both are wanted: the weight's on the weight-gradient stream, which is idle until the backbone's backward pass starts.
     Every buffer is allocated on the calling stream, which waits for the side stream before this function returns."""
+    norm_x, col_weight = _OPERANDS[cfg.kind]
+    norm_w, Np = cfg.kind != SOFTMAX, cfg.Np
     B, D = sv.xn.shape
     N = sv.inv_w.shape[0] if norm_w else sv.w.shape[0]
     dev = sv.x.device
@@ -138,11 +158,11 @@ def _cosine_backward(sv, Np, gcos, need_x, need_w, x_bwd, col_weight, r_part=Non
         ops.conv(st, FR_F32, src=gcos, w=sv.wt, out=slab, B=B, RH=1, RW=1, SH=1, SW=1, SC=Np, N=D, KH=1, KW=1,
                  stride=1, pad=0, mode=0, lda=Np, ldc=D, pro=0, epi=ops.EPI_SLAB, out_f32=1, splitk=splitk)()
         ops.call("fr_reduce_parts", slab, splitk, 1, B * D, G, None, None, st)()
-        if x_bwd is None:
+        if raw_x_grad or not norm_x:
             gx = G
         else:
             gx = torch.empty(B, D, device=dev)
-            if x_bwd == "radial":
+            if r_part is not None:
                 ops.call("fr_normalize_bwd_radial", G, sv.x, sv.inv_x, r_part, r_part.shape[1], gx, B, D, st)()
             else:
                 ops.call("fr_normalize_bwd", G, sv.x, sv.inv_x, gx, B, D, st)()
@@ -153,11 +173,22 @@ def _cosine_backward(sv, Np, gcos, need_x, need_w, x_bwd, col_weight, r_part=Non
     return gx, gw
 
 
+def _gcos_backward(saved, cfg, g, need_x, need_w, raw_x_grad, launch):
+    """The backward body of a head that is one gcos kernel in front of ``_cosine_backward``: ``launch(g, gcos, B, N, st)``
+    is the head's one launch, from the fp32 contiguous upstream gradient into gcos [B, cfg.Np].  ``raw_x_grad``: return G =
+    d loss / d normalize(x) instead of gx (the class-sharded head sums G over ranks before it goes through the normalisation
+    backward, which is linear in G)."""
+    B, N = saved.x.shape[0], saved.inv_w.shape[0]
+    gcos = torch.empty(B, cfg.Np, device=saved.x.device)
+    launch(g.contiguous().float(), gcos, B, N, ops.current_stream_ptr())
+    return _cosine_backward(saved, cfg, gcos, need_x, need_w, raw_x_grad)
+
+
 def margin_forward(x, weight, label, kind, s, m, easy_margin):
     """ArcFace (kind 0) / CosFace (kind 1): logits = s * where(j == label, phi(cos), cos) for fp32 device tensors, the
     margin in the GEMM's epilogue.  Returns (logits, saved, cfg) for ``margin_backward``.  A label outside [0, N) selects
     nothing in its row (the class-sharded head passes -1 for rows whose label lives on another rank)."""
-    sv, N, Np, ld = _cosine_operands(x, weight, label, norm_x=True, col_weight=False)
+    sv, N, Np, ld = _cosine_operands(kind, x, weight, label)
     _, logits = _logit_store(sv, N, ld)
     cos_t = torch.zeros(x.shape[0], device=x.device)
     if kind == ARCFACE:
@@ -175,23 +206,19 @@ def margin_forward(x, weight, label, kind, s, m, easy_margin):
 def margin_backward(saved, cfg, g, need_x, need_w, raw_x_grad=False):
     """(gx, gw) of ``margin_forward``.  ``raw_x_grad``: return G = d loss / d normalize(x) instead of gx (the
     class-sharded head sums G over ranks before it goes through the normalisation backward, which is linear in G)."""
-    B, N = saved.x.shape[0], saved.w.shape[0]
-    gcos = torch.empty(B, cfg.Np, device=saved.x.device)
-    ops.call("fr_margin_bwd", g.contiguous().float(), saved.label, saved.cos_t, gcos, B, N, cfg.Np, cfg.kind, cfg.easy,
-             cfg.cos_m, cfg.sin_m, cfg.th, cfg.s, FR_F32, ops.current_stream_ptr())()
-    return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, None if raw_x_grad else "normalize", col_weight=False)
+    return _gcos_backward(saved, cfg, g, need_x, need_w, raw_x_grad, lambda g, gcos, B, N, st: ops.call(
+        "fr_margin_bwd", g, saved.label, saved.cos_t, gcos, B, N, cfg.Np, cfg.kind, cfg.easy, cfg.cos_m, cfg.sin_m, cfg.th,
+        cfg.s, FR_F32, st)())
 
 
 def margin_ext_forward(x, weight, label, kind, mi, p0, p1):
     """SphereFace (kind 2: ``weight`` [N, D], mi = m, p0 = 1 + lambda) or Am_softmax (kind 3: ``weight`` is the [D, N]
     kernel, p0 = m, p1 = s) logits for fp32 device tensors: fr_margin_apply on the raw cosines.  Returns (logits, saved,
     cfg) for ``margin_ext_backward``."""
-    sv, N, Np, ld = _cosine_operands(x, weight, label, norm_x=kind == SPHEREFACE, col_weight=kind == AM_SOFTMAX)
-    cos = _raw_cosines(sv, N, ld)
-    store, logits = _logit_store(sv, N, ld)
-    ops.call("fr_margin_apply", cos, sv.label, sv.inv_x, store, x.shape[0], N, ld, kind, int(mi), float(p0), float(p1),
+    sv, N, Np, ld, store, logits = _cosine_front(kind, x, weight, label)
+    ops.call("fr_margin_apply", sv.cos, sv.label, sv.inv_x, store, x.shape[0], N, ld, kind, int(mi), float(p0), float(p1),
              ops.current_stream_ptr())()
-    return logits, sv._replace(cos=cos), HeadCfg(kind, Np, ld, mi=int(mi), p0=float(p0), p1=float(p1))
+    return logits, sv, HeadCfg(kind, Np, ld, mi=int(mi), p0=float(p0), p1=float(p1))
 
 
 def margin_ext_backward(saved, cfg, g, need_x, need_w, raw_x_grad=False):
@@ -207,9 +234,8 @@ def margin_ext_backward(saved, cfg, g, need_x, need_w, raw_x_grad=False):
     ops.call("fr_margin_apply_bwd", g.contiguous().float(), saved.cos, saved.label, saved.inv_x, gcos, r_part, B, N, cfg.ld,
              cfg.Np, cfg.kind, cfg.mi, cfg.p0, cfg.p1, ops.current_stream_ptr())()
     if raw_x_grad:
-        return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, None, col_weight=not sphere) + (r_part,)
-    return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, "radial" if sphere else None, col_weight=not sphere,
-                            r_part=r_part)
+        return _cosine_backward(saved, cfg, gcos, need_x, need_w, raw_x_grad=True) + (r_part,)
+    return _cosine_backward(saved, cfg, gcos, need_x, need_w, r_part=r_part)
 
 
 def curricular_forward(x, kernel, label, t, s, m, group=None, target_cos=None, train=True):
@@ -220,53 +246,48 @@ def curricular_forward(x, kernel, label, t, s, m, group=None, target_cos=None, t
     of the gather of the target cosines (the class-sharded head: a row's label may live on another rank; the hook exchanges
     them); the row values and ``t`` (moved only if ``train``) then come from its result.  Returns (logits, saved, cfg) for
     ``curricular_backward``."""
-    sv, N, Np, ld = _cosine_operands(x, kernel, label, norm_x=True, col_weight=True)
+    sv, N, Np, ld, store, logits = _cosine_front(CURRICULAR, x, kernel, label)
     B = x.shape[0]
     st = ops.current_stream_ptr()
-    cos = _raw_cosines(sv, N, ld)
     cos_m, sin_m = math.cos(m), math.sin(m)
     th, mm = math.cos(math.pi - m), math.sin(math.pi - m) * m
     rowv = torch.empty(4, B, device=x.device)  # tl, ctm, final, branch flag
     mean = torch.empty(1, device=x.device)
     if target_cos is not None:
-        tl = target_cos(cos, sv.label, N, ld)
+        tl = target_cos(sv.cos, sv.label, N, ld)
         ops.call("fr_curricular_rows_from", tl, rowv, mean, t, B, cos_m, sin_m, th, mm, int(bool(train)), st)()
     else:
-        ops.call("fr_curricular_rows", cos, sv.label, rowv, mean, t, B, N, ld, cos_m, sin_m, th, mm, int(group is None), st)()
+        ops.call("fr_curricular_rows", sv.cos, sv.label, rowv, mean, t, B, N, ld, cos_m, sin_m, th, mm, int(group is None),
+                 st)()
     if group is not None and target_cos is None:
         import torch.distributed as dist
         dist.all_reduce(mean, group=group)  # one float, stays on the device
         ops.call("fr_curricular_ema", t, mean, 1.0 / dist.get_world_size(group), st)()
-    store, logits = _logit_store(sv, N, ld)
-    ops.call("fr_curricular_apply", cos, sv.label, rowv, t, store, B, N, ld, float(s), st)()
+    ops.call("fr_curricular_apply", sv.cos, sv.label, rowv, t, store, B, N, ld, float(s), st)()
     # the backward pass needs the t this forward call used: the buffer moves on with the next call
-    saved = sv._replace(cos=cos, rowv=rowv, t=t.clone())
+    saved = sv._replace(rowv=rowv, t=t.clone())
     return logits, saved, HeadCfg(CURRICULAR, Np, ld, s=float(s), cos_m=cos_m, sin_m=sin_m)
 
 
 def curricular_backward(saved, cfg, g, need_x, need_w, raw_x_grad=False):
     """(gx, gkernel) of ``curricular_forward``; gkernel is [D, N].  ``raw_x_grad``: as in ``margin_backward``."""
-    B, N = saved.x.shape[0], saved.inv_w.shape[0]
-    gcos = torch.empty(B, cfg.Np, device=saved.x.device)
-    ops.call("fr_curricular_bwd", g.contiguous().float(), saved.cos, saved.label, saved.rowv, saved.t, gcos, B, N, cfg.ld,
-             cfg.Np, cfg.cos_m, cfg.sin_m, cfg.s, ops.current_stream_ptr())()
-    return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, None if raw_x_grad else "normalize", col_weight=True)
+    return _gcos_backward(saved, cfg, g, need_x, need_w, raw_x_grad, lambda g, gcos, B, N, st: ops.call(
+        "fr_curricular_bwd", g, saved.cos, saved.label, saved.rowv, saved.t, gcos, B, N, cfg.ld, cfg.Np, cfg.cos_m, cfg.sin_m,
+        cfg.s, st)())
 
 
 def magface_forward(x, kernel, label, s, margin_am, l_a, u_a, l_margin, u_margin, lamda):
     """MagFace (head/metrics.py:512-553) for fp32 device tensors; ``kernel`` is [D, N].  Returns (logits [B, N], loss_g
     [B, 1] = lamda * (a / u_a^2 + 1 / a) with a = clamp(||x||, l_a, u_a), saved, cfg) for ``magface_backward``.  The row
     kernel takes the norms from x itself.  A label outside [0, N) selects nothing in its row."""
-    sv, N, Np, ld = _cosine_operands(x, kernel, label, norm_x=True, col_weight=True)
+    sv, N, Np, ld, store, logits = _cosine_front(MAGFACE, x, kernel, label)
     B = x.shape[0]
     st = ops.current_stream_ptr()
-    cos = _raw_cosines(sv, N, ld)
     mag = tuple(float(v) for v in (margin_am, l_a, u_a, l_margin, u_margin, lamda))
     rowv = torch.empty(6, B, device=x.device)  # a, cos_m, sin_m, min_cos, loss_g, inside
     ops.call("fr_magface_rows", sv.x, rowv, B, x.shape[1], *mag[1:], st)()
-    store, logits = _logit_store(sv, N, ld)
-    ops.call("fr_magface_apply", cos, sv.label, rowv, store, B, N, ld, float(s), mag[0], st)()
-    return logits, rowv[4].clone().view(B, 1), sv._replace(cos=cos, rowv=rowv), HeadCfg(MAGFACE, Np, ld, s=float(s), mag=mag)
+    ops.call("fr_magface_apply", sv.cos, sv.label, rowv, store, B, N, ld, float(s), mag[0], st)()
+    return logits, rowv[4].clone().view(B, 1), sv._replace(rowv=rowv), HeadCfg(MAGFACE, Np, ld, s=float(s), mag=mag)
 
 
 def magface_backward(saved, cfg, g, glossg, need_x, need_w):
@@ -282,7 +303,7 @@ def magface_backward(saved, cfg, g, glossg, need_x, need_w):
     r = torch.empty(B, device=dev)
     ops.call("fr_magface_bwd", g, glossg, saved.cos, saved.label, saved.rowv, gcos, r, B, N, cfg.ld, cfg.Np, cfg.s,
              *cfg.mag[1:], ops.current_stream_ptr())()
-    return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, "radial", col_weight=True, r_part=r.view(B, 1))
+    return _cosine_backward(saved, cfg, gcos, need_x, need_w, r_part=r.view(B, 1))
 
 
 def adacos_forward(x, weight, label, scale, group=None):
@@ -292,12 +313,11 @@ def adacos_forward(x, weight, label, scale, group=None):
     logits are the NEW scale times the unclamped cosines.  ``group``: every rank all-gathers the [2, B] row values and
     reduces the gathered rows in rank order, so every rank holds the bits of the scale of one head over the concatenated
     batch (equal batch sizes on every rank).  Returns (logits, saved, cfg) for ``adacos_backward``."""
-    sv, N, Np, ld = _cosine_operands(x, weight, label, norm_x=True, col_weight=False)
+    sv, N, Np, ld, store, logits = _cosine_front(ADACOS, x, weight, label)
     B = x.shape[0]
     st = ops.current_stream_ptr()
-    cos = _raw_cosines(sv, N, ld)
     rowv = torch.empty(2, B, device=x.device)  # sum of exp(scale * cos) off the label column, raw target cosine
-    ops.call("fr_adacos_rows", cos, sv.label, scale, rowv, B, N, ld, st)()
+    ops.call("fr_adacos_rows", sv.cos, sv.label, scale, rowv, B, N, ld, st)()
     rows = B
     if group is not None:
         import torch.distributed as dist
@@ -306,19 +326,16 @@ def adacos_forward(x, weight, label, scale, group=None):
         dist.all_gather_into_tensor(every, rowv, group=group)
         rowv, rows = every.permute(1, 0, 2).reshape(2, world * B), world * B  # [2][world * B], ranks in order
     ops.call("fr_adacos_scale", rowv, rows, scale, st)()
-    store, logits = _logit_store(sv, N, ld)
-    ops.call("fr_adacos_apply", cos, scale, store, B, N, ld, ld, st)()
+    ops.call("fr_adacos_apply", sv.cos, scale, store, B, N, ld, ld, st)()
     # the backward pass needs the scale this forward call used: the buffer moves on with the next call
-    return logits, sv._replace(cos=cos, t=scale.clone()), HeadCfg(ADACOS, Np, ld)
+    return logits, sv._replace(t=scale.clone()), HeadCfg(ADACOS, Np, ld)
 
 
 def adacos_backward(saved, cfg, g, need_x, need_w, raw_x_grad=False):
     """(gx, gweight) of ``adacos_forward``: the scale is a constant of the graph and the cosines are not clamped, so gcos =
     scale_used * g (columns N .. Np zero).  ``raw_x_grad``: as in ``margin_backward``."""
-    B, N = saved.x.shape[0], saved.inv_w.shape[0]
-    gcos = torch.empty(B, cfg.Np, device=saved.x.device)
-    ops.call("fr_adacos_apply", g.contiguous().float(), saved.t, gcos, B, N, N, cfg.Np, ops.current_stream_ptr())()
-    return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, None if raw_x_grad else "normalize", col_weight=False)
+    return _gcos_backward(saved, cfg, g, need_x, need_w, raw_x_grad, lambda g, gcos, B, N, st: ops.call(
+        "fr_adacos_apply", g, saved.t, gcos, B, N, N, cfg.Np, st)())
 
 
 def npcface_forward(x, kernel, label, s, npc):
@@ -328,26 +345,21 @@ def npcface_forward(x, kernel, label, s, npc):
     excluded; the sum in a fixed order) and from them the label column's value at the margin m0 + m1 * mean; a row kernel
     re-weights the hard negatives to t * c + a.  Nothing waits on the host.  A label outside [0, N) selects nothing and
     makes nothing hard in its row.  Returns (logits, saved, cfg) for ``npcface_backward``."""
-    sv, N, Np, ld = _cosine_operands(x, kernel, label, norm_x=True, col_weight=True)
+    sv, N, Np, ld, store, logits = _cosine_front(NPCFACE, x, kernel, label)
     B = x.shape[0]
     st = ops.current_stream_ptr()
     cos_m, sin_m, m0, m1, t, a = (float(v) for v in npc)
-    cos = _raw_cosines(sv, N, ld)
     rowv = torch.empty(6, B, device=x.device)  # gt, ctm, final, d final / d gt, avg, count
-    ops.call("fr_npcface_rows", cos, sv.label, rowv, B, N, ld, cos_m, sin_m, m0, m1, st)()
-    store, logits = _logit_store(sv, N, ld)
-    ops.call("fr_npcface_apply", cos, sv.label, rowv, store, B, N, ld, t, a, float(s), st)()
-    return logits, sv._replace(cos=cos, rowv=rowv), HeadCfg(NPCFACE, Np, ld, s=float(s), p0=t, p1=a)
+    ops.call("fr_npcface_rows", sv.cos, sv.label, rowv, B, N, ld, cos_m, sin_m, m0, m1, st)()
+    ops.call("fr_npcface_apply", sv.cos, sv.label, rowv, store, B, N, ld, t, a, float(s), st)()
+    return logits, sv._replace(rowv=rowv), HeadCfg(NPCFACE, Np, ld, s=float(s), p0=t, p1=a)
 
 
 def npcface_backward(saved, cfg, g, need_x, need_w, raw_x_grad=False):
     """(gx, gkernel) of ``npcface_forward``; gkernel is [D, N].  The margin m0 + m1 * mean, the hard mask and the branch are
     constants of the graph (:621 no_grad).  ``raw_x_grad``: as in ``margin_backward``."""
-    B, N = saved.x.shape[0], saved.inv_w.shape[0]
-    gcos = torch.empty(B, cfg.Np, device=saved.x.device)
-    ops.call("fr_npcface_bwd", g.contiguous().float(), saved.cos, saved.label, saved.rowv, gcos, B, N, cfg.ld, cfg.Np,
-             cfg.p0, cfg.s, ops.current_stream_ptr())()
-    return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, None if raw_x_grad else "normalize", col_weight=True)
+    return _gcos_backward(saved, cfg, g, need_x, need_w, raw_x_grad, lambda g, gcos, B, N, st: ops.call(
+        "fr_npcface_bwd", g, saved.cos, saved.label, saved.rowv, gcos, B, N, cfg.ld, cfg.Np, cfg.p0, cfg.s, st)())
 
 
 def mv_softmax_forward(x, weight, label, s, mv):
@@ -357,26 +369,21 @@ def mv_softmax_forward(x, weight, label, s, mv):
     column's value, re-weights the hard negatives (c > thr) to w * c + w - 1, and leaves rowv [4, B] (gt, thr, final,
     d final / d gt) for the backward pass.  The cosines are never clamped.  Nothing waits on the host.  A label outside
     [0, N) selects nothing and makes nothing hard in its row.  Returns (logits, saved, cfg) for ``mv_softmax_backward``."""
-    sv, N, Np, ld = _cosine_operands(x, weight, label, norm_x=True, col_weight=True)
+    sv, N, Np, ld, store, logits = _cosine_front(MV_SOFTMAX, x, weight, label)
     B = x.shape[0]
     is_am, p0, p1, w = bool(mv[0]), float(mv[1]), float(mv[2]), float(mv[3])
-    cos = _raw_cosines(sv, N, ld)
     rowv = torch.empty(4, B, device=x.device)  # gt, thr, final, d final / d gt
-    store, logits = _logit_store(sv, N, ld)
-    ops.call("fr_mv_softmax_apply", cos, sv.label, rowv, store, B, N, ld, int(is_am), p0, p1, w, float(s),
+    ops.call("fr_mv_softmax_apply", sv.cos, sv.label, rowv, store, B, N, ld, int(is_am), p0, p1, w, float(s),
              ops.current_stream_ptr())()
-    return logits, sv._replace(cos=cos, rowv=rowv), HeadCfg(MV_SOFTMAX, Np, ld, s=float(s), p0=w)
+    return logits, sv._replace(rowv=rowv), HeadCfg(MV_SOFTMAX, Np, ld, s=float(s), p0=w)
 
 
 def mv_softmax_backward(saved, cfg, g, need_x, need_w, raw_x_grad=False):
     """(gx, gweight) of ``mv_softmax_forward``; gweight is [D, N].  The hard mask and the branch of the label column are
     comparisons and take no gradient; no cosine is masked out (the head never clamps).  ``raw_x_grad``: as in
     ``margin_backward``."""
-    B, N = saved.x.shape[0], saved.inv_w.shape[0]
-    gcos = torch.empty(B, cfg.Np, device=saved.x.device)
-    ops.call("fr_mv_softmax_bwd", g.contiguous().float(), saved.cos, saved.label, saved.rowv, gcos, B, N, cfg.ld, cfg.Np,
-             cfg.p0, cfg.s, ops.current_stream_ptr())()
-    return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, None if raw_x_grad else "normalize", col_weight=True)
+    return _gcos_backward(saved, cfg, g, need_x, need_w, raw_x_grad, lambda g, gcos, B, N, st: ops.call(
+        "fr_mv_softmax_bwd", g, saved.cos, saved.label, saved.rowv, gcos, B, N, cfg.ld, cfg.Np, cfg.p0, cfg.s, st)())
 
 
 def circle_forward(x, weight, label, circle):
@@ -384,46 +391,37 @@ def circle_forward(x, weight, label, circle):
     ``circle`` the head's (O_p, O_n, delta_p, delta_n, gamma).  Element-wise on the clamped cosines: one row kernel, no row
     values, nothing waits on the host.  A label outside [0, N) makes every column of its row a negative.  Returns (logits,
     saved, cfg) for ``circle_backward``."""
-    sv, N, Np, ld = _cosine_operands(x, weight, label, norm_x=True, col_weight=True)
+    sv, N, Np, ld, store, logits = _cosine_front(CIRCLE, x, weight, label)
     o_p, o_n, delta_p, delta_n, gamma = (float(v) for v in circle)
-    cos = _raw_cosines(sv, N, ld)
-    store, logits = _logit_store(sv, N, ld)
-    ops.call("fr_circle_apply", cos, sv.label, store, x.shape[0], N, ld, o_p, o_n, delta_p, delta_n, gamma,
+    ops.call("fr_circle_apply", sv.cos, sv.label, store, x.shape[0], N, ld, o_p, o_n, delta_p, delta_n, gamma,
              ops.current_stream_ptr())()
-    return logits, sv._replace(cos=cos), HeadCfg(CIRCLE, Np, ld, s=gamma, p0=o_p, p1=o_n)
+    return logits, sv, HeadCfg(CIRCLE, Np, ld, s=gamma, p0=o_p, p1=o_n)
 
 
 def circle_backward(saved, cfg, g, need_x, need_w, raw_x_grad=False):
     """(gx, gweight) of ``circle_forward``; gweight is [D, N].  alpha is a constant of the graph (:463-464 detach), so gcos =
     g * gamma * alpha inside the clamp, alpha recomputed from the saved raw cosines.  ``raw_x_grad``: as in
     ``margin_backward``."""
-    B, N = saved.x.shape[0], saved.inv_w.shape[0]
-    gcos = torch.empty(B, cfg.Np, device=saved.x.device)
-    ops.call("fr_circle_bwd", g.contiguous().float(), saved.cos, saved.label, gcos, B, N, cfg.ld, cfg.Np, cfg.p0, cfg.p1,
-             cfg.s, ops.current_stream_ptr())()
-    return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, None if raw_x_grad else "normalize", col_weight=True)
+    return _gcos_backward(saved, cfg, g, need_x, need_w, raw_x_grad, lambda g, gcos, B, N, st: ops.call(
+        "fr_circle_bwd", g, saved.cos, saved.label, gcos, B, N, cfg.ld, cfg.Np, cfg.p0, cfg.p1, cfg.s, st)())
 
 
 def am_softmax_n_forward(x, weight, label, m, s):
     """The FaceX-Zoo AM_Softmax logits (head/metrics.py:380-392) for fp32 device tensors; ``weight`` is [D, N].  It is
     Am_softmax's arithmetic (fr_margin_apply kind 3: s * (label ? clamp(c) - m : clamp(c))) on the cosines of NORMALISED
     embeddings.  Returns (logits, saved, cfg) for ``am_softmax_n_backward``."""
-    sv, N, Np, ld = _cosine_operands(x, weight, label, norm_x=True, col_weight=True)
-    cos = _raw_cosines(sv, N, ld)
-    store, logits = _logit_store(sv, N, ld)
-    ops.call("fr_margin_apply", cos, sv.label, None, store, x.shape[0], N, ld, AM_SOFTMAX, 0, float(m), float(s),
+    sv, N, Np, ld, store, logits = _cosine_front(AM_SOFTMAX_N, x, weight, label)
+    ops.call("fr_margin_apply", sv.cos, sv.label, None, store, x.shape[0], N, ld, AM_SOFTMAX, 0, float(m), float(s),
              ops.current_stream_ptr())()
-    return logits, sv._replace(cos=cos), HeadCfg(AM_SOFTMAX_N, Np, ld, mi=0, p0=float(m), p1=float(s))
+    return logits, sv, HeadCfg(AM_SOFTMAX_N, Np, ld, mi=0, p0=float(m), p1=float(s))
 
 
 def am_softmax_n_backward(saved, cfg, g, need_x, need_w, raw_x_grad=False):
     """(gx, gweight) of ``am_softmax_n_forward``; gweight is [D, N].  Unlike Am_softmax's, gx goes back through the row
     normalisation.  ``raw_x_grad``: as in ``margin_backward``."""
-    B, N = saved.x.shape[0], saved.inv_w.shape[0]
-    gcos = torch.empty(B, cfg.Np, device=saved.x.device)
-    ops.call("fr_margin_apply_bwd", g.contiguous().float(), saved.cos, saved.label, None, gcos, None, B, N, cfg.ld, cfg.Np,
-             AM_SOFTMAX, 0, cfg.p0, cfg.p1, ops.current_stream_ptr())()
-    return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, None if raw_x_grad else "normalize", col_weight=True)
+    return _gcos_backward(saved, cfg, g, need_x, need_w, raw_x_grad, lambda g, gcos, B, N, st: ops.call(
+        "fr_margin_apply_bwd", g, saved.cos, saved.label, None, gcos, None, B, N, cfg.ld, cfg.Np, AM_SOFTMAX, 0, cfg.p0,
+        cfg.p1, st)())
 
 
 def arcneg_thresh32(thresh):
@@ -445,26 +443,21 @@ def arcneg_forward(x, weight, label, s, arc):
     d a / d gt, writes s * a on the label column and s * (t c + t - 1), t = alpha * exp(-(c - a)^2 / sigma), off it, and
     leaves rowv [3, B] (gt, a, d a / d gt) for the backward pass.  The cosines are never clamped.  Nothing waits on the
     host.  A label outside [0, N) leaves its row at s * c.  Returns (logits, saved, cfg) for ``arcneg_backward``."""
-    sv, N, Np, ld = _cosine_operands(x, weight, label, norm_x=True, col_weight=False)
+    sv, N, Np, ld, store, logits = _cosine_front(ARCNEG, x, weight, label)
     B = x.shape[0]
     thresh, margin, mm, alpha, sigma = (float(v) for v in arc)
-    cos = _raw_cosines(sv, N, ld)
     rowv = torch.empty(3, B, device=x.device)  # gt, a, d a / d gt
-    store, logits = _logit_store(sv, N, ld)
-    ops.call("fr_arcneg_apply", cos, sv.label, rowv, store, B, N, ld, arcneg_thresh32(thresh), margin, mm, alpha, sigma,
+    ops.call("fr_arcneg_apply", sv.cos, sv.label, rowv, store, B, N, ld, arcneg_thresh32(thresh), margin, mm, alpha, sigma,
              float(s), ops.current_stream_ptr())()
-    return logits, sv._replace(cos=cos, rowv=rowv), HeadCfg(ARCNEG, Np, ld, s=float(s), p0=alpha, p1=sigma)
+    return logits, sv._replace(rowv=rowv), HeadCfg(ARCNEG, Np, ld, s=float(s), p0=alpha, p1=sigma)
 
 
 def arcneg_backward(saved, cfg, g, need_x, need_w, raw_x_grad=False):
     """(gx, gweight) of ``arcneg_forward``; gweight is [N, D].  t and the branch are constants of the graph (:431-432); t is
     recomputed from the saved raw cosines and the row's a; no cosine is masked out (the head never clamps).
     ``raw_x_grad``: as in ``margin_backward``."""
-    B, N = saved.x.shape[0], saved.inv_w.shape[0]
-    gcos = torch.empty(B, cfg.Np, device=saved.x.device)
-    ops.call("fr_arcneg_bwd", g.contiguous().float(), saved.cos, saved.label, saved.rowv, gcos, B, N, cfg.ld, cfg.Np, cfg.p0,
-             cfg.p1, cfg.s, ops.current_stream_ptr())()
-    return _cosine_backward(saved, cfg.Np, gcos, need_x, need_w, None if raw_x_grad else "normalize", col_weight=False)
+    return _gcos_backward(saved, cfg, g, need_x, need_w, raw_x_grad, lambda g, gcos, B, N, st: ops.call(
+        "fr_arcneg_bwd", g, saved.cos, saved.label, saved.rowv, gcos, B, N, cfg.ld, cfg.Np, cfg.p0, cfg.p1, cfg.s, st)())
 
 
 def _row_pitch(t):
@@ -512,7 +505,7 @@ def softmax_linear_backward(saved, cfg, g, need_x, need_w, raw_x_grad=False):
         ops.call("fr_col_sums", g, B, N, ldg, gb, st)()
     gp = torch.empty(B, cfg.Np, device=dev)  # the pitch both gradient GEMMs read, columns N .. Np zero
     ops.call("fr_pad_cols", g, gp, B, N, ldg, cfg.Np, st)()
-    return _cosine_backward(saved, cfg.Np, gp, need_x, need_w, None, col_weight=False, norm_w=False) + (gb,)
+    return _cosine_backward(saved, cfg, gp, need_x, need_w) + (gb,)
 
 
 class SoftmaxHeadFn(torch.autograd.Function):
@@ -621,16 +614,17 @@ def _check_labels(label, n):
         raise RuntimeError("index %d is out of bounds for dimension 1 with size %d" % (int(label.max()), n))
 
 
-def _head_entry(fn, n, x, weight, label, *args, t=None):
-    """What every head does around its Function: empty batch, label check, the one-float device buffer ``t`` of a head
-    that has one (CurricularFace's ``t``, AdaCos's ``scale``)."""
+def _head_entry(fn, n, x, weight, label, *args, buf=None):
+    """What every head does around its Function: empty batch, label check, the one-float device buffer of a head that has
+    one, ``buf`` = (the head function's name, the buffer's argument name, the tensor): CurricularFace's ``t``, AdaCos's
+    ``scale``."""
     if x.shape[0] == 0:  # the reference returns empty logits (F.linear / scatter_ on zero rows); nothing to launch
         ops.ptr(x)  # host tensors still fail loudly
         return x.new_zeros((0, n), dtype=torch.float32) + 0.0 * (x.sum() + weight.sum())
     _check_labels(label, n)
+    t = None if buf is None else buf[2]
     if t is not None and (t.dtype != torch.float32 or t.numel() != 1 or t.device != x.device or not t.is_contiguous()):
-        raise ValueError("%s: %s must be a contiguous float32 tensor of one element on %s"
-                         % ((("adacos_head", "scale") if fn is AdaCosHeadFn else ("curricular_head", "t")) + (x.device,)))
+        raise ValueError("%s: %s must be a contiguous float32 tensor of one element on %s" % (buf[:2] + (x.device,)))
     return fn.apply(x, weight, label, *args)
 
 
@@ -647,13 +641,14 @@ def margin_ext_head(x, weight, label, kind, mi, p0, p1):
 def curricular_head(x, kernel, label, t, s, m, group=None):
     """CurricularFace logits; the empty batch and label check of ``margin_head``.  ``t`` (float32 [1] on x's device) is
     updated in place; an empty batch leaves it as it is (the reference's mean over no rows turns it into NaN for good)."""
-    return _head_entry(CurricularHeadFn, kernel.shape[1], x, kernel, label, t, s, m, group, t=t)
+    return _head_entry(CurricularHeadFn, kernel.shape[1], x, kernel, label, t, s, m, group,
+                       buf=("curricular_head", "t", t))
 
 
 def adacos_head(x, W, label, scale, group=None):
     """AdaCos logits; the empty batch and label check of ``margin_head``.  ``scale`` (float32 [1] on x's device) is updated
     in place on every call; an empty batch leaves it as it is (the reference divides by zero rows there)."""
-    return _head_entry(AdaCosHeadFn, W.shape[0], x, W, label, scale, group, t=scale)
+    return _head_entry(AdaCosHeadFn, W.shape[0], x, W, label, scale, group, buf=("adacos_head", "scale", scale))
 
 
 def npcface_head(x, kernel, label, s, cos_m, sin_m, m0, m1, t, a):
