@@ -771,6 +771,31 @@ int fr_shard_rank_rows(const float* logits, const float* tlogit, int32_t* rank, 
 int fr_shard_target_cos(const float* cos, const int64_t* label_local, float* tl, int rows, int N, int ld, void* stream);
 int fr_shard_sum_parts(const float* r_part, int nparts, float* r, int rows, void* stream);
 
+/* ---- class sampling for the class-sharded head (Partial-FC, An et al. 2021/22; no counterpart in the reference, whose
+ *      head/metrics.py:104-113 splits the classes and runs all of them): every step a rank runs its head on n_s of the n
+ *      classes of its shard, the classes of the global batch among them.  All integer arithmetic is mod 2^32:
+ *   fmix32(h)  : h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16      (a bijection on uint32)
+ *   key(c)     = fmix32((class0 + c) ^ salt), c = 0 .. n - 1, class0 the shard's first global class; class0 + n <= 2^32, so
+ *                the keys of a shard are distinct and the selection has no ties
+ *   pos[c]     = some row's label_local is c (values outside [0, n), the -1 of rows owned elsewhere among them, mark nothing)
+ *   S          = every positive + the n_s - P non-positive classes with the smallest keys (P positives): |S| = n_s exactly
+ *   idx [n_s]  = S in ascending class order;  inv [n] = position in idx, or -1;
+ *   label_s [rows] = inv[label_local] where 0 <= label_local < n, else -1
+ * 1 <= n_s <= n and n_s >= min(n, rows), so that P <= n_s holds without reading the device.  Writes every element of idx,
+ * inv and label_s and nothing outside them; reads nothing on the host, does not synchronise the stream, allocates nothing.
+ * A three-pass radix descent (11 / 11 / 10 key bits; LDS histograms with integer atomics, added into one histogram per
+ * pass with integer atomics, narrowed by one workgroup) finds the (n_s - P)-th smallest key, a count + ordered-write pair
+ * compacts: integer arithmetic and integer atomics only, whose sums do not depend on their order, so the result is
+ * bit-defined and the same from run to run.  work: fr_class_sample_work(n) uint32 words. */
+int fr_class_sample_work(int n);
+int fr_class_sample(const int64_t* label_local, int rows, int n, int n_s, uint32_t salt, uint32_t class0, int32_t* idx,
+                    int32_t* inv, int64_t* label_s, uint32_t* work, void* stream);
+/* out[j][:] = w[idx[j]][:], j < n_s: the selected rows of a [n][D] fp32 parameter (D = 1: a bias), D >= 1 */
+int fr_gather_rows(const float* w, const int32_t* idx, float* out, int n_s, int D, void* stream);
+/* out[c][:] = inv[c] >= 0 ? g[inv[c]][:] : 0, c < n: the dense [n][D] gradient from the gathered one.  Every element of
+ * out is written exactly once: no memset, no atomics. */
+int fr_scatter_rows(const float* g, const int32_t* inv, float* out, int n, int D, void* stream);
+
 /* ---- GPU-side training-input transform (replaces the per-sample host transform of train.py:108-116
  *      applied in dataset.py:85-88): Resize(Hr x Wr, Pillow 8-bit bilinear, bit-exact) -> crop S x S at crop[b] = (x0, y0)
  *      -> horizontal flip where flip[b] -> ToTensor -> Normalize, for a batch of staged uint8 images.

@@ -23,6 +23,10 @@ def stage3(exp_name, **overrides):
                                          # | CircleLoss | AM_Softmax (the FaceX-Zoo head; not Am_softmax) | ArcNegFace
                                          # | Softmax (the plain linear head with a bias)
         LOSS_NAME="Focal",               # Focal | Softmax (nn.CrossEntropyLoss(): the batch-mean cross entropy, on the HIP path)
+        # optional, read by train.py when present: SHARDED_HEAD=True (the class-sharded head, frhip/sharded_head.py) and
+        # with it SHARDED_HEAD_SAMPLE_RATE in (0, 1], default 1.0: below 1 a training step runs on that fraction of each
+        # rank's classes, the classes of the batch among them, drawn from (SEED, batch counter); ArcFace, CosFace,
+        # SphereFace and Softmax only, and the rate must keep at least min(classes per rank, global batch) classes
         ENCODER_CHECKPOINT=None,
         ENCODER_AVG_IMAGE="<an arbitrary 112x112 image here>",
         ENCODER_INPUT_SIZE=112,

@@ -39,10 +39,22 @@ parameter ``bias`` [N] sharded alike.  The local logits are x_all W_shard^T + bi
 labels play no part in them.  G = g W_shard, reduce-scattered, is gx itself; the gradients of the weight shard and of the
 bias shard (the column sums of g over the global batch, the rows in order) are complete on their owner.
 
+Class sampling (``sample_rate`` < 1; Partial-FC, An et al. 2021/22; the reference has no counterpart): in training mode
+every rank runs the step above on n_s = ceil(sample_rate * shard size) of its classes -- the classes of its shard that occur
+in the global batch, and the non-positive classes with the smallest keys fmix32(global class ^ salt(seed, step)) up to n_s
+(fr_class_sample; ``sample_salt``).  The selected weight rows (and bias entries) are gathered, the labels remapped, and
+everything from the logits to the two gradient GEMMs sees N = n_s; the gradient rows are scattered back into a dense
+gradient of the shard's shape whose other rows are exactly 0.  The optimizer is untouched: an unselected row sees a zero
+gradient, so weight decay and momentum still act on it, as under torch.optim.SGD with Partial-FC v2.  The softmax
+denominator, the loss and prec@1/@5 then run over the selected classes of all ranks; prec@k is an upper estimate (the label
+competes with fewer classes).  Row-sharded heads only (ArcFace, CosFace, SphereFace, Softmax); eval mode runs all classes.
+
 The device arithmetic sits behind ``HipKernels`` (the only implementation in the package: HIP through the C ABI; no
 CPU fallback).  tests/ substitutes an oracle-backed stand-in to run the collective choreography at world_size 2 on
 ``gloo``.
 """
+import math
+
 import torch
 import torch.distributed as dist
 import torch.nn as nn
@@ -78,6 +90,26 @@ def localize_labels(label_all, lo, hi):
     """label - lo where this rank owns the label, -1 elsewhere."""
     own = (label_all >= lo) & (label_all < hi)
     return torch.where(own, label_all - lo, torch.full_like(label_all, -1))
+
+
+def fmix32(h):
+    """The 32-bit finaliser of MurmurHash3, a bijection on uint32 (the key of fr_class_sample)."""
+    h &= 0xFFFFFFFF
+    h ^= h >> 16
+    h = (h * 0x85EBCA6B) & 0xFFFFFFFF
+    h ^= h >> 13
+    h = (h * 0xC2B2AE35) & 0xFFFFFFFF
+    return h ^ (h >> 16)
+
+
+def sample_salt(seed, step):
+    """The salt of training step ``step``: fmix32(seed + 0x9E3779B9 * step) mod 2**32, a host int."""
+    return fmix32((int(seed) + 0x9E3779B9 * int(step)) & 0xFFFFFFFF)
+
+
+def sampled_classes(rate, n):
+    """n_s = ceil(rate * n) of a shard of n classes."""
+    return min(n, max(1, int(math.ceil(rate * n))))
 
 
 class Comm(object):
@@ -213,6 +245,33 @@ class HipKernels(object):
         """(G = g W_shard, gradient of the weight shard, gradient of the bias shard)."""
         return FRF.softmax_linear_backward(saved, cfg, g, need_x, need_w, raw_x_grad=True)
 
+    # class sampling
+    def sample_classes(self, label_local, n, n_s, salt, class0):
+        """(idx [n_s] int32 ascending, inv [n] int32, label_s [rows] int64) of fr_class_sample; nothing is read back."""
+        dev, rows = label_local.device, label_local.shape[0]
+        idx = torch.empty(n_s, device=dev, dtype=torch.int32)
+        inv = torch.empty(n, device=dev, dtype=torch.int32)
+        label_s = torch.empty(rows, device=dev, dtype=torch.int64)
+        work = torch.empty(int(ops.lib.fr_class_sample_work(n)), device=dev, dtype=torch.int32)
+        ops.call("fr_class_sample", label_local.contiguous(), rows, n, n_s, salt, class0, idx, inv, label_s, work,
+                 ops.current_stream_ptr())()
+        return idx, inv, label_s
+
+    def gather_rows(self, w, idx):
+        """w[idx]: the selected rows of a [n, D] parameter, or the selected entries of a [n] bias."""
+        w = w.contiguous()
+        out = torch.empty((idx.shape[0],) + tuple(w.shape[1:]), device=w.device)
+        ops.call("fr_gather_rows", w, idx, out, idx.shape[0], w.shape[1] if w.dim() == 2 else 1,
+                 ops.current_stream_ptr())()
+        return out
+
+    def scatter_rows(self, g, inv, n):
+        """The dense [n, ...] gradient: row c = g[inv[c]] where inv[c] >= 0, else exactly 0."""
+        g = g.contiguous()
+        out = torch.empty((n,) + tuple(g.shape[1:]), device=g.device)
+        ops.call("fr_scatter_rows", g, inv, out, n, g.shape[1] if g.dim() == 2 else 1, ops.current_stream_ptr())()
+        return out
+
     def sum_r(self, r_part):
         """[rows, 1]: the row's parts added in the order fr_normalize_bwd_radial adds them."""
         rows, nparts = r_part.shape
@@ -238,6 +297,14 @@ class ShardedHeadLossFn(torch.autograd.Function):
         lab_all = C.all_gather(label.contiguous().long())
         rows = x_all.shape[0]
         lab_loc = localize_labels(lab_all, head.lo, head.hi)
+        ctx.sample = None
+        if head.step_salt is not None:  # class sampling: from here on the shard is its n_s selected classes
+            n = head.hi - head.lo
+            idx, inv, lab_loc = K.sample_classes(lab_loc, n, head.n_s, head.step_salt, head.lo)
+            w = K.gather_rows(w.detach(), idx)
+            if bias is not None:
+                bias = K.gather_rows(bias.detach(), idx)
+            ctx.sample = (inv, n)
         if head.kind in (FRF.ARCFACE, FRF.COSFACE):
             logits, saved, cfg = K.logits(x_all, w.detach(), lab_loc, head.kind, head.s, head.m, head.easy_margin)
         elif head.kind == FRF.SPHEREFACE:
@@ -274,6 +341,10 @@ class ShardedHeadLossFn(torch.autograd.Function):
                                          ctx.needs_input_grad[1] or ctx.needs_input_grad[4])
         else:
             G_all, gw, r_part = K.ext_bwd(ctx.saved, ctx.cfg, grad, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        if ctx.sample is not None:  # back to the shard's shape: the selected rows, exact zeros elsewhere
+            inv, n = ctx.sample
+            gw = None if gw is None else K.scatter_rows(gw, inv, n)
+            gb = None if gb is None else K.scatter_rows(gb, inv, n)
         gx = None
         if G_all is not None:
             G = C.reduce_scatter_rows(G_all)
@@ -318,11 +389,27 @@ class ShardedMarginLoss(nn.Module):
     what the reference's single head sees under nn.DataParallel).  ``average_over_ranks=True`` (default) scales the
     feature gradient by the world size so that a backbone whose gradients are AVERAGED over ranks
     (frhip.parallel.DataParallel) ends up with the gradient of that global loss.
+
+    ``sample_rate`` in (0, 1] (row-sharded heads: ArcFace, CosFace, SphereFace, Softmax): below 1, a training step runs on
+    n_s = ceil(sample_rate * (hi - lo)) of this rank's classes, every class of the global batch among them, drawn anew each
+    step from (``sample_seed``, ``sample_step``); n_s must be at least min(hi - lo, rows of the global batch).  The
+    gradients keep the shard's shape, with exact zeros in the unselected rows: the optimizer is untouched, so weight decay
+    and momentum still act on those rows, as under torch.optim.SGD with Partial-FC v2.  The softmax denominator, the loss
+    and prec@1 / prec@5 run over the selected classes of all ranks, which makes prec@k an upper estimate.  ``sample_step``
+    is a host int that counts the training forwards; set it to the step counter when a run is resumed.  In eval mode, and
+    at rate 1.0, all classes run on the unsampled path.
     """
 
     def __init__(self, in_features, out_features, head="ArcFace", s=None, m=None, easy_margin=False, gamma=2.0,
-                 group=None, full_weight=None, average_over_ranks=True, kernels=None, loss="Focal", full_bias=None):
+                 group=None, full_weight=None, average_over_ranks=True, kernels=None, loss="Focal", full_bias=None,
+                 sample_rate=1.0, sample_seed=0):
         super().__init__()
+        if not 0.0 < sample_rate <= 1.0:
+            raise ValueError("ShardedMarginLoss: sample_rate must lie in (0, 1], got %r" % (sample_rate,))
+        if sample_rate < 1.0 and CLASS_DIM.get(head) == 1:
+            raise ValueError("ShardedMarginLoss: sample_rate < 1 with head %s: its kernel is [D, N], sharded by columns, and "
+                             "the column gather is not built; class sampling serves ArcFace, CosFace, SphereFace and "
+                             "Softmax" % head)
         if head not in KINDS and head not in LINEAR_KINDS:
             raise ValueError("ShardedMarginLoss: head must be one of %s, got %r"
                              % (", ".join(list(KINDS) + list(LINEAR_KINDS)), head))
@@ -339,6 +426,11 @@ class ShardedMarginLoss(nn.Module):
         self.kernels = kernels if kernels is not None else HipKernels()
         self.lo, self.hi = class_range(out_features, self.comm.world, self.comm.rank)
         self.grad_scale = float(self.comm.world) if average_over_ranks else 1.0
+        # class sampling: n_s of this rank's classes run in a training step; ``sample_step`` counts the training forwards
+        # (a host int: the step of the salt) and ``step_salt`` is the salt of the forward in flight, None when all classes run
+        self.sample_rate, self.sample_seed, self.sample_step = float(sample_rate), int(sample_seed), 0
+        self.n_s = self.hi - self.lo if sample_rate == 1.0 else sampled_classes(self.sample_rate, self.hi - self.lo)
+        self.step_salt = None
         self.full_shape = (out_features, in_features) if self.class_dim == 0 else (in_features, out_features)
         if full_weight is None:  # the draw of the replicated head (head/metrics.py), from the same RNG state
             full_weight = torch.empty(self.full_shape)
@@ -419,6 +511,16 @@ class ShardedMarginLoss(nn.Module):
         if self.kind == FRF.SPHEREFACE:  # head/metrics.py:238-239: every forward call counts
             self.iter += 1
             self.lamb = max(self.LambdaMin, self.base * (1 + self.lambda_gamma * self.iter) ** (-1 * self.power))
+        self.step_salt = None
+        if self.training:
+            n, rows = self.hi - self.lo, input.shape[0] * self.comm.world
+            if self.n_s < n:
+                if self.n_s < min(n, rows):  # every class of the batch must fit: P <= n_s without reading the device
+                    raise ValueError("ShardedMarginLoss: sample_rate %g keeps %d of this rank's %d classes, fewer than the "
+                                     "%d a global batch of %d rows can hold; the smallest admissible rate here is %g"
+                                     % (self.sample_rate, self.n_s, n, min(n, rows), rows, min(n, rows) / float(n)))
+                self.step_salt = sample_salt(self.sample_seed, self.sample_step)
+            self.sample_step += 1
         return ShardedHeadLossFn.apply(input, self.weight, label, self, getattr(self, "bias", None))
 
     def __repr__(self):

@@ -146,6 +146,11 @@ NOT_SHARDED_ROW_VALUE = {
 }
 
 
+# Sharded heads that class sampling (SHARDED_HEAD_SAMPLE_RATE < 1) does not serve, and why.
+_COLUMN_SHARDED = "its kernel is [D, N], sharded by columns, and the column gather of class sampling is not built"
+SAMPLED_NOT_SERVED = {"Am_softmax": _COLUMN_SHARDED, "CurricularFace": _COLUMN_SHARDED}
+
+
 def check_head_config(cfg):
     """Refuse, before anything is built, a combination the driver does not serve."""
     name = cfg["HEAD_NAME"]
@@ -153,6 +158,16 @@ def check_head_config(cfg):
     if cfg.get("SHARDED_HEAD", False) and why is not None:
         raise NotImplementedError("SHARDED_HEAD=True with HEAD_NAME '%s': the class-sharded head does not serve %s (%s); run "
                                   "it replicated, SHARDED_HEAD=False" % (name, name, why))
+    rate = cfg.get("SHARDED_HEAD_SAMPLE_RATE", 1.0)
+    if rate != 1.0:  # class sampling (frhip/sharded_head.py): an option of the class-sharded, row-sharded heads
+        if not 0.0 < rate < 1.0:
+            raise ValueError("SHARDED_HEAD_SAMPLE_RATE must lie in (0, 1], got %r" % (rate,))
+        if not cfg.get("SHARDED_HEAD", False):
+            raise NotImplementedError("SHARDED_HEAD_SAMPLE_RATE=%r needs SHARDED_HEAD=True: classes are sampled by the "
+                                      "class-sharded head only" % (rate,))
+        if name in SAMPLED_NOT_SERVED:
+            raise NotImplementedError("SHARDED_HEAD_SAMPLE_RATE=%r with HEAD_NAME '%s': %s; run it with "
+                                      "SHARDED_HEAD_SAMPLE_RATE=1.0" % (rate, name, SAMPLED_NOT_SERVED[name]))
 
 
 def main():
@@ -273,7 +288,9 @@ def main():
             raise NotImplementedError("SHARDED_HEAD needs LOSS_NAME 'Focal'")
         from frhip.sharded_head import ShardedMarginLoss
         crit = ShardedMarginLoss.from_head(head, gamma=loss_fn.gamma if loss_fn is not None else 2.0,
-                                           loss=cfg["LOSS_NAME"]).to(device)  # takes the resumed weight and t along
+                                           loss=cfg["LOSS_NAME"],  # takes the resumed weight and t along
+                                           sample_rate=cfg.get("SHARDED_HEAD_SAMPLE_RATE", 1.0),
+                                           sample_seed=cfg["SEED"]).to(device)
         optimizer = make_optimizer(list(crit.parameters()))  # the weight shard; the Softmax head's bias shard behind it
     # exposes .module like nn.DataParallel; all-reduce only when world > 1 (a weight shard is complete on its owner)
     BACKBONE = DataParallel(backbone, None if crit is not None else head)
@@ -311,6 +328,8 @@ def main():
             n = state["numpy_rng"]
             np.random.set_state((n[0], np.asarray(n[1], dtype=np.uint32), n[2], n[3], n[4]))
         print("Resuming at epoch {} batch {}".format(start_epoch, batch))
+    if crit is not None:
+        crit.sample_step = batch  # class sampling draws from (SEED, batch counter): a resumed run redraws the same sets
 
     disp_freq = max(1, len(loader) // 10)  # the reference divides by zero below 10 batches/epoch
     lts = cfg.get("LIMIT_TRAIN_SAMPLES", None)
