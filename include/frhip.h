@@ -214,6 +214,22 @@ int fr_conv_wgrad_strip_supported(int Cout, int Cin, int W);
  * of slab[g*n + i] in the library's fixed order (chunks of 16 slabs, csrc/slab_sum.h; n % 4 == 0, groups <= 256): the
  * sum a deferring launch left to its caller. */
 int fr_conv_wgrad_strip_defers(const FrWgradArgs* args);
+/* Host queries on the family's instance table (select_wgrad, csrc/conv_wgrad_strip.hip): pure arithmetic, no HIP call.
+ * fr_conv_wgrad_strip_groups: the strip groups (nsplit) for a launch that may use `wgs` workgroups -- the work items of
+ * the shape's strip geometry, capped at wgs / dW tiles, at least 1; 0: the family does not serve the problem.  Ignores
+ * args->nsplit and args->slab.  fr_conv_wgrad_strip_kernel: which kernel fr_conv_wgrad_strip would launch for exactly
+ * these arguments (nsplit included) under the current switches, one of the ids below; FR_WGRAD_NONE also where the entry
+ * rejects ldg / lda / slab / nsplit.  It does not look at prev_*, which do not choose the kernel. */
+enum {
+  FR_WGRAD_NONE = 0,      /* not served */
+  FR_WGRAD_STRIP = 1,     /* conv_wgrad_strip_kernel, stride 1 */
+  FR_WGRAD_STRIP_S2 = 2,  /* conv_wgrad_strip_kernel on the four parity planes, stride 2 */
+  FR_WGRAD_ROLL = 3,      /* conv_wgrad_roll_kernel (warp-specialised; 7x7, 14x14, 28x28) */
+  FR_WGRAD_VR = 4,        /* conv_wgrad_vr_kernel (warp-specialised; 56x56, 112x112) */
+  FR_WGRAD_S2ROLL = 5     /* conv_wgrad_s2roll_kernel (warp-specialised, stride 2) */
+};
+int fr_conv_wgrad_strip_groups(const FrWgradArgs* args, int wgs);
+int fr_conv_wgrad_strip_kernel(const FrWgradArgs* args);
 int fr_reduce_slabs(const float* slab, int groups, long long n, float* out, void* stream);
 
 /* ---- stem: NCHW fp32 images (+ optional constant avg image, restyle_psp.py:445-447) -> im2col rows
@@ -888,8 +904,9 @@ int fr_fill_rows(float* out, const float* bias, long long rows, int C, void* str
  * the same question per kernel family instead, because the answer doubles as the launch geometry the caller must size
  * buffers for: fr_conv3x3_strip_parts / fr_conv3x3_s2_strip_parts return the number of partial-sum rows a launch will
  * write (0 = shape not served: the caller uses fr_conv_igemm, which serves every shape), fr_conv_wgrad_strip_supported
- * answers yes / no.  Every entry point additionally returns < 0 for an unsupported argument (text in
- * fr_last_error_string()), never silently computing something else. */
+ * answers yes / no, fr_conv_wgrad_strip_groups returns the strip groups to launch with (0 = shape not served: the caller
+ * uses fr_conv_wgrad) and fr_conv_wgrad_strip_kernel names the kernel a launch reaches.  Every entry point additionally
+ * returns < 0 for an unsupported argument (text in fr_last_error_string()), never silently computing something else. */
 int fr_abi_version(void);
 /* Run-time switches (kernel-family A/B switches, test hooks; README "Switches"): an int per name, first read from the
  * environment variable of that name, then cached for the life of the process.  fr_set_option overrides the cached value

@@ -91,6 +91,7 @@ FrBnFinArgs = structs["FrBnFinArgs"]
 FR_F32, FR_BF16 = 0, 1
 PRO_NONE, PRO_BN, PRO_PRELU, PRO_RESBN, PRO_RESBN_SE = 0, 1, 2, 4, 5
 EPI_STORE, EPI_STATS, EPI_PRELU_BWD, EPI_BNBWD, EPI_MARGIN, EPI_ATOMIC, EPI_SLAB, EPI_BIAS_RES, EPI_STATS_X = range(9)
+WGRAD_NONE, WGRAD_STRIP, WGRAD_STRIP_S2, WGRAD_ROLL, WGRAD_VR, WGRAD_S2ROLL = range(6)  # fr_conv_wgrad_strip_kernel
 
 
 class FrhipError(RuntimeError):

@@ -1061,25 +1061,6 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_s2roll_kernel(const FrWgrad
              cit * CT + wci * 16 + ln.li);
 }
 
-template <int W>
-int launch_roll(const FrWgradArgs& a, hipStream_t st) {
-  return fr_by_pro(a.pro, [&](auto pro) {
-    return fr_launch_slab_kernel<conv_wgrad_roll_kernel<W, decltype(pro)::value>>(a, st, 512, RL<W>::LDS);
-  });
-}
-template <int W>
-int launch_vr(const FrWgradArgs& a, hipStream_t st) {
-  return fr_by_pro(a.pro, [&](auto pro) {
-    return fr_launch_slab_kernel<conv_wgrad_vr_kernel<W, decltype(pro)::value>>(a, st, 512, VC<W>::LDS);
-  });
-}
-template <int WL>
-int launch_s2(const FrWgradArgs& a, hipStream_t st) {
-  return fr_by_pro(a.pro, [&](auto pro) {
-    return fr_launch_slab_kernel<conv_wgrad_s2roll_kernel<WL, decltype(pro)::value>>(a, st, 512, SL2<WL>::LDS);
-  });
-}
-
 }  // namespace
 
 #ifdef FRHIP_STAMPS
@@ -1095,47 +1076,33 @@ bool fr_wgrad_roll_enabled() {
   return *on != 0;
 }
 
-// stride-1 3x3 at 7x7 / 14x14 / 28x28 / 56x56 / 112x112, channel counts multiples of 64, at least one image (14x14) / phase (28x28) per group
-bool fr_wgrad_roll_serves(const FrWgradArgs& a) {
-  if (!(fr_wgrad_roll_enabled() && a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.GH == a.SH &&
-        a.GW == a.SW && a.SH == a.SW && a.Cout % CT == 0 && a.SC % CT == 0 && a.nsplit >= 1))
-    return false;
-  if (a.SW == 14) return a.nsplit <= a.B;
-  if (a.SW == 28) return a.nsplit <= a.B * RC<28>::NPH;
-  if (a.SW == 7) return a.nsplit <= a.B;
-  if (a.SW == 56 || a.SW == 112) return a.nsplit <= a.B * (a.SW + 2);
-  return false;
+// Lines of select_wgrad (conv_wgrad_strip.hip), named <kernel id, gradient width>.  The limit: a group takes at least one
+// image (two-phase schedule), phase or virtual row.
+template <int KERNEL, int W>
+int fr_wgrad_ws_limit(int B) {
+  if constexpr (KERNEL == FR_WGRAD_ROLL) return B * (RC<W>::NPH == 2 ? 1 : RC<W>::NPH);
+  else if constexpr (KERNEL == FR_WGRAD_VR) return B * VC<W>::VH;
+  else return B * SC2<W>::NPH;
 }
-
-// stride-2 3x3 with a 28 / 14 / 7 wide gradient, channel counts multiples of 64, at least one phase per group
-bool fr_wgrad_s2roll_serves(const FrWgradArgs& a) {
-  if (!(fr_wgrad_roll_enabled() && a.KH == 3 && a.KW == 3 && a.stride == 2 && a.pad == 1 && a.GH == a.GW &&
-        a.SH == 2 * a.GH && a.SW == 2 * a.GW && a.Cout % CT == 0 && a.SC % CT == 0 && a.nsplit >= 1))
-    return false;
-  if (a.GW == 56) return a.nsplit <= a.B * SC2<56>::NPH;
-  if (a.GW == 28) return a.nsplit <= a.B * SC2<28>::NPH;
-  if (a.GW == 14) return a.nsplit <= a.B * SC2<14>::NPH;
-  if (a.GW == 7) return a.nsplit <= a.B * SC2<7>::NPH;
-  return false;
+template <int KERNEL, int W>
+int fr_wgrad_ws_launch(const FrWgradArgs& a, hipStream_t st) {
+  return fr_by_pro(a.pro, [&](auto pro) {
+    constexpr int PRO = decltype(pro)::value;
+    if constexpr (KERNEL == FR_WGRAD_ROLL) return fr_launch_slab_kernel<conv_wgrad_roll_kernel<W, PRO>>(a, st, 512, RL<W>::LDS);
+    else if constexpr (KERNEL == FR_WGRAD_VR) return fr_launch_slab_kernel<conv_wgrad_vr_kernel<W, PRO>>(a, st, 512, VC<W>::LDS);
+    else return fr_launch_slab_kernel<conv_wgrad_s2roll_kernel<W, PRO>>(a, st, 512, SL2<W>::LDS);
+  });
 }
-
-int fr_wgrad_s2roll_launch(const FrWgradArgs& a, hipStream_t st) {
-  switch (a.GW) {
-    case 56: return launch_s2<56>(a, st);
-    case 28: return launch_s2<28>(a, st);
-    case 14: return launch_s2<14>(a, st);
-    case 7: return launch_s2<7>(a, st);
-  }
-  FR_UNSUPPORTED("fr_conv_wgrad_strip: stride-2 width not served by the warp-specialised kernel");
-}
-
-int fr_wgrad_roll_launch(const FrWgradArgs& a, hipStream_t st) {
-  switch (a.SW) {
-    case 7: return launch_roll<7>(a, st);
-    case 14: return launch_roll<14>(a, st);
-    case 28: return launch_roll<28>(a, st);
-    case 56: return launch_vr<56>(a, st);
-    case 112: return launch_vr<112>(a, st);
-  }
-  FR_UNSUPPORTED("fr_conv_wgrad_strip: width not served by the warp-specialised kernel");
-}
+// the instances this file compiles (a line of select_wgrad that this list lacks does not link)
+#define FR_WGRAD_WS_INSTANCE(KERNEL, W)           \
+  template int fr_wgrad_ws_limit<KERNEL, W>(int); \
+  template int fr_wgrad_ws_launch<KERNEL, W>(const FrWgradArgs&, hipStream_t);
+FR_WGRAD_WS_INSTANCE(FR_WGRAD_ROLL, 7)
+FR_WGRAD_WS_INSTANCE(FR_WGRAD_ROLL, 14)
+FR_WGRAD_WS_INSTANCE(FR_WGRAD_ROLL, 28)
+FR_WGRAD_WS_INSTANCE(FR_WGRAD_VR, 56)
+FR_WGRAD_WS_INSTANCE(FR_WGRAD_VR, 112)
+FR_WGRAD_WS_INSTANCE(FR_WGRAD_S2ROLL, 56)
+FR_WGRAD_WS_INSTANCE(FR_WGRAD_S2ROLL, 28)
+FR_WGRAD_WS_INSTANCE(FR_WGRAD_S2ROLL, 14)
+FR_WGRAD_WS_INSTANCE(FR_WGRAD_S2ROLL, 7)

@@ -394,22 +394,72 @@ int by_pro(const FrWgradArgs& a, hipStream_t st) {
   });
 }
 
+// One line of the table: the strip kernel with ROWS-row strips of NIMG images (S2: of the gradient, on the four parity planes
+// of the input -- see WC), and the warp-specialised kernel KERNEL of conv_wgrad_roll.hip that takes the launch while
+// FRHIP_WGRAD_ROLL is on and every group gets a unit of its work.  `fills` is the strip geometry's either way.
+// 4-wave strip workgroups (two resident per CU, NW = 4) were measured at about half the throughput of the 8-wave form
+// with register prefetch (tools/kbench.py, B = 256) and are not instantiated.
+template <int KERNEL, int W, int ROWS, int NIMG, bool S2 = false, bool RK = false>
+FrWgradInstance line(const FrWgradArgs& a) {
+  constexpr int NS = WC<W, ROWS, NIMG, 8, S2, RK>::NS;
+  const int fills = S2 ? (a.B * NS + NIMG - 1) / NIMG : a.B * NS / NIMG;
+  if (fr_wgrad_roll_enabled() && a.nsplit >= 1 && a.nsplit <= fr_wgrad_ws_limit<KERNEL, W>(a.B))
+    return {fills, KERNEL, fr_wgrad_ws_launch<KERNEL, W>};
+  return {fills, S2 ? FR_WGRAD_STRIP_S2 : FR_WGRAD_STRIP, by_pro<W, ROWS, NIMG, 8, S2, RK>};
+}
+
+// The family's only shape predicate and its only table: square 3x3, pad 1, stride 1 (GH == SH) or 2 (SH == 2 GH), channel
+// counts multiples of CT, gradient width on a line below.  FR_WGRAD_NONE: not served (fills -1: a stride-2 width off the table).
+FrWgradInstance select_wgrad(const FrWgradArgs& a) {
+  const bool s1 = a.stride == 1 && a.SH == a.GH, s2 = a.stride == 2 && a.SH == 2 * a.GH;
+  if (a.KH != 3 || a.KW != 3 || a.pad != 1 || a.GH != a.GW || a.SH != a.SW || !(s1 || s2) || a.Cout % CT || a.SC % CT)
+    return {0, FR_WGRAD_NONE, nullptr};
+  if (s1) switch (a.GW) {
+      case 112: return line<FR_WGRAD_VR, 112, 2, 1>(a);
+      case 56: return line<FR_WGRAD_VR, 56, 4, 1>(a);
+      // 28x28 / 14x14: the row-aligned K layout (round 2; its A/B switch left in round 5)
+      case 28: return line<FR_WGRAD_ROLL, 28, 7, 1, false, true>(a);
+      case 14: return line<FR_WGRAD_ROLL, 14, 14, 1, false, true>(a);
+      case 7: return line<FR_WGRAD_ROLL, 7, 7, 4>(a);
+      default: return {0, FR_WGRAD_NONE, nullptr};
+    }
+  switch (a.GW) {  // stride 2
+    case 56: return line<FR_WGRAD_S2ROLL, 56, 2, 1, true>(a);
+    case 28: return line<FR_WGRAD_S2ROLL, 28, 4, 1, true>(a);
+    case 14: return line<FR_WGRAD_S2ROLL, 14, 7, 1, true>(a);
+    case 7: return line<FR_WGRAD_S2ROLL, 7, 7, 2, true>(a);
+  }
+  return {-1, FR_WGRAD_NONE, nullptr};
+}
+
+bool bad_launch_args(const FrWgradArgs& a) { return a.ldg % 8 || a.lda % 8 || !a.slab || a.nsplit < 1; }
+
 }  // namespace
 
-// 1 when (W) is in the strip table and the channel counts are multiples of 64
+// 1 when (W) is on a stride-1 line of the table and the channel counts are multiples of 64
 extern "C" int fr_conv_wgrad_strip_supported(int Cout, int Cin, int W) {
-  if (Cout % CT || Cin % CT) return 0;
-  return W == 112 || W == 56 || W == 28 || W == 14 || W == 7;
+  FrWgradArgs a = {};
+  a.B = a.stride = a.pad = a.nsplit = 1, a.KH = a.KW = 3, a.GH = a.GW = a.SH = a.SW = W, a.Cout = Cout, a.SC = Cin;
+  return select_wgrad(a).kernel != FR_WGRAD_NONE;
 }
 
 // every shape fr_conv_wgrad_strip serves honours defer / prev_*
 extern "C" int fr_conv_wgrad_strip_defers(const FrWgradArgs* args) {
-  const FrWgradArgs& a = *args;
-  if (a.ldg % 8 || a.lda % 8 || !a.slab || a.nsplit < 1 || a.nsplit > 256 || a.KH != 3 || a.KW != 3 || a.pad != 1 ||
-      a.Cout % CT || a.SC % CT)
-    return 0;
-  if (a.stride == 2) return a.GH == a.GW && a.SH == 2 * a.GH && a.SW == 2 * a.GW && (a.GW == 56 || a.GW == 28 || a.GW == 14 || a.GW == 7);
-  return a.stride == 1 && a.GH == a.SH && a.GW == a.SW && a.SH == a.SW && fr_conv_wgrad_strip_supported(a.Cout, a.SC, a.SW);
+  return !bad_launch_args(*args) && args->nsplit <= 256 && select_wgrad(*args).kernel != FR_WGRAD_NONE;
+}
+
+extern "C" int fr_conv_wgrad_strip_groups(const FrWgradArgs* args, int wgs) {
+  const FrWgradInstance inst = select_wgrad(*args);
+  const int tiles = (args->Cout / CT) * (args->SC / CT);
+  if (inst.kernel == FR_WGRAD_NONE || tiles < 1) return 0;  // (no channels: nothing to launch)
+  const int cap = tiles <= wgs ? wgs / tiles : 1;
+  const int groups = inst.fills < cap ? inst.fills : cap;
+  return groups > 1 ? groups : 1;
+}
+
+// (the prev_* fields are not looked at: they do not choose the kernel)
+extern "C" int fr_conv_wgrad_strip_kernel(const FrWgradArgs* args) {
+  return bad_launch_args(*args) ? FR_WGRAD_NONE : select_wgrad(*args).kernel;
 }
 
 extern "C" int fr_reduce_slabs(const float* slab, int groups, long long n, float* out, void* stream) {
@@ -419,36 +469,13 @@ extern "C" int fr_reduce_slabs(const float* slab, int groups, long long n, float
 
 extern "C" int fr_conv_wgrad_strip(const FrWgradArgs* args, void* stream) {
   const FrWgradArgs& a = *args;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (a.ldg % 8 || a.lda % 8 || !a.slab || a.nsplit < 1) FR_UNSUPPORTED("fr_conv_wgrad_strip: bad strides / slab");
+  if (bad_launch_args(a)) FR_UNSUPPORTED("fr_conv_wgrad_strip: bad strides / slab");
   if (a.prev_n && (!a.prev_slab || !a.prev_dw || a.prev_groups < 1 || a.prev_groups > 256 || a.prev_n % 4 ||
                    a.prev_slab == a.slab))
     FR_UNSUPPORTED("fr_conv_wgrad_strip: bad prev_* (deferred slab sum)");
-  if (a.KH == 3 && a.KW == 3 && a.stride == 2 && a.pad == 1 && a.GH == a.GW && a.SH == 2 * a.GH && a.SW == 2 * a.GW &&
-      a.Cout % CT == 0 && a.SC % CT == 0) {
-    if (fr_wgrad_s2roll_serves(a)) return fr_wgrad_s2roll_launch(a, st);
-    // stride 2: the input tile holds the four parity planes of the strip (see WC)
-    switch (a.GW) {
-      case 56: return by_pro<56, 2, 1, 8, true>(a, st);
-      case 28: return by_pro<28, 4, 1, 8, true>(a, st);
-      case 14: return by_pro<14, 7, 1, 8, true>(a, st);
-      case 7: return by_pro<7, 7, 2, 8, true>(a, st);
-    }
-    FR_UNSUPPORTED("fr_conv_wgrad_strip: stride-2 width not in the strip table");
-  }
-  if (a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.GH != a.SH || a.GW != a.SW || a.SH != a.SW ||
-      !fr_conv_wgrad_strip_supported(a.Cout, a.SC, a.SW))
-    FR_UNSUPPORTED("fr_conv_wgrad_strip: square 3x3 bf16 convolutions, stride 1 or 2, 64-multiple channels");
-  if (fr_wgrad_roll_serves(a)) return fr_wgrad_roll_launch(a, st);
-  // 4-wave workgroups (two resident per CU, NW = 4) were measured at about half the throughput of the 8-wave form
-  // with register prefetch (tools/kbench.py, B = 256) and are not instantiated.
-  switch (a.SW) {
-    case 112: return by_pro<112, 2, 1, 8>(a, st);
-    case 56: return by_pro<56, 4, 1, 8>(a, st);
-    // 28x28 / 14x14: the row-aligned K layout (round 2; its A/B switch left in round 5)
-    case 28: return by_pro<28, 7, 1, 8, false, true>(a, st);
-    case 14: return by_pro<14, 14, 1, 8, false, true>(a, st);
-    case 7: return by_pro<7, 7, 4, 8>(a, st);
-  }
-  FR_UNSUPPORTED("fr_conv_wgrad_strip: width not in the strip table");
+  const FrWgradInstance inst = select_wgrad(a);
+  if (inst.kernel == FR_WGRAD_NONE)
+    FR_UNSUPPORTED(inst.fills < 0 ? "fr_conv_wgrad_strip: stride-2 width not in the strip table"
+                                  : "fr_conv_wgrad_strip: square 3x3 bf16 convolutions, stride 1 or 2, 64-multiple channels");
+  return inst.launch(a, reinterpret_cast<hipStream_t>(stream));
 }

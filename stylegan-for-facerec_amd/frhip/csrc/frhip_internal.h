@@ -43,14 +43,21 @@ int fr_s2roll_parts(int B);
 int fr_s2roll_launch(const FrConvArgs& a, hipStream_t st);
 bool fr_s2roll_enabled();
 
-// 3x3 stride-1 weight gradients at 7x7 ... 112x112 on the warp-specialised kernels (conv_wgrad_roll.hip); dispatched from
-// fr_conv_wgrad_strip
+// What the table of the 3x3 weight-gradient family (select_wgrad, conv_wgrad_strip.hip) answers for a problem: the host
+// queries report these fields and fr_conv_wgrad_strip calls `launch`, so the two cannot disagree.
+struct FrWgradInstance {
+  int fills;   // work items of the line's strip geometry: what fr_conv_wgrad_strip_groups caps the group count at
+  int kernel;  // FR_WGRAD_*; FR_WGRAD_NONE: the family does not serve the problem
+  int (*launch)(const FrWgradArgs&, hipStream_t);
+};
+// The warp-specialised kernels (conv_wgrad_roll.hip) as lines of select_wgrad: KERNEL = FR_WGRAD_ROLL / _VR / _S2ROLL at
+// gradient width W.  fr_wgrad_ws_limit: the most groups (nsplit) a launch over B images takes -- one image, phase or
+// virtual row each.  Instantiated in conv_wgrad_roll.hip for the widths each kernel has.
 bool fr_wgrad_roll_enabled();
-bool fr_wgrad_roll_serves(const FrWgradArgs& a);
-int fr_wgrad_roll_launch(const FrWgradArgs& a, hipStream_t st);
-// ... and the stride-2 ones with a 56 / 28 / 14 / 7 wide gradient (conv_wgrad_s2roll_kernel, same file)
-bool fr_wgrad_s2roll_serves(const FrWgradArgs& a);
-int fr_wgrad_s2roll_launch(const FrWgradArgs& a, hipStream_t st);
+template <int KERNEL, int W>
+int fr_wgrad_ws_limit(int B);
+template <int KERNEL, int W>
+int fr_wgrad_ws_launch(const FrWgradArgs& a, hipStream_t st);
 
 // stride-2 3x3 forward at 128 / 256 / 512 channels on the warp-specialised kernel (conv3x3_s2_ws.hip); a line of
 // select_s2.  fr_s2ws_strips: partial-sum rows of a served (B, C, low-res width), 0 = not served.

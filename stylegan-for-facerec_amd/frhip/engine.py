@@ -573,26 +573,17 @@ class BackbonePlan(object):
             L.append(_EvWait(self.stream2_t, ev))
 
     def _wgrad(self, L, param=None, **kw):
-        """Append a weight-gradient launch: LDS-strip kernel for bf16 stride-1 3x3 layers, generic otherwise.  Returns the
-        parameters whose gradients are final once this launch has run (a deferring launch completes its predecessor's)."""
-        if (self.fr == FR_BF16 and self.use_strip and kw["KH"] == 3 and kw["stride"] == 1 and
-                ops.wgrad_strip_supported(kw["Cout"], kw["SC"], kw["SW"])):
-            tiles = (kw["Cout"] // 64) * (kw["SC"] // 64)
-            rows = {112: 2, 56: 4, 28: 7, 14: 14, 7: 7}[kw["SW"]]
-            fills = kw["B"] * (kw["SW"] // rows) // (4 if kw["SW"] == 7 else 1)
-            groups = int(max(1, min(fills, _WGRAD_WGS // tiles if tiles <= _WGRAD_WGS else 1)))
-            return self._slab_launch(L, dict(kw, nsplit=groups), groups * kw["Cout"] * 9 * kw["SC"], param=param)
-        if (self.fr == FR_BF16 and self.use_strip and kw["KH"] == 3 and kw["stride"] == 2 and
-                kw["GW"] in (56, 28, 14, 7) and kw["SW"] == 2 * kw["GW"] and kw["Cout"] % 64 == 0 and kw["SC"] % 64 == 0):
-            # stride-2 layers: the same kernel on the four parity planes of the input (conv_wgrad_strip.hip, S2)
-            tiles = (kw["Cout"] // 64) * (kw["SC"] // 64)
-            rows, nimg = {56: (2, 1), 28: (4, 1), 14: (7, 1), 7: (7, 2)}[kw["GW"]]
-            fills = (kw["B"] * (kw["GW"] // rows) + nimg - 1) // nimg
-            groups = int(max(1, min(fills, _WGRAD_WGS // tiles if tiles <= _WGRAD_WGS else 1)))
-            return self._slab_launch(L, dict(kw, nsplit=groups), groups * kw["Cout"] * 9 * kw["SC"], param=param)
+        """Append a weight-gradient launch: the 3x3 strip family (fr_conv_wgrad_strip) where its table serves the bf16
+        layer, generic otherwise.  Returns the parameters whose gradients are final once this launch has run (a
+        deferring launch completes its predecessor's)."""
+        if self.fr == FR_BF16 and self.use_strip:
+            probe = ops.wgrad_args(**kw)
+            groups = ops.wgrad_strip_groups(probe, _WGRAD_WGS)  # 0: not a shape of the family
+            if groups:
+                return self._slab_launch(L, dict(kw, nsplit=groups), groups * kw["Cout"] * 9 * kw["SC"], probe=probe,
+                                         param=param)
         if kw.get("nsplit", 1) > 1:  # pixel slices go to slabs and are added in a fixed order (no float atomics)
-            return self._slab_launch(L, kw, kw["nsplit"] * kw["Cout"] * kw["KH"] * kw["KW"] * kw["SC"], strip=False,
-                                     param=param)
+            return self._slab_launch(L, kw, kw["nsplit"] * kw["Cout"] * kw["KH"] * kw["KW"] * kw["SC"], param=param)
         l = ops.wgrad(self.stream2, self.fr, **kw)
         l.tstream = self.stream2_t
         L.append(l)
@@ -623,17 +614,18 @@ class BackbonePlan(object):
         L.append(r)
         return param
 
-    def _slab_launch(self, L, kw, need, strip=True, param=None):
-        """Append a slab-mode weight-gradient launch.  Returns the parameters whose gradients THIS launch completes:
+    def _slab_launch(self, L, kw, need, probe=None, param=None):
+        """Append a slab-mode weight-gradient launch: of the strip family when ``probe`` holds the arguments _wgrad asked
+        its group count with, generic otherwise.  Returns the parameters whose gradients THIS launch completes:
         [param] for a launch that sums its own slabs, the previous deferring launch's parameter for one that folds it,
         [] for the first deferring launch."""
         done = []
+        strip = probe is not None
         if strip:
-            probe = ops._fill(_lib.FrWgradArgs(), **dict(kw, slab=self.part))
-            if _lib.lib.fr_conv_wgrad_strip_defers(ctypes.byref(probe)):
-                which = self._slab_flip
+            which = self._slab_flip
+            buf, users = self._slab_buffer(which, need)
+            if ops.wgrad_strip_defers(ops._fill(probe, nsplit=kw["nsplit"], slab=buf)):  # the slabs it would write
                 self._slab_flip ^= 1
-                buf, users = self._slab_buffer(which, need)
                 kw = dict(kw, slab=buf, defer=1)
                 if self._pending is not None:
                     _l0, pg, pn, pdw, pparam, pwhich = self._pending

@@ -13,7 +13,8 @@ from . import _lib
 from ._lib import (EPI_ATOMIC, EPI_BIAS_RES, EPI_BNBWD, EPI_MARGIN, EPI_PRELU_BWD, EPI_SLAB, EPI_STATS, EPI_STATS_X, EPI_STORE,  # noqa: F401
                    FR_BF16,
                    FR_F32,
-                   PRO_BN, PRO_NONE, PRO_PRELU, PRO_RESBN, PRO_RESBN_SE, lib)
+                   PRO_BN, PRO_NONE, PRO_PRELU, PRO_RESBN, PRO_RESBN_SE,
+                   WGRAD_NONE, WGRAD_ROLL, WGRAD_S2ROLL, WGRAD_STRIP, WGRAD_STRIP_S2, WGRAD_VR, lib)
 
 TORCH_DTYPE = {FR_F32: torch.float32, FR_BF16: torch.bfloat16}
 
@@ -145,6 +146,25 @@ def wgrad_strip(stream, **kw):
 
 def wgrad_strip_supported(cout, cin, w):
     return bool(lib.fr_conv_wgrad_strip_supported(int(cout), int(cin), int(w)))
+
+
+def wgrad_args(**kw):
+    """FrWgradArgs from its fields (tensors allowed for pointer fields): what the host queries below are asked with."""
+    return _fill(_lib.FrWgradArgs(), **kw)
+
+
+def wgrad_strip_groups(args, wgs):
+    """Strip groups (nsplit) of a fr_conv_wgrad_strip launch that may use ``wgs`` workgroups; 0: shape not served."""
+    return int(lib.fr_conv_wgrad_strip_groups(ctypes.byref(args), int(wgs)))
+
+
+def wgrad_strip_defers(args):
+    return bool(lib.fr_conv_wgrad_strip_defers(ctypes.byref(args)))
+
+
+def wgrad_strip_kernel(args):
+    """WGRAD_* id of the kernel fr_conv_wgrad_strip would launch for exactly these arguments (WGRAD_NONE: none)."""
+    return int(lib.fr_conv_wgrad_strip_kernel(ctypes.byref(args)))
 
 
 def bn_apply(stream, dtype, **kw):

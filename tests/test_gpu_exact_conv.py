@@ -414,7 +414,7 @@ def _wgrad_reference(K, x, g, pa, pb, pro, stride, what):
     return dw
 
 
-def _wgrad_strip(K, cout, cin, W, B, pro, groups, stride, seed, pads=(0, 0)):
+def _wgrad_strip(K, cout, cin, W, B, pro, groups, stride, seed, pads=(0, 0), kernel=None):
     what = "wgrad %d_%d_%d_%s_b%d_g%d_s%d" % (cout, cin, W, pro, B, groups, stride)
     x, g, pa, pb = _wgrad_operands(seed, cout, cin, W, B, pro, stride)
     ref = _wgrad_reference(K, x, g, pa, pb, pro, stride, what)
@@ -425,6 +425,8 @@ def _wgrad_strip(K, cout, cin, W, B, pro, groups, stride, seed, pads=(0, 0)):
     run = K.wgrad_strip(K.current_stream_ptr(), g=X.padded(g.to("cuda", BF), ldg), src=X.padded(x.to("cuda", BF), lda), dw=dw.t,
                         slab=slab.t, B=B, GH=Wo, GW=Wo, Cout=cout, SH=W, SW=W, SC=cin, KH=3, KW=3, stride=stride, pad=1,
                         ldg=ldg, lda=lda, pro=X.PRO[pro], nsplit=groups, pro_a=pa.cuda(), pro_b=pb.cuda())
+    if kernel is not None:
+        assert K.wgrad_strip_kernel(run.keep[0]) == kernel, what + ": fr_conv_wgrad_strip_kernel"
     run()
     torch.cuda.synchronize()
     dw.assert_guards(what + " dW")
@@ -449,6 +451,21 @@ def test_wgrad_strip(K, cout, cin, W, pro, B, groups):
 def test_wgrad_strip_stride2(K, C, WL, groups):
     """fr_conv_wgrad_strip on the stride-2 layers (parity planes; the stride-2 rolling kernel), PReLU prologue."""
     _wgrad_strip(K, C, C, 2 * WL, 3, "prelu", groups, 2, 167, pads=(8, 16) if groups == 3 else (0, 0))
+
+
+# (stride, gradient width, B, groups, kernel): the group count AT each warp-specialised line's limit -- one image (7x7,
+# 14x14), phase (28x28: 7 per image; stride 2: 1 at 7x7, 4 at 14x14) per group -- and one past it at the stride-2 7x7 line,
+# where the launch goes to the strip kernel instead
+WGS_LIMIT_CASES = [(1, 7, 2, 2, "WGRAD_ROLL"), (1, 14, 2, 2, "WGRAD_ROLL"), (1, 28, 2, 14, "WGRAD_ROLL"),
+                   (2, 7, 3, 3, "WGRAD_S2ROLL"), (2, 14, 3, 12, "WGRAD_S2ROLL"), (2, 7, 3, 4, "WGRAD_STRIP_S2")]
+
+
+@pytest.mark.parametrize("stride,WG,B,groups,kernel", WGS_LIMIT_CASES, ids=["s%d_%d_b%d_g%d_%s" % s for s in WGS_LIMIT_CASES])
+def test_wgrad_strip_at_the_group_limits_of_the_table(K, stride, WG, B, groups, kernel):
+    """The smallest launches at which a limit of select_wgrad can be off by one (64 channels): the instance
+    fr_conv_wgrad_strip_kernel names for the arguments is the expected one, and every dW element is exact."""
+    assert K.lib.fr_get_option(b"FRHIP_WGRAD_ROLL", 1) == 1
+    _wgrad_strip(K, 64, 64, WG * stride, B, "prelu", groups, stride, 173, kernel=getattr(K, kernel))
 
 
 def test_wgrad_deferred_slab_chain(K):

@@ -475,6 +475,18 @@ def test_dispatch_geometry_of_the_strip_tables():
     ws = L.fr_conv_wgrad_strip_supported
     assert all(ws(c, c, w) == 1 for c, w in ((64, 112), (64, 56), (128, 28), (256, 14), (512, 7)))
     assert ws(96, 64, 56) == 0 and ws(64, 64, 20) == 0
+    # strip groups of the B = 256 step: at 256 workgroups the "bench" group counts of WGS_CASES (tests/test_gpu_kernels.py,
+    # min(fills, 256 / tiles)), at the engine's 128 workgroups (_WGRAD_WGS) half of them
+    import dispatch_sweep as S
+
+    def wg(c, w, stride=1, wgs=128, B=256):
+        return L.fr_conv_wgrad_strip_groups(ctypes.byref(S.wgrad_args(_lib.FrWgradArgs, B, c, c, w, stride)), wgs)
+    assert wg(256, 14, wgs=256) == 16 and wg(512, 7, wgs=256) == 4 and wg(128, 28, wgs=256) == 64
+    assert wg(64, 56) == 128 and wg(64, 112) == 128                   # one dW tile: as many groups as workgroups
+    assert wg(256, 14) == 8 and wg(512, 7) == 2 and wg(128, 28) == 32
+    assert wg(64, 56, wgs=256) == 256 and wg(512, 7, B=3) == 1        # 7x7: four images per fill, none whole at B = 3
+    assert wg(64, 56, stride=2) == 128 and wg(512, 7, stride=2, wgs=256) == 4 and wg(512, 7, stride=2, wgs=256, B=3) == 2  # pairs
+    assert wg(96, 14) == 0 and wg(64, 20) == 0 and wg(64, 112, stride=2) == 0                              # not served
 
 
 def test_dispatch_queries_answer_as_recorded(golden_dir):
@@ -503,6 +515,54 @@ def test_dispatch_queries_answer_as_recorded(golden_dir):
                     k = int(bad[0])
                     pytest.fail("%s%r under %r answers %d, recorded %d (first of %d differences)"
                                 % (query, S.arguments(query, k), setting, int(got[k]), int(want[k]), len(bad)))
+
+
+def test_wgrad_dispatch_queries_answer_as_recorded(golden_dir):
+    """The host queries of the 3x3 weight-gradient family (fr_conv_wgrad_strip_groups at 128 and 256 workgroups,
+    _supported, _defers, fr_conv_wgrad_strip_kernel at 1, 8, 128 and 256 groups), swept over every batch 1 .. 520, the
+    channel counts and widths of tests/dispatch_sweep.py (served and unserved) and both strides, with FRHIP_WGRAD_ROLL on
+    and off: the answers equal, exactly, what the predicates, switch statements and engine arithmetic answered BEFORE they
+    were folded into select_wgrad (tests/golden/make_golden_dispatch.py says how that was recorded).  A different group
+    count is a different step; a different kernel id is a launch that silently fell to the slower kernel."""
+    import dispatch_sweep as S
+    from frhip import _lib
+    with np.load(os.path.join(golden_dir, "g26_wgrad_dispatch.npz")) as z:
+        gold = {k: z[k] for k in z.files}
+    index = json.loads(gold["index"].tobytes().decode())
+    assert len(index) == 2 * len(S.WGRAD_QUERIES) == 16
+    with S.Switches(_lib.lib, S.WGRAD_SWITCHES) as sw:
+        for setting in S.wgrad_settings():
+            sw.set(setting)
+            for query, got in S.wgrad_answers(_lib.lib, _lib.FrWgradArgs).items():
+                name = index[S.wgrad_key(setting, query)]
+                want = np.repeat(gold["v_" + name], gold["c_" + name])
+                assert got.shape == want.shape, (query, got.shape, want.shape)
+                bad = np.flatnonzero(got != want)
+                if len(bad):
+                    k = int(bad[0])
+                    pytest.fail("%s at (B, Cout, Cin, W, stride) = %r under %r answers %d, recorded %d (first of %d "
+                                "differences)" % (query, S.wgrad_arguments(k), setting, int(got[k]), int(want[k]), len(bad)))
+
+
+def test_wgrad_strip_entry_rejects_off_table_shapes_without_a_gpu():
+    """fr_conv_wgrad_strip answers from select_wgrad before any launch: the error texts of the shapes it does not serve, and
+    the group query on a problem without channels (no dW tile to divide the workgroups by)."""
+    import dispatch_sweep as S
+    from frhip import _lib
+    L = _lib.lib
+
+    def err(B, c, w, stride, **kw):
+        a = S.wgrad_args(_lib.FrWgradArgs, B, c, c, w, stride)
+        for k, v in kw.items():
+            setattr(a, k, v)
+        assert L.fr_conv_wgrad_strip(ctypes.byref(a), None) < 0
+        return L.fr_last_error_string()
+    assert err(2, 64, 20, 2) == b"fr_conv_wgrad_strip: stride-2 width not in the strip table"
+    assert err(2, 64, 20, 1).startswith(b"fr_conv_wgrad_strip: square 3x3 bf16 convolutions")
+    assert err(2, 96, 14, 2).startswith(b"fr_conv_wgrad_strip: square 3x3 bf16 convolutions")
+    assert err(2, 64, 14, 1, nsplit=0) == b"fr_conv_wgrad_strip: bad strides / slab"
+    a = S.wgrad_args(_lib.FrWgradArgs, 2, 0, 64, 14, 1)
+    assert L.fr_conv_wgrad_strip_groups(ctypes.byref(a), 128) == 0
 
 
 def test_configs_select_the_compute_dtype():

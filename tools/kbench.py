@@ -123,14 +123,7 @@ def wgrad_case(kind, cout, cin, W, B, stride=1, pro=1, iters=20):
     TOUCH[:] = [g, x]
     flops = 2.0 * B * Ho * Ho * cout * cin * 9
     if kind == "wgs":
-        tiles = (cout // 64) * (cin // 64)
-        if stride == 2:  # the engine's group count (engine.py _wgrad)
-            rows, nimg = {56: (2, 1), 28: (4, 1), 14: (7, 1), 7: (7, 2)}[Ho]
-            fills = (B * (Ho // rows) + nimg - 1) // nimg
-        else:
-            rows = {112: 2, 56: 4, 28: 7, 14: 14, 7: 7}[W]
-            fills = B * (W // rows) // (4 if W == 7 else 1)
-        groups = max(1, min(fills, 256 // tiles))
+        groups = ops.wgrad_strip_groups(ops.wgrad_args(**kw), 256)  # the table's group count at 256 workgroups
         slab = torch.empty(groups * cout * 9 * cin, device="cuda")
         l = ops.wgrad_strip(st, nsplit=groups, slab=slab, **kw)
     else:
