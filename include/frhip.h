@@ -725,10 +725,15 @@ int fr_arcneg_bwd(const float* g, const float* cos, const int64_t* label, const 
                   int ld, int ldg, float alpha, float sigma, float s, void* stream);
 
 /* ---- focal loss on the batch-mean cross entropy (loss/focal.py:17-21) + top-k (util/utils.py:343-358) */
-/* per row: lse[m], ce[m] = lse - z[label], rank[m] = #{n: z[n] > z[label]} */
+/* per row of logits [rows][ld] (columns N..ld are not read): lse[m]; ce[m] = lse - z[label], formed as log(S) - (z[label] -
+ * max) with S = sum exp(z - max) added in double for it (lse itself is max + logf of the fp32 sum), so that a confident
+ * row (ce of 1e-3 under logits of 64) keeps a relative error of a few 1e-7; rank[m] = #{n < N: !(z[n] <= z[label])}: on finite data the columns strictly above the label (a tie
+ * does not count against it); a NaN column counts as above it (torch.topk's order), and a NaN label logit or a label outside
+ * [0, N) gives rank N, never a hit.  The ce of a label outside [0, N) is lse, bit for bit.  rows > 0, ld >= N > 0 and every
+ * pointer are required (FR_UNSUPPORTED before any launch), as for the entries below down to fr_focal_bwd. */
 int fr_ce_rows(const float* logits, const int64_t* label, float* lse, float* ce, int32_t* rank, int rows, int N,
                int ld, void* stream);
-/* rank[m] only (accuracy on arbitrary logits, util/utils.py:343-358) */
+/* rank[m] only, by the same rule (accuracy on arbitrary logits, util/utils.py:343-358) */
 int fr_rank_rows(const float* logits, const int64_t* label, int32_t* rank, int rows, int N, int ld, void* stream);
 /* out[j] = scale * #{m < rows: rank[m] < k_j}, j < nk <= 4: precision@k in percent with scale = 100 / rows rounded to float,
  * the value correct_k.mul_(100.0 / batch_size) of util/utils.py:343-358 gives (counts are exact in fp32) */
@@ -884,8 +889,11 @@ int fr_sgd_step(const FrSgdTensor* table_dev, const int32_t* chunks_dev, int nch
  *      'Adam' branch, train.py:197-198), same table / chunk scheme as fr_sgd_step:
  *   m += (g - m) * w1 ; v = v * beta2 + (w2 * g) * g ; p += (-step_size * m) / (sqrt(v) / bc2_sqrt + eps)
  * with the scalars torch derives in double precision on the host and rounds to float: w1 = 1 - beta1, w2 = 1 - beta2,
- * step_size = lr / (1 - beta1^step), bc2_sqrt = sqrt(1 - beta2^step).  Operation order = ATen's CPU kernels (lerp,
- * addcmul, addcdiv), so the update matches torch.optim.Adam to the last bits. */
+ * step_size = lr / (1 - beta1^step), bc2_sqrt = sqrt(1 - beta2^step).  Operation order = ATen's kernels (lerp, mul +
+ * addcmul, sqrt / bc2_sqrt + eps, addcdiv), every operation rounded to fp32 on its own (no FMA contraction, correctly
+ * rounded sqrt and division): bit for bit the np.float32 restatement of tests/loss_optim_ref.py.  torch's own kernels fuse
+ * the multiply-adds of lerp and addcmul, so they agree with this to the last bit or two, not bit for bit.
+ * nchunks <= 0 launches nothing and returns 0 (fr_sgd_step alike); with nchunks > 0 both tables are required. */
 typedef struct FrAdamTensor {
   float* p;
   const float* g;

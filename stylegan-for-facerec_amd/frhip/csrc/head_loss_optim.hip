@@ -915,34 +915,59 @@ __global__ __launch_bounds__(256) void circle_bwd_kernel(const float* __restrict
 }
 
 // ------------------------------------------------------------------------------------------ cross entropy rows
+// The label's rank, shared by ce_rows_kernel, rank_rows_kernel and shard_rank_rows_kernel: a column counts unless it is
+// <= the label's logit.  On finite data that is z[n] > z[label] (a tie does not count against the label).  A NaN counts as
+// above the label wherever it stands, as torch.topk orders it, and a NaN label logit is below every column: rank N.  A
+// label outside [0, N) is given a NaN logit, so its row is never a hit (the reference's pred.eq(target) finds no match).
+__device__ __forceinline__ int ranks_above(float v, float zl) { return !(v <= zl) ? 1 : 0; }
+
+// ce = lse - z[label] as log(S) - (z[label] - mx): with a confident label (z[label] = mx, or near it) the second term is
+// exact or small and ce keeps the relative error of log(S); (mx + logf(S)) - z[label] rounds the sum to an ulp of mx
+// first, which is an absolute error of 2e-6 at mx = 64 on a ce of 1e-3 (profiles/ce_rows_error.txt).  There S = 1 + ce, so
+// an ulp of S is a relative error of 1e-7 / ce in ce: for ce, S is added a second time in double in a fixed order (thread t
+// adds its columns t, t + 256, .. in ascending order, the xor butterfly, the four waves in order; the fp32 sum carries the 1
+// of the leading column through nine roundings), and log(S) = logf(Sf) + (S - Sf) / S takes the rounding of S to fp32 back
+// out.  lse = mx + logf(the fp32 sum) keeps the bits it always had: focal_bwd_kernel forms the gradient from it, and a
+// training run in bf16 amplifies a changed last bit of a gradient within tens of steps.  A label outside [0, N): ce = lse.
 __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ z, const long long* __restrict__ label,
                                                       float* __restrict__ lse, float* __restrict__ ce,
                                                       int* __restrict__ rank, int N, int ld) {
   __shared__ float sred[4];
+  __shared__ double dred[4];
   __shared__ int ired[4];
   const int m = blockIdx.x, tid = threadIdx.x;
   const float* row = z + (size_t)m * ld;
   const long long lab = label[m];
-  const float zl = (lab >= 0 && lab < N) ? row[lab] : 0.f;
+  const bool has = lab >= 0 && lab < N;
+  const float zl = has ? row[lab] : __builtin_nanf("");
   float mx = -INFINITY;
   int cnt = 0;
   for (int n = tid; n < N; n += 256) {
     const float v = row[n];
     mx = fmaxf(mx, v);
-    cnt += v > zl ? 1 : 0;
+    cnt += ranks_above(v, zl);
   }
   block_put(sred, wave_max(mx));
   mx = waves_max4(sred);
   __syncthreads();
   float se = 0.f;
-  for (int n = tid; n < N; n += 256) se += __expf(row[n] - mx);
+  double sd = 0.0;
+  for (int n = tid; n < N; n += 256) {
+    const float e = __expf(row[n] - mx);
+    se += e;
+    sd += (double)e;
+  }
   se = wave_sum(se);
+  sd = wave_sum_d(sd);
   float fc = wave_sum((float)cnt);
-  block_put(sred, se, ired, (int)fc);
+  block_put(sred, se, dred, sd, ired, (int)fc);
   if (tid == 0) {
     const float l = mx + logf(waves_sum<4>(sred));
+    const double S = waves_sum<4>(dred);
+    const float Sf = (float)S;
+    const float ls = logf(Sf) + (float)((S - (double)Sf) / S);
     lse[m] = l;
-    ce[m] = l - zl;
+    ce[m] = has ? ls - (zl - mx) : l;
     rank[m] = waves_sum<4>(ired);
   }
 }
@@ -1070,9 +1095,9 @@ __global__ __launch_bounds__(256) void rank_rows_kernel(const float* __restrict_
   const int m = blockIdx.x, tid = threadIdx.x;
   const float* row = z + (size_t)m * ld;
   const long long lab = label[m];
-  const float zl = (lab >= 0 && lab < N) ? row[lab] : INFINITY;
+  const float zl = (lab >= 0 && lab < N) ? row[lab] : __builtin_nanf("");
   int cnt = 0;
-  for (int n = tid; n < N; n += 256) cnt += row[n] > zl ? 1 : 0;
+  for (int n = tid; n < N; n += 256) cnt += ranks_above(row[n], zl);
   block_put(ired, (int)wave_sum((float)cnt));
   if (tid == 0) rank[m] = waves_sum<4>(ired);
 }
@@ -1134,13 +1159,13 @@ __global__ void shard_combine_kernel(const float* __restrict__ stats_all, int wo
     sum += s[rows + m] * expf(s[m] - gmax);
     t += s[2 * rows + m];  // exactly one rank owns the label, the others contribute 0
   }
-  const float l = gmax + logf(sum);
-  lse[m] = l;
-  ce[m] = l - t;
+  const float ls = logf(sum);
+  lse[m] = gmax + ls;
+  ce[m] = ls - (t - gmax);  // the order of ce_rows_kernel, on the fp32 sums the ranks sent (no double residual of S here)
   tlogit[m] = t;
 }
 
-// rank[m] = #{n in this shard: z[m][n] > t[m]}; the ranks' counts add up to the global rank of the label
+// rank[m] = #{n in this shard: !(z[m][n] <= t[m])} (ranks_above); the ranks' counts add up to the global rank of the label
 __global__ __launch_bounds__(256) void shard_rank_rows_kernel(const float* __restrict__ z, const float* __restrict__ t,
                                                               int* __restrict__ rank, int N, int ld) {
   __shared__ int ired[4];
@@ -1148,7 +1173,7 @@ __global__ __launch_bounds__(256) void shard_rank_rows_kernel(const float* __res
   const float* row = z + (size_t)m * ld;
   const float zl = t[m];
   int cnt = 0;
-  for (int n = tid; n < N; n += 256) cnt += row[n] > zl ? 1 : 0;
+  for (int n = tid; n < N; n += 256) cnt += ranks_above(row[n], zl);
   block_put(ired, (int)wave_sum((float)cnt));
   if (tid == 0) rank[m] = waves_sum<4>(ired);
 }
@@ -1172,11 +1197,15 @@ __global__ __launch_bounds__(256) void sgd_kernel(const FrSgdTensor* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------ Adam
-// Operation order of torch.optim.Adam's single-tensor path (lerp, mul + addcmul, sqrt / sqrt(bc2) + eps, addcdiv); the
-// explicit _rn intrinsics keep the compiler from contracting them into different roundings.
+// Operation order of torch.optim.Adam's single-tensor path (lerp, mul + addcmul, sqrt / sqrt(bc2) + eps, addcdiv), every
+// operation rounded to fp32 on its own.  Plain operators under "fp contract(off)", and sqrtf: without
+// OCML_BASIC_ROUNDED_OPERATIONS the __fmul_rn / __fadd_rn of the HIP headers are plain operators that the compiler may
+// still contract into an FMA, and __fsqrt_rn is the native square root, which is not correctly rounded (it was 1 ulp off in
+// about 1 element of 100; tests/test_gpu_loss_optim.py holds the kernel to the np.float32 restatement bit for bit).
 __global__ __launch_bounds__(256) void adam_kernel(const FrAdamTensor* __restrict__ table,
                                                    const int2* __restrict__ chunks, float step_size, float w1,
                                                    float beta2, float w2, float eps, float bc2_sqrt) {
+#pragma clang fp contract(off)
   const int2 ch = chunks[blockIdx.x];
   const FrAdamTensor t = table[ch.x];
   const long long base = (long long)ch.y * SGD_CHUNK;
@@ -1184,13 +1213,13 @@ __global__ __launch_bounds__(256) void adam_kernel(const FrAdamTensor* __restric
   if (end > t.n) end = t.n;
   const float neg_step = -step_size;
   for (long long i = base + threadIdx.x; i < end; i += 256) {
-    const float g = t.g[i];
-    const float m = __fadd_rn(t.m[i], __fmul_rn(w1, __fsub_rn(g, t.m[i])));
-    const float v = __fadd_rn(__fmul_rn(t.v[i], beta2), __fmul_rn(__fmul_rn(w2, g), g));
+    const float g = t.g[i], m0 = t.m[i];
+    const float m = m0 + w1 * (g - m0);
+    const float v = t.v[i] * beta2 + (w2 * g) * g;
     t.m[i] = m;
     t.v[i] = v;
-    const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), bc2_sqrt), eps);
-    t.p[i] = __fadd_rn(t.p[i], __fdiv_rn(__fmul_rn(neg_step, m), denom));  // addcdiv: self + (value * t1) / t2
+    const float denom = sqrtf(v) / bc2_sqrt + eps;
+    t.p[i] = t.p[i] + (neg_step * m) / denom;  // addcdiv: self + (value * t1) / t2
   }
 }
 
@@ -1445,6 +1474,8 @@ extern "C" int fr_circle_bwd(const float* g, const float* cos, const int64_t* la
 
 extern "C" int fr_ce_rows(const float* logits, const int64_t* label, float* lse, float* ce, int32_t* rank, int rows,
                           int N, int ld, void* stream) {
+  if (rows <= 0 || N <= 0 || ld < N) FR_UNSUPPORTED("fr_ce_rows: shape (rows > 0, ld >= N > 0)");
+  if (!logits || !label || !lse || !ce || !rank) FR_UNSUPPORTED("fr_ce_rows: logits, label, lse, ce and rank are required");
   hipLaunchKernelGGL(ce_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, (const long long*)label,
                      lse, ce, rank, N, ld);
   FR_LAUNCH_CHECK();
@@ -1452,6 +1483,8 @@ extern "C" int fr_ce_rows(const float* logits, const int64_t* label, float* lse,
 
 extern "C" int fr_rank_rows(const float* logits, const int64_t* label, int32_t* rank, int rows, int N, int ld,
                             void* stream) {
+  if (rows <= 0 || N <= 0 || ld < N) FR_UNSUPPORTED("fr_rank_rows: shape (rows > 0, ld >= N > 0)");
+  if (!logits || !label || !rank) FR_UNSUPPORTED("fr_rank_rows: logits, label and rank are required");
   hipLaunchKernelGGL(rank_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits,
                      (const long long*)label, rank, N, ld);
   FR_LAUNCH_CHECK();
@@ -1467,6 +1500,7 @@ extern "C" int fr_topk_precision(const int32_t* rank, int rows, int nk, int k0, 
 
 extern "C" int fr_focal_finalize(const float* ce, const int32_t* rank, int rows, float gamma, float* scalars,
                                  void* stream) {
+  if (rows <= 0 || !ce || !rank || !scalars) FR_UNSUPPORTED("fr_focal_finalize: ce, rank, scalars and rows > 0 are required");
   hipLaunchKernelGGL(focal_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, ce, rank, rows, gamma,
                      scalars);
   FR_LAUNCH_CHECK();
@@ -1474,6 +1508,9 @@ extern "C" int fr_focal_finalize(const float* ce, const int32_t* rank, int rows,
 
 extern "C" int fr_focal_bwd(const float* logits, const int64_t* label, const float* lse, const float* scalars,
                             const float* gup, float* grad, int rows, int N, int ld, void* stream) {
+  if (rows <= 0 || N <= 0 || ld < N) FR_UNSUPPORTED("fr_focal_bwd: shape (rows > 0, ld >= N > 0)");
+  if (!logits || !label || !lse || !scalars || !gup || !grad)
+    FR_UNSUPPORTED("fr_focal_bwd: logits, label, lse, scalars, gup and grad are required");
   dim3 grid((N + 1023) / 1024, rows);
   hipLaunchKernelGGL(focal_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, logits, (const long long*)label,
                      lse, scalars, gup, grad, rows, N, ld);
@@ -1554,6 +1591,7 @@ extern "C" int fr_shard_sum_parts(const float* r_part, int nparts, float* r, int
 extern "C" int fr_adam_step(const FrAdamTensor* table_dev, const int32_t* chunks_dev, int nchunks, float step_size,
                             float w1, float beta2, float w2, float eps, float bc2_sqrt, void* stream) {
   if (nchunks <= 0) return 0;
+  if (!table_dev || !chunks_dev) FR_UNSUPPORTED("fr_adam_step: table_dev and chunks_dev are required when nchunks > 0");
   hipLaunchKernelGGL(adam_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, table_dev, (const int2*)chunks_dev,
                      step_size, w1, beta2, w2, eps, bc2_sqrt);
   FR_LAUNCH_CHECK();
@@ -1564,6 +1602,7 @@ extern "C" int fr_sgd_chunk_elems(void) { return SGD_CHUNK; }
 extern "C" int fr_sgd_step(const FrSgdTensor* table_dev, const int32_t* chunks_dev, int nchunks, float lr,
                            float momentum, void* stream) {
   if (nchunks <= 0) return 0;
+  if (!table_dev || !chunks_dev) FR_UNSUPPORTED("fr_sgd_step: table_dev and chunks_dev are required when nchunks > 0");
   hipLaunchKernelGGL(sgd_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, table_dev,
                      (const int2*)chunks_dev, lr, momentum);
   FR_LAUNCH_CHECK();

@@ -779,7 +779,8 @@ def topk_precision(rank, topk):
 
 
 def topk_ranks(logits, target):
-    """rank[m] = number of classes scoring strictly above the label's logit (device int32 [B])."""
+    """rank[m] = number of classes n with not (z[m][n] <= z[m][label]) (device int32 [B]): those scoring strictly above the
+    label's logit, every NaN, and all N of them when the label's logit is NaN or the label lies outside [0, N)."""
     B, N = logits.shape
     if B == 0:
         ops.ptr(logits)

@@ -107,7 +107,9 @@ def accuracy(output, target, topk=(1,)):
 
     The reference sorts with ``topk`` over all N classes; here one HIP pass counts, per row, the classes that
     score strictly above the label (its rank) and precision@k = mean(rank < k) -- identical unless two logits
-    tie exactly at the k-th place.
+    tie exactly at the k-th place.  A NaN logit counts as above the label (``topk`` puts it first), and a row
+    whose label logit is NaN or whose target lies outside [0, N) has rank N: a miss at every k, as the
+    reference's ``pred.eq(target)`` counts it.
     """
     from frhip import functional as FRF
     rank = FRF.topk_ranks(output, target)
