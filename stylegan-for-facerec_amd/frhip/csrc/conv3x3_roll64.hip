@@ -21,6 +21,8 @@
 //     workgroup (256-512 per launch instead of 14 336).
 //
 // Same contracts as fr_conv3x3_strip (prologues, epilogues, flip = mirrored taps for the data gradient).
+// Shared with the other 3x3 kernels: the epilogue cells (conv_epilogue.h), pro8, the segment picker fr_pick_nseg and the
+// prologue switch fr_by_pro (frhip_internal.h), the launch fr_launch_lds (common.h).
 #include <stdlib.h>
 
 #include <type_traits>
@@ -87,9 +89,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_roll64_kernel(const FrConvArgs
   // per-channel coefficients live in LDS: [pro_a | pro_b | epi_a | epi_b] x 64
   float* const coef = reinterpret_cast<float*>(smem + K::PRO_OFF);
   if (tid < K::C) {
-    coef[tid] = PRO != FR_PRO_NONE ? p.pro_a[tid] : 0.f;
-    coef[K::C + tid] = PRO == FR_PRO_BN ? p.pro_b[tid] : 0.f;
-    coef[2 * K::C + tid] = AUX ? p.epi_a[tid] : 0.f;
+    fr_roll_stage_coef<PRO, AUX>(coef, p, tid);
     coef[3 * K::C + tid] = (AUX && fr_epi_uses_b(epi)) ? p.epi_b[tid] : 0.f;
   }
   __syncthreads();
@@ -421,32 +421,18 @@ __global__ __launch_bounds__(512, 2) void conv3x3_roll64_kernel(const FrConvArgs
 
 int roll_nseg(int B, int W) {
   // row segments per (image, band): enough workgroups for one per CU on 256 CUs; H / 4 iterations must divide evenly
-  const int bands = W / R64::BW;
   static const int cand[4] = {1, 2, 7, 14};
   static const int* forced = fr_option_slot("FRHIP_ROLL_NSEG", -1);  // test hook: walks of whole images at small batches
-  for (int k = 0; k < 4; ++k) {
-    if (*forced == cand[k]) return cand[k];
-  }
-  for (int k = 0; k < 4; ++k) {
-    if ((long long)B * bands * cand[k] >= 256) return cand[k];
-  }
-  return 14;
+  return fr_pick_nseg(cand, 4, *forced, (long long)B * (W / R64::BW));
 }
 
 template <int W, int PRO, bool AUX>
 int launch(const FrConvArgs& a, hipStream_t st) {
-  static unsigned long long attr_done = 0;  // one bit per device
-  if (fr_attr_needed(attr_done)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_roll64_kernel<W, PRO, AUX>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, R64::LDS);
-    fr_attr_done(attr_done);
-  }
   const int nseg = roll_nseg(a.B, W);
   const int items = a.B * (W / R64::BW) * nseg;
   // one workgroup per CU (156 KB of LDS), persistent over its items: weights and coefficients are staged once
   const int grid = items < 256 ? items : 256;
-  FR_LAUNCH_KERNEL((conv3x3_roll64_kernel<W, PRO, AUX>), dim3(grid), dim3(R64::NTH), R64::LDS, st, a, nseg, items);
-  FR_LAUNCH_CHECK();
+  return fr_launch_lds<&conv3x3_roll64_kernel<W, PRO, AUX>>(grid, R64::NTH, R64::LDS, st, a, nseg, items);
 }
 
 template <int W>
@@ -461,12 +447,8 @@ int by_pro(const FrConvArgs& a, hipStream_t st) {
     if (a.pro != FR_PRO_PRELU || !a.aux || !a.epi_a || !a.epi_b) FR_UNSUPPORTED("rolling-window convolution: the folded epilogue needs the PReLU prologue, aux, epi_a and epi_b");
     return launch<W, FR_PRO_PRELU, true>(a, st);
   }
-  switch (a.pro) {
-    case FR_PRO_NONE: return launch<W, FR_PRO_NONE, false>(a, st);
-    case FR_PRO_BN: return launch<W, FR_PRO_BN, false>(a, st);
-    case FR_PRO_PRELU: return launch<W, FR_PRO_PRELU, false>(a, st);
-  }
-  FR_UNSUPPORTED("rolling-window convolution: prologue / epilogue combination not served");
+  return fr_by_pro(a.pro, [&](auto pro) { return launch<W, decltype(pro)::value, false>(a, st); },
+                   "rolling-window convolution: prologue / epilogue combination not served");
 }
 
 }  // namespace

@@ -19,12 +19,16 @@
 //
 // Same contracts as fr_conv3x3_s2_strip for the combinations served: forward with any prologue and the STORE / STATS
 // epilogues; gradient (mode 2, all four classes) with the PReLU-backward epilogue.  Everything else stays on the strip kernel.
+// Shared with the other 3x3 kernels: the gradient's tap table (conv_taps.h: FrTaps<1, P>; the forward's plane-split columns
+// are this file's), the epilogue cells (conv_epilogue.h), pro8, fr_keep16, pin, static_for, the segment picker fr_pick_nseg
+// and the prologue switch fr_by_pro (frhip_internal.h), the launch fr_launch_lds (common.h).
 #include <stdlib.h>
 
 #include <type_traits>
 
 #include "common.h"
 #include "conv_epilogue.h"
+#include "conv_taps.h"
 #include "frhip_internal.h"
 
 namespace {
@@ -58,52 +62,27 @@ struct S2R {
 
 // One (K step, M tile) of a computing wave's iteration, in execution order.
 //   forward: 2 channel chunks x 9 taps x 2 tiles.  roff = kernel row (ring row 2r + kh - 1), coff = kernel column.
-//   gradient: classes P = 2 ph + pw in turn, each 2 chunks x its taps x 2 tiles.  dx row 2i + ph collects g rows i + 1 (kh = 0)
-//   and i (kh = 2) for ph = 1, g row i (kh = 1) for ph = 0 (columns alike): roff / coff = 0 / 1 ring row / column offsets.
+//   gradient: classes P = 2 ph + pw in turn, each 2 chunks x its taps x 2 tiles, the taps of FrTaps<1, P> (conv_taps.h):
+//   roff / coff = 0 / 1 ring row / column offsets.
 struct Step {
   int cls, ktap, roff, coff, chunk, i, last;
 };
 constexpr int cls_off(int P) { return P == 0 ? 0 : (P == 1 ? 4 : (P == 2 ? 12 : (P == 3 ? 20 : 36))); }
+template <int P>
+constexpr Step grad_step(int l) {  // step l of class P
+  using T = FrTaps<1, P>;
+  const int t = (l / 2) % T::NT;
+  return {P, T::ktap(t), T::roff(t), T::coff(t), l / (T::NT * 2), l & 1, l == T::NT * 4 - 1};
+}
 template <int KIND>
 constexpr Step step_of(int s) {
-  Step r{};
   if (KIND == 0) {
     const int tap = (s % 18) / 2;
-    r.cls = 0;
-    r.chunk = s / 18;
-    r.i = s & 1;
-    r.ktap = tap;
-    r.roff = tap / 3;
-    r.coff = tap % 3;
-    r.last = s == 35;
-    return r;
+    return {0, tap, tap / 3, tap % 3, s / 18, s & 1, s == 35};
   }
   const int P = s < 4 ? 0 : (s < 12 ? 1 : (s < 20 ? 2 : 3));
   const int l = s - cls_off(P);
-  const int PH = P >> 1, PW = P & 1, NWD = PW ? 2 : 1, NT = (PH ? 2 : 1) * NWD;
-  const int t = (l / 2) % NT;
-  const int kh = PH ? 2 * (t / NWD) : 1, kw = PW ? 2 * (t % NWD) : 1;
-  r.cls = P;
-  r.chunk = l / (NT * 2);
-  r.i = l & 1;
-  r.ktap = kh * 3 + kw;
-  r.roff = PH ? 1 - t / NWD : 0;
-  r.coff = PW ? 1 - t % NWD : 0;
-  r.last = l == NT * 4 - 1;
-  return r;
-}
-
-// Pins the uses of a loaded chunk behind this point of the program.  The instruction scheduler otherwise hoists the unpacking
-// of the OTHER register set's chunks (committed after the next barrier) in front of the barrier, and with it their
-// s_waitcnt: the wait then covers loads that were meant to stay in flight for another iteration.
-__device__ __forceinline__ void pin(U128& a) { asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w)); }
-
-template <int S, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (S < N) {
-    f(std::integral_constant<int, S>{});
-    static_for<S + 1, N>(f);
-  }
+  return P == 0 ? grad_step<0>(l) : (P == 1 ? grad_step<1>(l) : (P == 2 ? grad_step<2>(l) : grad_step<3>(l)));
 }
 
 template <int KIND, int PRO>
@@ -118,11 +97,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_s2_roll64_kernel(const FrConvA
 
   // per-channel coefficients: [pro_a | pro_b | epi_a] x 64
   float* const coef = reinterpret_cast<float*>(smem + LY::COEF_OFF);
-  if (tid < K::C) {
-    coef[tid] = PRO != FR_PRO_NONE ? p.pro_a[tid] : 0.f;
-    coef[K::C + tid] = PRO == FR_PRO_BN ? p.pro_b[tid] : 0.f;
-    coef[2 * K::C + tid] = KIND == 1 ? p.epi_a[tid] : 0.f;
-  }
+  if (tid < K::C) fr_roll_stage_coef<PRO, KIND == 1>(coef, p, tid);
   // the cells no iteration ever writes: column -1 of the forward rows' odd plane, the column right of a g row
   if (KIND == 0) {
     for (int idx = tid; idx < K::F_NR * K::CH; idx += K::NTH)
@@ -207,10 +182,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_s2_roll64_kernel(const FrConvA
             if (PRO != FR_PRO_NONE) {  // pro2 (frhip_internal.h): 5 / 7 vector instructions per dword instead of 11-12
               x = pro8<PRO>(x, pa, pb);
             }
-            x.x &= keep;
-            x.y &= keep;
-            x.z &= keep;
-            x.w &= keep;
+            fr_keep16(x, keep);
             st16(smem + (s0 + ((hrow >> u) & 1)) * K::F_RSTR + hlds[u], x);
           }
         };
@@ -278,10 +250,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_s2_roll64_kernel(const FrConvA
           for (int u = 0; u < 2; ++u) {
             const int m = u * 32 + t5, mc = m < K::WL ? m : K::WL - 1;
             U128 x = sg[u];
-            x.x &= keep;
-            x.y &= keep;
-            x.z &= keep;
-            x.w &= keep;
+            fr_keep16(x, keep);
             st16(slot + mc * K::PSTR + ch * 16, x);
           }
         };
@@ -484,29 +453,16 @@ __global__ __launch_bounds__(512, 2) void conv3x3_s2_roll64_kernel(const FrConvA
 int s2roll_nseg(int B) {
   // row segments per image: enough workgroups for one per CU on 256 CUs; 56 rows must divide evenly
   static const int cand[6] = {1, 2, 4, 7, 14, 28};  // rows per walk 56 / nseg: even (the data-moving loop is unrolled by two)
-  static const int* fslot = fr_option_slot("FRHIP_S2ROLL_NSEG", -1);  // test hook: the tests walk whole images with small batches
-  const int forced = *fslot;
-  for (int k = 0; k < 6; ++k)
-    if (forced == cand[k]) return cand[k];
-  for (int k = 0; k < 6; ++k)
-    if ((long long)B * cand[k] >= 256) return cand[k];
-  return 28;
+  static const int* forced = fr_option_slot("FRHIP_S2ROLL_NSEG", -1);  // test hook: the tests walk whole images with small batches
+  return fr_pick_nseg(cand, 6, *forced, B);
 }
 
 template <int KIND, int PRO>
 int launch(const FrConvArgs& a, hipStream_t st) {
-  using LY = S2R::L<KIND>;
-  static unsigned long long attr_done = 0;  // one bit per device
-  if (fr_attr_needed(attr_done)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_s2_roll64_kernel<KIND, PRO>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, LY::LDS);
-    fr_attr_done(attr_done);
-  }
   const int nseg = s2roll_nseg(a.B);
   const int items = a.B * nseg;
   const int grid = items < 256 ? items : 256;  // persistent: weights are loaded into registers once per workgroup
-  FR_LAUNCH_KERNEL((conv3x3_s2_roll64_kernel<KIND, PRO>), dim3(grid), dim3(S2R::NTH), LY::LDS, st, a, nseg, items);
-  FR_LAUNCH_CHECK();
+  return fr_launch_lds<&conv3x3_s2_roll64_kernel<KIND, PRO>>(grid, S2R::NTH, S2R::L<KIND>::LDS, st, a, nseg, items);
 }
 
 }  // namespace
@@ -525,10 +481,6 @@ int fr_s2roll_parts(int B) { return B * s2roll_nseg(B); }
 
 int fr_s2roll_launch(const FrConvArgs& a, hipStream_t st) {
   if (a.mode == 2) return launch<1, FR_PRO_NONE>(a, st);
-  switch (a.pro) {
-    case FR_PRO_NONE: return launch<0, FR_PRO_NONE>(a, st);
-    case FR_PRO_BN: return launch<0, FR_PRO_BN>(a, st);
-    case FR_PRO_PRELU: return launch<0, FR_PRO_PRELU>(a, st);
-  }
-  FR_UNSUPPORTED("rolling-window convolution: prologue / epilogue combination not served");
+  return fr_by_pro(a.pro, [&](auto pro) { return launch<0, decltype(pro)::value>(a, st); },
+                   "rolling-window convolution: prologue / epilogue combination not served");
 }

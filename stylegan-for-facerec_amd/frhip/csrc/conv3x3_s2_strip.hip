@@ -16,12 +16,16 @@
 // two tap-steps ahead), no barrier inside a tap list, bf16 results leave through an LDS tile as row-contiguous
 // 16-byte stores.  Same contracts as fr_conv_igemm (mode 0 stride 2 / mode 2): bit-compatible layouts of src, w,
 // out, aux and the column partial sums.
+// Shared with the other 3x3 kernels: the tap table and the tap loop (conv_taps.h: FrTaps, fr_mma_taps; the ring depths are
+// this file's), the epilogue cells (conv_epilogue.h), the prologue pro8, fr_chunk_pixel and the prologue switch fr_by_pro
+// (frhip_internal.h), the launch fr_launch_lds (common.h).
 #include <stdlib.h>
 
 #include <type_traits>
 
 #include "common.h"
 #include "conv_epilogue.h"
+#include "conv_taps.h"
 #include "frhip_internal.h"
 
 #ifdef FRHIP_STAMPS
@@ -80,86 +84,19 @@ struct S2 {
   static_assert(LDS <= 160 * 1024, "LDS budget");
 };
 
-// Tap list of plane / class P = 2*ph + pw: NT = (ph ? 2 : 1) * (pw ? 2 : 1) taps; tap t -> (kernel tap index, LDS row
-// and column offset).  Forward: kernel row kh reads high-res row 2i+kh-1 = plane row i-1 (kh = 0, ph = 1), i (kh = 1,
-// ph = 0) or i (kh = 2, ph = 1); the image holds rows row0-1 .. row0+ROWS-1, so the LDS row offset is 0 or 1.
-// Gradient: dx row 2i+ph collects g rows i+1 (kh = 0) and i (kh = 2) for ph = 1, g row i (kh = 1) for ph = 0; the
-// image holds rows row0 .. row0+ROWS.
-template <int KIND, int P>
-struct Taps {
-  static constexpr int PH = P >> 1, PW = P & 1;
-  static constexpr int NH = PH ? 2 : 1, NWD = PW ? 2 : 1, NT = NH * NWD;
-  static constexpr int kh(int t) { return PH ? 2 * (t / NWD) : 1; }
-  static constexpr int kw(int t) { return PW ? 2 * (t % NWD) : 1; }
-  static constexpr int ktap(int t) { return kh(t) * 3 + kw(t); }
-  static constexpr int roff(int t) { return KIND == 0 ? (PH ? t / NWD : 1) : (PH ? 1 - t / NWD : 0); }
-  static constexpr int coff(int t) { return KIND == 0 ? (PW ? t % NWD : 1) : (PW ? 1 - t % NWD : 0); }
-};
-
-// acc += sum over the taps of (KIND, P) and all CIN channels, A from the LDS image, B from global/L2.
+// acc += sum over the taps of (KIND, P) and all CIN channels, A from the LDS image, B from global/L2: the shared tap loop
+// (conv_taps.h) with the strip instances' ring depths
 template <class C, int CIN, int KIND, int P>
 __device__ __forceinline__ void mma_taps(const char* smem, const int (&abase0)[C::TM], f32x4 (&acc)[C::TM][C::TN],
                                          const bf16_t* const (&wrow)[C::TN], const int wsh) {
-  using T = Taps<KIND, P>;
-  constexpr int NT = T::NT;
-  constexpr int UC = NT == 1 ? 2 : 1;  // 32-channel chunks per unrolled body (so that a body holds >= 2 tap-steps)
-  constexpr int QB = UC * NT;          // tap-steps per body: 2, 2, 2, 4
-  constexpr int DB = 2;                // weight ring depth == request distance in tap-steps
-  constexpr int NSTEP = QB * C::TM;
-  // A ring depth (divides NSTEP): one slot per M tile; 2 in the whole-image 256-channel instance (13 slots: 8-76 bytes of
-  // scratch, same time)
+  using T = FrTaps<KIND, P>;
+  constexpr int UC = T::NT == 1 ? 2 : 1;  // 32-channel chunks per unrolled body (so that a body holds >= 2 tap-steps: 2, 2, 2, 4)
+  constexpr int DB = 2;                   // weight ring depth == request distance in tap-steps
+  // A ring depth (divides the steps of a body): one slot per M tile; 2 in the whole-image 256-channel instance (13 slots:
+  // 8-76 bytes of scratch, same time)
   constexpr int D = (C::TM == 13 && CIN >= 256) ? 2 : C::TM;
   static_assert(D * 4 + C::TM * C::TN * 4 <= 140, "fragment ring + accumulators: register budget");
-  static_assert((CIN / 32) % UC == 0 && QB % DB == 0 && NSTEP % D == 0, "bad body shape");
-  int abase[C::TM];
-#pragma unroll
-  for (int i = 0; i < C::TM; ++i) abase[i] = abase0[i];
-  s16x8 bq[DB][C::TN];
-  s16x8 ring[D];
-  auto load_b = [&](int slot, int c0, int q) {
-    const int t = q % NT, u = q / NT;
-#pragma unroll
-    for (int j = 0; j < C::TN; ++j)
-      bq[slot][j] = *reinterpret_cast<const s16x8*>(wrow[j] + ((T::ktap(t) * CIN + c0 + u * 32) << wsh));
-  };
-  auto a_addr = [&](int step) -> const s16x8* {  // step in [0, 2*NSTEP): second half = next body
-    const int wrap = step >= NSTEP ? 1 : 0;
-    const int st = wrap ? step - NSTEP : step;
-    const int q = st / C::TM, i = st - q * C::TM;
-    const int t = q % NT, u = q / NT;
-    return reinterpret_cast<const s16x8*>(smem + abase[i] + T::roff(t) * C::RSTR + T::coff(t) * C::PSTR + u * 64 +
-                                          wrap * UC * 64);
-  };
-#pragma unroll
-  for (int d = 0; d < DB; ++d) load_b(d, 0, d);
-#pragma unroll
-  for (int d = 0; d < D; ++d) ring[d] = *a_addr(d);
-  for (int c0 = 0; c0 < CIN; c0 += 32 * UC) {
-#pragma unroll
-    for (int st = 0; st < NSTEP; ++st) {
-      const int q = st / C::TM, i = st - q * C::TM;
-      const int slot = q % DB;
-      const s16x8 a = ring[st % D];
-#pragma unroll
-      for (int j = 0; j < C::TN; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bq[slot][j], a, acc[i][j], 0, 0, 0);  // = (W X^T) tile
-      ring[st % D] = *a_addr(st + D);  // past the last chunk this reads (never used) bytes inside the LDS slack
-      if (i == C::TM - 1) {
-        int nq = q + DB, nc = c0;
-        if (nq >= QB) {
-          nq -= QB;
-          nc += 32 * UC;
-        }
-        nc = nc < CIN ? nc : CIN - 32 * UC;  // clamp instead of branching: the count of loads in flight stays static
-        load_b(slot, nc, nq);
-      }
-      __builtin_amdgcn_sched_group_barrier(0x008, C::TN, 0);  // MFMA
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);      // DS read
-      if (i == C::TM - 1) __builtin_amdgcn_sched_barrier(0);  // keep the weight requests two tap-steps ahead
-    }
-#pragma unroll
-    for (int i = 0; i < C::TM; ++i) abase[i] += 64 * UC;
-  }
+  fr_mma_taps<C, T, CIN, CIN, DB, D, UC>(smem, abase0, acc, wrow, wsh);
 }
 
 template <int CIN, int COUT, int WL, int ROWS, int WN, int NW, int KIND, int PRO, int NSPL = 1, int NIMG = 1>
@@ -207,10 +144,8 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_s2_kernel(const FrConvArgs
 #pragma unroll
       for (int u = 0; u < UNR; ++u) {
         const int idx = base + u * NTH + tid;
-        int pc = idx / C::CH;
-        const int img = NIMG > 1 ? pc / PLANE : 0;
-        pc -= img * PLANE;
-        const int gh = pc / C::GW, gw = pc - gh * C::GW;
+        int img, gh, gw;
+        fr_chunk_pixel<NIMG, C::GH, C::GW, C::CH>(idx, img, gh, gw);
         size_t pix;
         if (KIND == 0) {  // plane (ph, pw) of the high-res input: low-res rows row0-1 .. row0+ROWS-1, columns -1 .. WL-1
           const int i = row0 + gh - 1, j = gw - 1;
@@ -227,10 +162,8 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_s2_kernel(const FrConvArgs
       for (int u = 0; u < UNR; ++u) {
         const int idx = base + u * NTH + tid;
         if (idx < TOTAL) {
-          int pc = idx / C::CH;
-          const int img = NIMG > 1 ? pc / PLANE : 0;
-          pc -= img * PLANE;
-          const int gh = pc / C::GW, gw = pc - gh * C::GW;
+          int img, gh, gw;
+          fr_chunk_pixel<NIMG, C::GH, C::GW, C::CH>(idx, img, gh, gw);
           U128 x = v[u];
           if (PRO != FR_PRO_NONE && ok[u]) {  // pro2 (frhip_internal.h): the prologue on packed pairs
             x = pro8<PRO>(x, pa, pb);
@@ -264,7 +197,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_s2_kernel(const FrConvArgs
 #pragma unroll
     for (int u = 0; u < NPF; ++u) {
       const int idx = u * NTH + tid;
-      int pc = idx / C::CH;
+      int pc = idx / C::CH;  // (not fr_chunk_pixel: through the helper the prefetching 512-channel kernels change)
       const int img = NIMG > 1 ? pc / PLANE : 0;
       pc -= img * PLANE;
       const int gh = pc / C::GW, gw = pc - gh * C::GW;
@@ -280,10 +213,8 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_s2_kernel(const FrConvArgs
     for (int u = 0; u < NPF; ++u) {
       const int idx = u * NTH + tid;
       if (idx < TOTAL) {
-        int pc = idx / C::CH;
-        const int img = NIMG > 1 ? pc / PLANE : 0;
-        pc -= img * PLANE;
-        const int gh = pc / C::GW, gw = pc - gh * C::GW;
+        int img, gh, gw;
+        fr_chunk_pixel<NIMG, C::GH, C::GW, C::CH>(idx, img, gh, gw);
         U128 x = pf[PFP ? u : 0];
         if (PRO != FR_PRO_NONE && ((pfok >> u) & 1u)) {
           x = pro8<PRO>(x, pa, pb);
@@ -565,12 +496,9 @@ int launch(const FrConvArgs& a, hipStream_t st) {
 
 template <int CIN, int COUT, int WL, int ROWS, int WN, int NW, int KIND, int NSPL = 1, int NIMG = 1>
 int by_pro(const FrConvArgs& a, hipStream_t st) {
-  switch (a.pro) {
-    case FR_PRO_NONE: return launch<CIN, COUT, WL, ROWS, WN, NW, KIND, FR_PRO_NONE, NSPL, NIMG>(a, st);
-    case FR_PRO_BN: return launch<CIN, COUT, WL, ROWS, WN, NW, KIND, FR_PRO_BN, NSPL, NIMG>(a, st);
-    case FR_PRO_PRELU: return launch<CIN, COUT, WL, ROWS, WN, NW, KIND, FR_PRO_PRELU, NSPL, NIMG>(a, st);
-  }
-  FR_UNSUPPORTED("fr_conv3x3_s2_strip: unknown prologue");
+  return fr_by_pro(
+      a.pro, [&](auto pro) { return launch<CIN, COUT, WL, ROWS, WN, NW, KIND, decltype(pro)::value, NSPL, NIMG>(a, st); },
+      "fr_conv3x3_s2_strip: unknown prologue");
 }
 
 // One line of the table: an LDS-strip instance of one KIND (0: forward, one partial-sum row per strip; 1: data gradient,

@@ -19,12 +19,16 @@
 // (7 rows @28, the whole image @14, four images @7) with the output channels split over 1 / 2 / 4 workgroups.
 // Same layouts, partial-sum rows and arithmetic (K order: plane, channel stage, tap, 32-channel chunk) as
 // fr_conv3x3_s2_strip mode 0; dispatched from there.
+// Shared with the other 3x3 kernels: the tap table and the tap loop (conv_taps.h: FrTaps, fr_mma_taps; the ring depths are
+// this file's), the epilogue cells (conv_epilogue.h), the prologue pro8, fr_keep16, fr_chunk_pixel and the prologue
+// switch fr_by_pro (frhip_internal.h), the launch fr_launch_lds (common.h).
 #include <stdlib.h>
 
 #include <type_traits>
 
 #include "common.h"
 #include "conv_epilogue.h"
+#include "conv_taps.h"
 #include "frhip_internal.h"
 
 #ifdef FRHIP_STAMPS
@@ -74,86 +78,23 @@ struct WS {
   static_assert(TM == 13 && TN == 2, "196 pixels x 32 channels per computing wave");
 };
 
-// taps of parity plane P = 2*ph + pw (conv3x3_s2_strip.hip, Taps<0, P>)
-template <int P>
-struct Taps {
-  static constexpr int PH = P >> 1, PW = P & 1;
-  static constexpr int NWD = PW ? 2 : 1, NT = (PH ? 2 : 1) * NWD;
-  static constexpr int kh(int t) { return PH ? 2 * (t / NWD) : 1; }
-  static constexpr int kw(int t) { return PW ? 2 * (t % NWD) : 1; }
-  static constexpr int ktap(int t) { return kh(t) * 3 + kw(t); }
-  static constexpr int roff(int t) { return PH ? t / NWD : 1; }
-  static constexpr int coff(int t) { return PW ? t % NWD : 1; }
-};
-
-// acc += taps of plane P over the CK resident channels; A from the plane buffer, B (weights) from global / L2
+// acc += taps of plane P over the CK resident channels; A from the plane buffer, B (weights) from global / L2: the shared
+// tap loop (conv_taps.h) with this kernel's ring depths
 template <class C, int CIN, int P>
 __device__ __forceinline__ void mma_taps(const char* buf, const int (&abase0)[C::TM], f32x4 (&acc)[C::TM][C::TN],
                                          const bf16_t* const (&wrow)[C::TN], const int wsh) {
-  using T = Taps<P>;
-  constexpr int NT = T::NT;
+  using T = FrTaps<0, P>;
 #ifndef FRHIP_S2WS_DB
 #define FRHIP_S2WS_DB 4
 #endif
   constexpr int DB = FRHIP_S2WS_DB;    // weight ring: requested DB tap-steps (26 MFMAs each) ahead -- one wave per SIMD has no
                                        // partner to hide an L2 round trip behind
-  constexpr int UC = DB % NT == 0 ? DB / NT : 1;  // 32-channel chunks per unrolled body: a body holds a multiple of DB tap-steps
-  constexpr int QB = UC * NT;
-  constexpr int NSTEP = QB * C::TM;
+  constexpr int UC = DB % T::NT == 0 ? DB / T::NT : 1;  // 32-channel chunks per unrolled body: a body holds a multiple of DB tap-steps
 #ifndef FRHIP_S2WS_D
 #define FRHIP_S2WS_D 13
 #endif
   constexpr int D = FRHIP_S2WS_D;      // pixel-fragment ring: one wave per SIMD has nobody to hide an LDS round trip behind
-  static_assert((CK / 32) % UC == 0 && QB % DB == 0 && DB <= QB && NSTEP % D == 0, "bad body shape");
-  int abase[C::TM];
-#pragma unroll
-  for (int i = 0; i < C::TM; ++i) abase[i] = abase0[i];
-  s16x8 bq[DB][C::TN];
-  s16x8 ring[D];
-  auto load_b = [&](int slot, int c0, int q) {
-    const int t = q % NT, u = q / NT;
-#pragma unroll
-    for (int j = 0; j < C::TN; ++j)
-      bq[slot][j] = *reinterpret_cast<const s16x8*>(wrow[j] + ((T::ktap(t) * CIN + c0 + u * 32) << wsh));
-  };
-  auto a_addr = [&](int step) -> const s16x8* {
-    const int wrap = step >= NSTEP ? 1 : 0;
-    const int st = wrap ? step - NSTEP : step;
-    const int q = st / C::TM, i = st - q * C::TM;
-    const int t = q % NT, u = q / NT;
-    return reinterpret_cast<const s16x8*>(buf + abase[i] + T::roff(t) * C::RSTR + T::coff(t) * C::PSTR + u * 64 +
-                                          wrap * UC * 64);
-  };
-#pragma unroll
-  for (int d = 0; d < DB; ++d) load_b(d, 0, d);
-#pragma unroll
-  for (int d = 0; d < D; ++d) ring[d] = *a_addr(d);
-  for (int c0 = 0; c0 < CK; c0 += 32 * UC) {
-#pragma unroll
-    for (int st = 0; st < NSTEP; ++st) {
-      const int q = st / C::TM, i = st - q * C::TM;
-      const int slot = q % DB;
-      const s16x8 a = ring[st % D];
-#pragma unroll
-      for (int j = 0; j < C::TN; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bq[slot][j], a, acc[i][j], 0, 0, 0);  // = (W X^T) tile
-      ring[st % D] = *a_addr(st + D);  // past the last chunk: (never used) bytes inside the buffer's slack
-      if (i == C::TM - 1) {
-        int nq = q + DB, nc = c0;
-        if (nq >= QB) {
-          nq -= QB;
-          nc += 32 * UC;
-        }
-        nc = nc < CK ? nc : CK - 32 * UC;  // clamp instead of branching: the count of loads in flight stays static
-        load_b(slot, nc, nq);
-      }
-      __builtin_amdgcn_sched_group_barrier(0x008, C::TN, 0);  // MFMA
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);      // DS read
-      if (i == C::TM - 1) __builtin_amdgcn_sched_barrier(0);  // keep the weight requests two tap-steps ahead
-    }
-#pragma unroll
-    for (int i = 0; i < C::TM; ++i) abase[i] += 64 * UC;
-  }
+  fr_mma_taps<C, T, CIN, CK, DB, D, UC>(buf, abase0, acc, wrow, wsh);
 }
 
 template <int CIN, int WL, int ROWS, int NIMG, int PRO>
@@ -204,10 +145,8 @@ __global__ __launch_bounds__(512) void conv3x3_s2_ws_kernel(const FrConvArgs p, 
     for (int u = 0; u < C::PER; ++u) {
       int idx = u * NLT + lt;
       idx = idx < C::TOTAL ? idx : C::TOTAL - C::CH + ch;  // clamp: the last pixel, this thread's own channel chunk
-      int pc = idx / C::CH;
-      const int img = NIMG > 1 ? pc / C::PLANE : 0;
-      pc -= img * C::PLANE;
-      const int gh = pc / C::GW, gw = pc - gh * C::GW;
+      int img, gh, gw;
+      fr_chunk_pixel<NIMG, C::GH, C::GW, C::CH>(idx, img, gh, gw);
       const int i = row0 + gh - 1, j = gw - 1;
       const bool ok = i >= 0 && j >= 0;
       okm |= ok ? (1u << u) : 0u;
@@ -247,11 +186,7 @@ __global__ __launch_bounds__(512) void conv3x3_s2_ws_kernel(const FrConvArgs p, 
           // vector instructions are what a stage costs beside the computing wave of its SIMD (file header).
           x = pro8<PRO>(x, pa, pb);
         }
-        const unsigned keep = ((okm >> u) & 1u) ? 0xFFFFFFFFu : 0u;  // zero padding stays zero (BN would turn it into the shift)
-        x.x &= keep;
-        x.y &= keep;
-        x.z &= keep;
-        x.w &= keep;
+        fr_keep16(x, ((okm >> u) & 1u) ? 0xFFFFFFFFu : 0u);  // zero padding stays zero (BN would turn it into the shift)
         st16(dst + loff[u], x);
       }
     };
@@ -390,12 +325,8 @@ int launch(const FrConvArgs& a, hipStream_t st) {
 
 template <int CIN, int WL, int ROWS, int NIMG>
 int by_pro(const FrConvArgs& a, hipStream_t st) {
-  switch (a.pro) {
-    case FR_PRO_NONE: return launch<CIN, WL, ROWS, NIMG, FR_PRO_NONE>(a, st);
-    case FR_PRO_BN: return launch<CIN, WL, ROWS, NIMG, FR_PRO_BN>(a, st);
-    case FR_PRO_PRELU: return launch<CIN, WL, ROWS, NIMG, FR_PRO_PRELU>(a, st);
-  }
-  FR_UNSUPPORTED("fr_conv3x3_s2_strip (warp-specialised forward): unknown prologue");
+  return fr_by_pro(a.pro, [&](auto pro) { return launch<CIN, WL, ROWS, NIMG, decltype(pro)::value>(a, st); },
+                   "fr_conv3x3_s2_strip (warp-specialised forward): unknown prologue");
 }
 
 }  // namespace

@@ -19,6 +19,9 @@
 // Same reference arithmetic as fr_conv_igemm: Conv2d 3x3 s1 of bottleneck_IR (backbone/model_irse.py:57-59)
 // with BN apply (:57) or PReLU (:58) on the input, and its autograd data gradient (flip = 1: taps mirrored,
 // weights given as [Cin][tap][Cout]).
+// Shared with the other 3x3 kernels: the epilogue cells (conv_epilogue.h), the prologue pro8 and fr_chunk_pixel
+// (frhip_internal.h), the launch fr_launch_lds (common.h).  The K loop (nine taps with a run-time flip) and the two-source
+// prologue switch are this file's own.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -156,13 +159,9 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_strip_kernel(const FrConvA
   auto chunk_off = [&](int s, int idx, bool& ok, bool& own) -> size_t {
     int b = s / C::NS;
     const int row0 = (s - b * C::NS) * ROWS;
-    int pc_ = idx / C::CH;
-    if (NIMG > 1) {
-      const int img = pc_ / (C::GH * WP);
-      pc_ -= img * (C::GH * WP);
-      b = s * NIMG + img;
-    }
-    const int gh = pc_ / WP, gw = pc_ - gh * WP;
+    int img, gh, gw;
+    fr_chunk_pixel<NIMG, C::GH, WP, C::CH>(idx, img, gh, gw);
+    if (NIMG > 1) b = s * NIMG + img;
     const int h = row0 + gh - 1, w = gw - 1;
     ok = idx < TOTAL && (unsigned)h < (unsigned)C::H && (unsigned)w < (unsigned)W;
     own = ok && gh >= 1 && gh <= ROWS;  // a pixel of this strip's own rows (halo rows belong to the neighbours)
@@ -170,14 +169,9 @@ __global__ __launch_bounds__(NW * 64, 2) void conv3x3_strip_kernel(const FrConvA
   };
   auto chunk_store = [&](int idx, U128 x, U128 x2, bool ok, bool own, size_t off) {
     if (idx < TOTAL) {
-      int pc_ = idx / C::CH;
-      int ioff = 0;
-      if (NIMG > 1) {
-        const int img = pc_ / (C::GH * WP);
-        pc_ -= img * (C::GH * WP);
-        ioff = img * C::ISTR;
-      }
-      const int gh = pc_ / WP, gw = pc_ - gh * WP;
+      int img, gh, gw;
+      fr_chunk_pixel<NIMG, C::GH, WP, C::CH>(idx, img, gh, gw);
+      const int ioff = img * C::ISTR;
       if ((PRO == FR_PRO_BN || PRO == FR_PRO_PRELU) && ok) {
         // pro2 (frhip_internal.h): the prologue on packed pairs, 5 / 7 vector instructions per dword where the C form below
         // compiles to 11-12 (round 6: the strip's vector work is what its load phase costs beside the other waves)

@@ -28,6 +28,16 @@ constexpr int fr_strips_of(int B) {
   return B * C::NS / NIMG;
 }
 
+// Row segments per walk of a rolling-window kernel: `forced` when it is a candidate (option slot, test hook), else the first
+// of the n ascending candidates that gives one workgroup per CU on 256 CUs (per_seg = work items at one segment), else the last
+inline int fr_pick_nseg(const int* cand, int n, int forced, long long per_seg) {
+  for (int k = 0; k < n; ++k)
+    if (forced == cand[k]) return cand[k];
+  for (int k = 0; k < n; ++k)
+    if (per_seg * cand[k] >= 256) return cand[k];
+  return cand[n - 1];
+}
+
 // out[i] = sum_g slab[g][i] in the fixed order g = 0, 1, ... (n elements, n % 4 == 0); conv_wgrad_strip.hip
 int fr_launch_reduce_slabs(const float* slab, int groups, long long n, float* out, hipStream_t st);
 
@@ -106,6 +116,42 @@ __device__ __forceinline__ U128 pro8(U128 x, const float (&a)[8], const float (&
   x.w = pro2<PRO>(x.w, a[6], b[6], a[7], b[7]);
   return x;
 }
+// keep (all ones) or zero (0) a chunk without a branch: padding stays zero behind a prologue (BN would turn it into the shift)
+__device__ __forceinline__ void fr_keep16(U128& x, unsigned keep) {
+  x.x &= keep;
+  x.y &= keep;
+  x.z &= keep;
+  x.w &= keep;
+}
+// Pins the uses of a loaded chunk behind this point of the program.  The instruction scheduler otherwise hoists the unpacking
+// of the OTHER register set's chunks (committed after the next barrier) in front of the barrier, and with it their
+// s_waitcnt: the wait then covers loads that were meant to stay in flight for another iteration.
+__device__ __forceinline__ void pin(U128& a) { asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w)); }
+// f(std::integral_constant<int, S>) ... f(std::integral_constant<int, N - 1>): a loop whose index is a constant expression
+template <int S, int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+  if constexpr (S < N) {
+    f(std::integral_constant<int, S>{});
+    static_for<S + 1, N>(f);
+  }
+}
+// the 64-channel rolling-window kernels: per-channel coefficients into LDS, by threads 0..63 -- coef = [pro_a | pro_b | epi_a]
+// x 64 (0 where PRO / EA has no use for one)
+template <int PRO, bool EA>
+__device__ __forceinline__ void fr_roll_stage_coef(float* coef, const FrConvArgs& p, int tid) {
+  coef[tid] = PRO != FR_PRO_NONE ? p.pro_a[tid] : 0.f;
+  coef[64 + tid] = PRO == FR_PRO_BN ? p.pro_b[tid] : 0.f;
+  coef[2 * 64 + tid] = EA ? p.epi_a[tid] : 0.f;
+}
+// staged chunk index -> (image, halo row, halo column) of NIMG stacked [GH][GW] halo images with CH 16-byte chunks per pixel
+template <int NIMG, int GH, int GW, int CH>
+__device__ __forceinline__ void fr_chunk_pixel(int idx, int& img, int& gh, int& gw) {
+  int pc = idx / CH;
+  img = NIMG > 1 ? pc / (GH * GW) : 0;
+  pc -= img * (GH * GW);
+  gh = pc / GW;
+  gw = pc - gh * GW;
+}
 
 constexpr int FR_WGRAD_CT = 64;  // co and ci tile of every weight-gradient slab kernel
 
@@ -130,14 +176,15 @@ int fr_launch_slab_kernel(const FrWgradArgs& a, hipStream_t st, int threads, int
   if (a.defer) return 0;
   return fr_launch_reduce_slabs(a.slab, a.nsplit, (long long)a.Cout * 9 * a.SC, a.dw, st);
 }
-// f(std::integral_constant<int, PRO>) for the prologue of a weight-gradient launch
+// f(std::integral_constant<int, PRO>) for the one-source prologue of a launch; `unknown`: the calling family's message for
+// any other value (default: the weight-gradient family's)
 template <class F>
-int fr_by_pro(int pro, F f) {
+int fr_by_pro(int pro, F f, const char* unknown = "fr_conv_wgrad_strip: unknown prologue") {
   switch (pro) {
     case FR_PRO_NONE: return f(std::integral_constant<int, FR_PRO_NONE>{});
     case FR_PRO_BN: return f(std::integral_constant<int, FR_PRO_BN>{});
     case FR_PRO_PRELU: return f(std::integral_constant<int, FR_PRO_PRELU>{});
   }
-  FR_UNSUPPORTED("fr_conv_wgrad_strip: unknown prologue");
+  FR_UNSUPPORTED(unknown);
 }
 #endif
