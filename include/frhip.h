@@ -701,6 +701,39 @@ int fr_circle_apply(const float* cos, const int64_t* label, float* out, int rows
 int fr_circle_bwd(const float* g, const float* cos, const int64_t* label, float* gcos, int rows, int N, int ld, int ldg,
                   float o_p, float o_n, float gamma, void* stream);
 
+/* ---- SST_Prototype (head/metrics.py:638-708, "Semi-Siamese Training for Shallow Face Learning").  The head has no weight:
+ *      its class matrix is a queue of gallery embeddings, kept on the device in both GEMM layouts, q [D][Q] (the reference's
+ *      buffer `queue`, the data gradient's operand) and qt [Q][D] (the cosine GEMM's operand), already normalised.  A call
+ *      works on rows = B or 2 B probe rows (the two views stacked); row m has the label index + m % B and belongs to block
+ *      blk = m / B.  The cosines come from two FR_EPI_STORE GEMMs: cos [rows][ld] against the whole of qt, whose window
+ *      columns [index, index + B) are don't-care, and cw [rows][ldw] against the stacked gallery rows [g2n; g1n] that stand in
+ *      the window: row m reads cw[m][blk * B + j] for the window column index + j (rows = B: the compact block cw[m][j]). */
+/* replaces update_queue, :675-680, without its host reads.  gn [B][D]: the chosen gallery view, rows already normalised by
+ * fr_row_normalize; ids [B].  Writes qt[index + b][d] = q[d][index + b] = gn[b][d] (the same bits in both copies) and
+ * labels[index + b] = ids[b], for b < B, d < D.  It writes nothing else of q, qt and labels, reads nothing on the host and
+ * does not synchronise.  index + B <= Q (the reference's slice assignment raises otherwise); it does not advance index. */
+int fr_sst_enqueue(const float* gn, const int64_t* ids, float* qt, float* q, int64_t* labels, int index, int B, int D, int Q,
+                   void* stream);
+/* replaces compute_theta / add_margin and forward's * scale, :654-673, :701-702, without the clone of the queue.  A column
+ * inside the window takes its cosine from cw, every other column from cos;  c = clamp(., -1, 1), the clamps comparisons: NaN
+ * passes;  on the label column, kind 0 ('softmax' and any other string): c;  kind 1 ('am_softmax'): c - p0, p0 = margin;
+ * kind 2 ('arc_softmax'): c * p0 - sqrt(1 - c * c) * p1, p0 = cos(margin), p1 = sin(margin) rounded to fp32 (no threshold
+ * fallback, no mm);  out[m][n] = that * s.  Every operation is rounded to fp32 on its own, in the reference's order, with no
+ * FMA contraction: on the same cosines out has the bits of the reference's fp32 expression (as fr_circle_apply).  ld a
+ * multiple of 4, ldw >= rows; columns Q..ld of out are written as 0.  cos, cw and the queue are left alone. */
+int fr_sst_apply(const float* cos, const float* cw, float* out, int rows, int B, int Q, int ld, int ldw, int index, int kind,
+                 float p0, float p1, float s, void* stream);
+/* the backward of :654-673, :701-702.  g is [rows][Q] contiguous.  gcos [rows][ldg] (ldg >= ld, a multiple of 4):
+ * (g[m][n] * s) where -1 <= cos[m][n] <= 1 (torch.clamp passes gradient on the closed interval; a NaN cosine gets 0), and
+ * exactly 0 in the window columns and in the padding Q..ldg: the label column lies in the window, so d out / d c = s
+ * everywhere else.  gwin [rows][ldw], every column written, in cw's layout: gwin[m][blk * B + j] = (g[m][index + j] * s) * d
+ * under the pass mask of cw[m][blk * B + j], d = 1 off the label column (j = m % B) and on it for kinds 0 and 1, d = p0 +
+ * (c / sqrt(1 - c * c)) * p1 for kind 2; 0 outside the row's block.  So gwin is the K operand of one GEMM against the
+ * stacked gallery rows, and the live queue's window enters neither direction.  A target cosine of exactly +-1 makes the
+ * reference's own gradient infinite under kind 2 (sqrt(1 - c^2) = 0); nothing is done about that here either. */
+int fr_sst_bwd(const float* g, const float* cos, const float* cw, float* gcos, float* gwin, int rows, int B, int Q, int ld,
+               int ldg, int ldw, int index, int kind, float p0, float p1, float s, void* stream);
+
 /* ---- ArcNegFace (head/metrics.py:394-433) on the raw cosines cos [rows][ld] of the FR_EPI_STORE GEMM between
  *      fr_row_normalize'd embeddings and the fr_row_normalize'd [N][D] weight.  The head never clamps its cosines and has
  *      no state besides its weight. */
@@ -904,6 +937,22 @@ typedef struct FrAdamTensor {
 int fr_adam_step(const FrAdamTensor* table_dev, const int32_t* chunks_dev, int nchunks, float step_size, float w1,
                  float beta2, float w2, float eps, float bc2_sqrt, void* stream);
 
+/* ---- multi-tensor moving average of parameters: the gallery network of SST_Prototype follows the probe network (head/
+ *      metrics.py:638-708 takes both networks' embeddings; the reference has no driver that moves the gallery), same table /
+ *      chunk scheme as fr_sgd_step:
+ *   dst = a * dst + b * src
+ * with a = float(alpha), b = float(1.0 - alpha), the subtraction done in double on the host.  Two multiplies and one add,
+ * each rounded to fp32 on its own (no FMA contraction): bit for bit the np.float32 restatement.  src is left alone.
+ * nchunks <= 0 launches nothing and returns 0; with nchunks > 0 both tables are required.  One thread block per chunk of
+ * fr_ema_chunk_elems() elements. */
+typedef struct FrEmaTensor {
+  float* dst;
+  const float* src;
+  long long n;
+} FrEmaTensor;
+int fr_ema_chunk_elems(void);
+int fr_ema_step(const FrEmaTensor* table_dev, const int32_t* chunks_dev, int nchunks, float a, float b, void* stream);
+
 /* out[r][c] = bias ? bias[c] : 0  (fp32 [rows][C]); seeds the split-K accumulation of Linear(25088,512) */
 int fr_fill_rows(float* out, const float* bias, long long rows, int C, void* stream);
 
@@ -933,7 +982,8 @@ int fr_get_option(const char* name, int dflt);
 int fr_arm_stop_event(void* event);
 int fr_finish_stop_event(void* stream);
 /* sizeof() of the argument structs as compiled, for binding self-checks: 0 FrConvArgs, 1 FrWgradArgs,
- * 2 FrApplyArgs, 3 FrBnBwdArgs, 4 FrSgdTensor, 5 FrPackTensor, 6 FrAdamTensor, 7 FrBnEvalEntry, 8 FrBnFinArgs */
+ * 2 FrApplyArgs, 3 FrBnBwdArgs, 4 FrSgdTensor, 5 FrPackTensor, 6 FrAdamTensor, 7 FrBnEvalEntry, 8 FrBnFinArgs,
+ * 9 FrEmaTensor */
 int fr_struct_size(int which);
 const char* fr_last_error_string(void);
 

@@ -26,6 +26,7 @@ extern "C" int fr_struct_size(int which) {
     case 6: return (int)sizeof(FrAdamTensor);
     case 7: return (int)sizeof(FrBnEvalEntry);
     case 8: return (int)sizeof(FrBnFinArgs);
+    case 9: return (int)sizeof(FrEmaTensor);
   }
   return -1;
 }

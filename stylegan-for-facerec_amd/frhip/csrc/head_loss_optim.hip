@@ -13,6 +13,8 @@
 //   FocalLoss on mean CE                                              loss/focal.py:17-21
 //   accuracy top-1/5                                                  util/utils.py:343-358
 //   optim.SGD(momentum, coupled weight decay on group 0)              train.py:196, :313-316
+//   the gallery network of SST_Prototype as a moving average of the probe network (head/metrics.py:638-708; the
+//   reference has no driver for it: dst = a dst + b src over the parameters)
 #include <stdio.h>
 
 #include "common.h"
@@ -1223,6 +1225,24 @@ __global__ __launch_bounds__(256) void adam_kernel(const FrAdamTensor* __restric
   }
 }
 
+// ------------------------------------------------------------------------------------------ parameter moving average
+// dst = a * dst + b * src: two multiplies and one add, each rounded to fp32 on its own (plain operators under "fp
+// contract(off)", as adam_kernel), so the result has the bits of the np.float32 restatement.
+__global__ __launch_bounds__(256) void ema_kernel(const FrEmaTensor* __restrict__ table, const int2* __restrict__ chunks,
+                                                  float a, float b) {
+#pragma clang fp contract(off)
+  const int2 ch = chunks[blockIdx.x];
+  const FrEmaTensor t = table[ch.x];
+  const long long base = (long long)ch.y * SGD_CHUNK;
+  long long end = base + SGD_CHUNK;
+  if (end > t.n) end = t.n;
+  for (long long i = base + threadIdx.x; i < end; i += 256) {
+    const float keep = a * t.dst[i];
+    const float take = b * t.src[i];
+    t.dst[i] = keep + take;
+  }
+}
+
 }  // namespace
 
 extern "C" int fr_row_normalize(const float* x, void* xn, void* xt, float* inv, int rows, int rows_pad, int D,
@@ -1605,5 +1625,16 @@ extern "C" int fr_sgd_step(const FrSgdTensor* table_dev, const int32_t* chunks_d
   if (!table_dev || !chunks_dev) FR_UNSUPPORTED("fr_sgd_step: table_dev and chunks_dev are required when nchunks > 0");
   hipLaunchKernelGGL(sgd_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, table_dev,
                      (const int2*)chunks_dev, lr, momentum);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_ema_chunk_elems(void) { return SGD_CHUNK; }
+
+extern "C" int fr_ema_step(const FrEmaTensor* table_dev, const int32_t* chunks_dev, int nchunks, float a, float b,
+                           void* stream) {
+  if (nchunks <= 0) return 0;
+  if (!table_dev || !chunks_dev) FR_UNSUPPORTED("fr_ema_step: table_dev and chunks_dev are required when nchunks > 0");
+  hipLaunchKernelGGL(ema_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, table_dev, (const int2*)chunks_dev, a,
+                     b);
   FR_LAUNCH_CHECK();
 }

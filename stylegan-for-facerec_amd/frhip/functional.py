@@ -1,4 +1,5 @@
-"""autograd.Function wrappers over the HIP kernels for the heads (the margin heads and the plain Softmax head), the focal
+"""autograd.Function wrappers over the HIP kernels for the heads (the margin heads, the plain Softmax head and the queue head
+SST_Prototype), the focal
 loss, the plain cross entropy and top-k accuracy.
 
 These are what ``head/metrics.py``, ``loss/focal.py``, ``loss/softmax.py`` and ``util/utils.py`` call.  Inputs must be
@@ -458,6 +459,118 @@ def arcneg_backward(saved, cfg, g, need_x, need_w, raw_x_grad=False):
     ``raw_x_grad``: as in ``margin_backward``."""
     return _gcos_backward(saved, cfg, g, need_x, need_w, raw_x_grad, lambda g, gcos, B, N, st: ops.call(
         "fr_arcneg_bwd", g, saved.cos, saved.label, saved.rowv, gcos, B, N, cfg.ld, cfg.Np, cfg.p0, cfg.p1, cfg.s, st)())
+
+
+SST_KINDS = {"am_softmax": 1, "arc_softmax": 2}  # fr_sst_apply's kind; every other loss_type is 0 (head/metrics.py:657-666)
+
+# What an SST_Prototype forward call keeps: x [2B, D] the stacked probe rows, inv_x their reciprocal norms, cos [2B, Q] the
+# raw cosines against the whole queue, cw [2B, Rp] those against the stacked gallery rows, gt [D, Rp] the transposed
+# normalised gallery rows (Rp = pad(2B, 32), columns >= 2B zero).  SSTCfg.gen: the owner's generation at the call.
+SSTSaved = collections.namedtuple("SSTSaved", "x inv_x cos cw gt")
+SSTCfg = collections.namedtuple("SSTCfg", "B Q Rp index kind p0 p1 s gen")
+
+
+def sst_margin(loss_type, margin):
+    """(kind, p0, p1) of fr_sst_apply for a head's ``loss_type`` / ``margin``."""
+    kind = SST_KINDS.get(loss_type, 0)
+    if kind == 2:
+        return kind, math.cos(margin), math.sin(margin)
+    return kind, (float(margin) if kind == 1 else 0.0), 0.0
+
+
+def _sst_gemm(st, src, w, out, rows, K, N, ldc, epi=ops.EPI_STORE, splitk=0):
+    ops.conv(st, FR_F32, src=src, w=w, out=out, B=rows, RH=1, RW=1, SH=1, SW=1, SC=K, N=N, KH=1, KW=1, stride=1, pad=0,
+             mode=0, lda=K, ldc=ldc, pro=0, epi=epi, out_f32=1, splitk=splitk)()
+
+
+def sst_forward(p, g, ids, q, qt, labels, index, take_g1, kind, p0, p1, s, gen=0):
+    """SST_Prototype logits (head/metrics.py:689-708) for fp32 device tensors.  ``p`` [2B, D] is the stacked probe views
+    [p1; p2], ``g`` [2B, D] the stacked gallery views [g2; g1] in the order the probe rows meet them, ``ids`` int64 [B];
+    ``q`` [D, Q], ``qt`` [Q, D] and ``labels`` [Q] are the module's queue in both layouts and its label buffer, ``index`` the
+    window's first column.  Two fr_row_normalize launches (the stacked probes, the stacked galleries, which also leaves
+    their transpose), fr_sst_enqueue with the view the coin chose (``take_g1``), the FR_EPI_STORE GEMM of the 2B rows
+    against ``qt``, one more against the 2B gallery rows (its two diagonal blocks are p1n . g2n^T and p2n . g1n^T), and
+    fr_sst_apply, which takes the window columns from that block.  The queue is neither cloned, normalised nor repacked,
+    and nothing waits on the host.  Returns (out [2B, Q]: output1 over output2, saved, cfg) for ``sst_backward``."""
+    ops.ptr(p)  # host tensors fail loudly, before anything asks for a device
+    R, D = p.shape
+    B, Q = R // 2, q.shape[1]
+    dev = p.device
+    st = ops.current_stream_ptr()
+    p = p.contiguous().float()
+    g = g.contiguous().float()
+    Rp = _pad(R, 32)
+    xn = torch.empty(R, D, device=dev)
+    inv_x = torch.empty(R, device=dev)
+    ops.call("fr_row_normalize", p, xn, None, inv_x, R, R, D, 0, FR_F32, st)()
+    gn = torch.empty(Rp, D, device=dev)  # rows >= 2B zero
+    gt = torch.empty(D, Rp, device=dev)
+    inv_g = torch.empty(R, device=dev)
+    ops.call("fr_row_normalize", g, gn, gt, inv_g, R, Rp, D, Rp, FR_F32, st)()
+    ops.call("fr_sst_enqueue", gn[B:R] if take_g1 else gn[:B], ids, qt, q, labels, int(index), B, D, Q, st)()
+    cos = torch.empty(R, Q, device=dev)
+    _sst_gemm(st, xn, qt, cos, R, D, Q, Q)
+    cw = torch.empty(R, Rp, device=dev)
+    _sst_gemm(st, xn, gn, cw, R, D, R, Rp)
+    out = torch.empty(R, Q, device=dev)
+    ops.call("fr_sst_apply", cos, cw, out, R, B, Q, Q, Rp, int(index), kind, float(p0), float(p1), float(s), st)()
+    return out, SSTSaved(p, inv_x, cos, cw, gt), SSTCfg(B, Q, Rp, int(index), kind, float(p0), float(p1), float(s), gen)
+
+
+def sst_backward(saved, cfg, g, q):
+    """gx [2B, D] of ``sst_forward``: fr_sst_bwd, the split-K data-gradient GEMM of gcos against ``q`` (the queue itself;
+    gcos is zero in the window, so the live window's content does not enter), the window's contribution gwin . [g2n; g1n]
+    as further slabs, fr_reduce_parts over all slabs in a fixed order, fr_normalize_bwd.  Nothing flows to the gallery rows
+    or the queue: no weight-gradient GEMM."""
+    R, D = saved.x.shape
+    Q, Rp = cfg.Q, cfg.Rp
+    dev = saved.x.device
+    st = ops.current_stream_ptr()
+    gcos = torch.empty(R, Q, device=dev)
+    gwin = torch.empty(R, Rp, device=dev)
+    ops.call("fr_sst_bwd", g.contiguous().float(), saved.cos, saved.cw, gcos, gwin, R, cfg.B, Q, Q, Q, Rp, cfg.index,
+             cfg.kind, cfg.p0, cfg.p1, cfg.s, st)()
+    nk = Q // 32
+    splitk = max(1, min(nk, 64, nk // 8))
+    # the window's GEMM is a handful of workgroups whose time is the length of their K loop (54 us at K = 512 in one
+    # slice, profiles/sst_prototype_b256_q16384.txt): slices of four K steps, eight at the most
+    wsplit = max(1, min(8, Rp // 128))
+    slab = torch.empty(splitk + wsplit, R, D, device=dev)  # K slices and the window's slabs, added in a fixed order
+    _sst_gemm(st, gcos, q, slab, R, Q, D, D, ops.EPI_SLAB, splitk)
+    _sst_gemm(st, gwin, saved.gt, slab[splitk:], R, Rp, D, D, ops.EPI_SLAB, wsplit)
+    G = torch.empty(R, D, device=dev)
+    ops.call("fr_reduce_parts", slab, splitk + wsplit, 1, R * D, G, None, None, st)()
+    gx = torch.empty(R, D, device=dev)
+    ops.call("fr_normalize_bwd", G, saved.x, saved.inv_x, gx, R, D, st)()
+    return gx
+
+
+class SSTHeadFn(torch.autograd.Function):
+    """SST_Prototype (head/metrics.py:638-708) on the HIP path; see ``sst_forward``.  ``owner`` is the module: its
+    ``_generation`` counts forward calls, and a backward call behind a later forward call raises, since that call overwrote
+    another window of the queue this one's data gradient reads."""
+
+    @staticmethod
+    def forward(ctx, p, g, ids, q, qt, labels, index, take_g1, kind, p0, p1, s, owner):
+        out, saved, cfg = sst_forward(p, g, ids, q, qt, labels, index, take_g1, kind, p0, p1, s, owner._generation)
+        ctx.save_for_backward(*saved)
+        ctx.cfg, ctx.q, ctx.owner = cfg, q, owner  # q: written through its pointer on every call, so not a saved tensor
+        ctx.set_materialize_grads(False)
+        # two outputs, not one that the caller slices: the backward of a slice fills and adds a whole [2B, Q] matrix
+        return out[:cfg.B], out[cfg.B:]
+
+    @staticmethod
+    def backward(ctx, g1, g2):
+        if ctx.owner._generation != ctx.cfg.gen:
+            raise RuntimeError("SST_Prototype: backward() after a later forward call of the same module -- the queue holds "
+                               "one step at a time (%d forward calls since)" % (ctx.owner._generation - ctx.cfg.gen))
+        gx = None
+        if ctx.needs_input_grad[0] and (g1 is not None or g2 is not None):
+            saved = SSTSaved(*ctx.saved_tensors)
+            halves = [saved.cos.new_zeros(ctx.cfg.B, ctx.cfg.Q) if h is None else h.float() for h in (g1, g2)]
+            g = torch.cat(halves)
+            gx = sst_backward(saved, ctx.cfg, g, ctx.q)
+        return (gx,) + (None,) * 12
 
 
 def _row_pitch(t):

@@ -1,4 +1,5 @@
-"""SGD with momentum as ONE multi-tensor HIP launch per step (reference: optim.SGD at train.py:196).
+"""SGD with momentum as ONE multi-tensor HIP launch per step (reference: optim.SGD at train.py:196); ``Adam`` and the
+parameter moving average ``ParamEMA`` on the same table / chunk scheme.
 
 Same constructor shape as ``torch.optim.SGD`` (param groups with per-group ``weight_decay`` / ``lr``), same
 update:  d = g + wd*p ; buf = momentum*buf + d ; p -= lr*buf, with buf starting at zero so
@@ -209,6 +210,66 @@ class Adam(torch.optim.Optimizer):
                 self.state[p]["step"] += 1.0
             rec[1] = step
         return loss
+
+
+class ParamEMA(object):
+    """``dst = alpha * dst + (1 - alpha) * src`` over the parameters of two modules of the same class, as ONE multi-tensor HIP
+    launch per ``step()``: the gallery network of semi-siamese training (``head.metrics.SST_Prototype``) following the probe
+    network.  Buffers are not touched: a gallery network keeps its own BatchNorm statistics.  The kernel takes ``a =
+    float(alpha)`` and ``b = float(1.0 - alpha)`` (the subtraction in double) and rounds the two products and the sum to fp32
+    one by one; on host parameters ``step()`` runs the same expression in torch.  The launch table is cached on the
+    tensors' addresses, as ``SGD``'s."""
+
+    def __init__(self, dst_module, src_module, alpha=0.999):
+        dst, src = list(dst_module.named_parameters()), list(src_module.named_parameters())
+        if [n for n, _ in dst] != [n for n, _ in src]:
+            raise ValueError("frhip.optim.ParamEMA: the two modules must have the same parameters, in the same order")
+        self.pairs = [(d, s) for (_, d), (_, s) in zip(dst, src)]
+        self.alpha = float(alpha)
+        self._sig = None
+        self._table = None  # (table_dev, chunks_dev, nchunks)
+
+    def _signature(self):
+        return tuple((d.data_ptr(), s.data_ptr()) for d, s in self.pairs)
+
+    def _build(self):
+        chunk = _lib.lib.fr_ema_chunk_elems()
+        arr = (_lib.FrEmaTensor * len(self.pairs))()
+        chunks = []
+        for i, (d, s) in enumerate(self.pairs):
+            if d.device != s.device or d.dtype != torch.float32 or s.dtype != torch.float32:
+                raise _lib.FrhipError("frhip.optim.ParamEMA: both parameters must be float32 tensors on one device")
+            if not _dense_same(d, s):
+                raise _lib.FrhipError("frhip.optim.ParamEMA: the two parameters must share one dense layout")
+            arr[i].dst, arr[i].src, arr[i].n = d.data_ptr(), s.data_ptr(), d.numel()
+            chunks.extend((i, c) for c in range((d.numel() + chunk - 1) // chunk))
+        dev = self.pairs[0][0].device
+        raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+        ch = torch.tensor(chunks, dtype=torch.int32).reshape(-1).to(dev)
+        self._table = (raw, ch, len(chunks))
+
+    @torch.no_grad()
+    def step(self):
+        if not self.pairs:
+            return
+        a, b = self.alpha, 1.0 - self.alpha
+        devices = set(t.device.type for pair in self.pairs for t in pair)
+        if devices == {"cpu"}:
+            for d, s in self.pairs:
+                if not _dense_same(d, s):
+                    raise _lib.FrhipError("frhip.optim.ParamEMA: the two parameters must share one dense layout")
+                d.copy_(d * a + s * b)  # two products and a sum, each rounded on its own: what the kernel computes
+            return
+        if devices != {"cuda"}:
+            raise _lib.FrhipError("frhip.optim.ParamEMA: the parameters of both modules must live on one device")
+        sig = self._signature()
+        if sig != self._sig:
+            self._build()
+            self._sig = sig
+        raw, ch, n = self._table
+        table = ctypes.cast(ctypes.c_void_p(raw.data_ptr()), ctypes.POINTER(_lib.FrEmaTensor))  # device array
+        ops.Launch("fr_ema_step", [table, ctypes.c_void_p(ch.data_ptr()), n, float(a), float(b),
+                                   ops.current_stream_ptr()])()
 
 
 def _dense_same(a, b):

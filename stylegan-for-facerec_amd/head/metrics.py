@@ -6,6 +6,7 @@
     from head.metrics import CircleLoss, AM_Softmax                          (reference head/metrics.py:435, :371)
     from head.metrics import ArcNegFace                                      (reference head/metrics.py:394)
     from head.metrics import Softmax                                         (reference head/metrics.py:12)
+    from head.metrics import SST_Prototype                                   (reference head/metrics.py:638)
 
 The four heads the reference driver can select (``HEAD_NAME``, train.py:56,178-182) and ``CurricularFace`` / ``MagFace`` /
 ``AdaCos`` / ``NPCFace`` / ``MV_Softmax`` / ``CircleLoss`` / ``AM_Softmax`` / ``ArcNegFace`` (eight of the FaceX-Zoo heads of the reference's
@@ -56,6 +57,16 @@ head/metrics.py that its driver never names; train.py here accepts them) run on 
     accumulated dot product; the backward pass is the two gradient GEMMs of the cosine heads without their normalisation
     backwards, and a column-sum kernel that adds the bias gradient over the rows in order.  On host tensors it is
     ``F.linear``.  Parameters ``weight`` and ``bias``.
+  * ``SST_Prototype`` (semi-siamese training): no parameter; the class matrix is the buffer ``queue`` of normalised gallery
+    embeddings, kept on the device in both GEMM layouts.  Per call: the two stacked probe views and the two stacked gallery
+    views are normalised (two launches), one launch writes the chosen gallery view into B columns of both copies of the
+    queue and its ids into the label buffer, the same fp32 GEMM gives the raw cosines of the 2B rows against the whole queue
+    and, in a small second launch, against the gallery rows that stand in the window; one row kernel clamps, takes the
+    window columns from the small GEMM, applies the label column's margin (``am_softmax`` / ``arc_softmax``) and the scale in
+    the reference's fp32 operation order.  The queue is never cloned, normalised or repacked, nothing waits on the host, and
+    the backward pass is one row kernel, the split-K data-gradient GEMM against ``queue`` itself plus a few slabs for the
+    window, and the row normalisation's backward: nothing flows to the gallery rows or the queue.  On host tensors it is the
+    reference's arithmetic written out of place.
 On host tensors ``SphereFace`` / ``Am_softmax`` / ``CurricularFace`` / ``MagFace`` / ``AdaCos`` / ``NPCFace`` / ``MV_Softmax`` /
 ``CircleLoss`` / ``AM_Softmax`` / ``ArcNegFace`` run the reference's plain-PyTorch arithmetic (the
 restatement the tests compare with); ``ArcFace`` / ``CosFace`` refuse host tensors.  ``SphereFace.iter`` counts forward
@@ -105,8 +116,22 @@ Differences from the reference that a caller can observe:
     target cosine above 1 by rounding (1 + 2^-23) makes acos NaN, and with it ``a``, every ``t`` of the row and so the
     whole row of logits and gradients; a target cosine of exactly +1 makes the reference's own gradient infinite, and
     nothing is done about it here either; a raw negative beyond +-1 keeps its value and its gradient ``scale * t``.
+  * ``SST_Prototype``: ``label`` is an int64 tensor of shape [B] on the embeddings' device, also for B = 1 (the reference's
+    ``squeeze`` makes it 0-dim there) and without the reference's unconditional ``.cuda()`` (:696).  ``label_list`` is a
+    property that reads the buffer ``labels`` (int64, non-persistent) on demand, and on the device path the fourth returned
+    value is a ``collections.abc.Set`` over a device clone of it that materialises on first use; it compares equal to the
+    reference's ``set``.  A window that would run past the queue (``index + B > queue_size``) raises ``RuntimeError`` on
+    both paths before any state is touched and before the coin is drawn, where the reference raises at its slice
+    assignment after it has computed the logits.  The device path needs ``queue_size % 32 == 0`` (``NotImplementedError``
+    otherwise; the host path serves any size) and fp32.  A backward call behind a later forward call of the same module
+    raises: the queue holds one step at a time.  The host path replaces ``queue`` by a new tensor on every call instead of
+    writing into it.  With ``arc_softmax`` a target cosine of exactly +-1 makes the reference's own gradient infinite, and
+    nothing is done about it here either.  ``queue_state()`` / ``load_queue_state()`` are additions for a driver's state
+    file; the state dict stays the reference's (``queue`` alone).
 """
+import collections.abc
 import math
+import random
 
 import torch
 import torch.distributed as dist
@@ -567,3 +592,169 @@ class ArcNegFace(nn.Module):
         a = torch.where(branch, arc, gt - self.mm)
         t = (self.alpha * torch.exp(-torch.pow(c - a, 2) / self.sigma)).detach()
         return self.scale * (t * c + t - 1).scatter(1, at, a)
+
+
+class _QueueIds(collections.abc.Set):
+    """The set of labels other than -1 in a snapshot of ``SST_Prototype.labels`` (a device clone taken at call time).  It
+    reads the snapshot on first use, so the forward pass that returns it waits for nothing on the host."""
+
+    def __init__(self, snapshot):
+        self._snapshot, self._ids = snapshot, None
+
+    def _set(self):
+        if self._ids is None:
+            self._ids = frozenset(v for v in self._snapshot.cpu().tolist() if v != -1)
+            self._snapshot = None
+        return self._ids
+
+    def __contains__(self, item):
+        return item in self._set()
+
+    def __iter__(self):
+        return iter(self._set())
+
+    def __len__(self):
+        return len(self._set())
+
+    def __repr__(self):
+        return "_QueueIds(%r)" % (set(self._set()),)
+
+
+class SST_Prototype(nn.Module):
+    """SST_Prototype, "Semi-Siamese Training for Shallow Face Learning" (reference head/metrics.py:638-708): HIP kernels on
+    device tensors, plain PyTorch on the host.
+
+    The head has no parameter: its class matrix is the buffer ``queue`` [feat_dim, queue_size] of normalised gallery
+    embeddings, the only state-dict key.  ``forward(p1, g2, p2, g1, cur_ids)`` takes two views of B identities embedded by
+    the probe network (p) and the gallery network (g), normalises all four, detaches the gallery rows, and returns
+    ``(output1, output2, label, id_set)``: ``output1 = scale * add_margin(p1 . queue')`` with ``queue'`` the queue whose
+    columns [index, index + B) hold g2's rows, ``output2`` the same of p2 and g1, ``label = arange(B) + index``.  Then one
+    ``random.random()`` draw decides which gallery view the queue keeps in that window (above 0.5: g1), ``cur_ids`` go into
+    the label list there and ``index`` moves on by B, modulo queue_size -- in every mode, eval and ``no_grad`` included.
+    ``add_margin`` clamps to [-1, 1] and changes the label column: ``c - margin`` for ``'am_softmax'``, ``c cos(margin) -
+    sqrt(1 - c^2) sin(margin)`` for ``'arc_softmax'`` (no threshold fallback), nothing for any other ``loss_type``.
+
+    On the device ``queue`` is the data gradient's GEMM operand as it stands and ``queue_t`` [queue_size, feat_dim], a
+    non-persistent buffer rebuilt after ``load_state_dict`` and ``.to()``, the cosine GEMM's; ``labels`` is a non-persistent
+    int64 buffer and ``label_list`` a property that reads it on demand.  A step writes B columns of each and nothing else;
+    see ``frhip.functional.sst_forward``.  ``queue_state()`` / ``load_queue_state()`` carry ``index`` and the labels for a
+    driver's state file.  Limits: see the module docstring."""
+
+    def __init__(self, feat_dim=512, queue_size=16384, scale=30.0, loss_type='softmax', margin=0.0):
+        super().__init__()
+        self.queue_size = queue_size
+        self.feat_dim = feat_dim
+        self.scale = scale
+        self.margin = margin
+        self.loss_type = loss_type
+        queue = torch.rand(feat_dim, queue_size).uniform_(-1, 1).renorm_(2, 1, 1e-5).mul_(1e5)
+        self.register_buffer('queue', F.normalize(queue, p=2, dim=0))
+        self.register_buffer('queue_t', self.queue.t().contiguous(), persistent=False)
+        self.register_buffer('labels', torch.full((queue_size,), -1, dtype=torch.int64), persistent=False)
+        self.index = 0
+        self._generation = 0  # forward calls so far: a backward call behind a later forward call raises
+        self._t_of = None  # (data_ptr, version) of the queue that queue_t was built from
+
+    # -- the queue in both layouts
+
+    def _queue_key(self):
+        return (self.queue.data_ptr(), self.queue._version, self.queue.device, self.queue.dtype)
+
+    def _sync_queue_t(self):
+        """``queue_t`` again from ``queue`` where the latter was replaced or written by anyone but the enqueue kernel
+        (``load_state_dict``, ``.to()``, an assignment): the kernel writes through pointers and moves no version."""
+        if self._t_of != self._queue_key() or self.queue_t.device != self.queue.device:
+            if not self.queue.is_contiguous():
+                self.queue = self.queue.contiguous()
+            self.queue_t = self.queue.t().contiguous()
+            self._t_of = self._queue_key()
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        self._t_of = None
+        return out
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        super()._load_from_state_dict(*args, **kwargs)
+        self._t_of = None
+
+    # -- the label list
+
+    @property
+    def label_list(self):
+        return self.labels.cpu().tolist()
+
+    def get_id_set(self):
+        return set(v for v in self.label_list if v != -1)
+
+    def queue_state(self):
+        """(index, labels as a host int64 tensor): what a driver's state file keeps besides the state dict."""
+        return self.index, self.labels.detach().cpu().clone()
+
+    def load_queue_state(self, index, labels):
+        labels = torch.as_tensor(labels, dtype=torch.int64)
+        if labels.shape != self.labels.shape or not 0 <= int(index) < self.queue_size:
+            raise ValueError("SST_Prototype.load_queue_state: index in [0, %d) and %d labels are required"
+                             % (self.queue_size, self.queue_size))
+        self.labels.copy_(labels)
+        self.index = int(index)
+
+    # -- the reference's arithmetic
+
+    def add_margin(self, cos_theta, label):
+        cos_theta = cos_theta.clamp(-1, 1)
+        at = label.view(-1, 1)
+        if self.loss_type == 'am_softmax':
+            return cos_theta.scatter(1, at, cos_theta.gather(1, at) - self.margin)
+        if self.loss_type == 'arc_softmax':
+            gt = cos_theta.gather(1, at)
+            sin_theta = torch.sqrt(1.0 - torch.pow(gt, 2))
+            return cos_theta.scatter(1, at, gt * math.cos(self.margin) - sin_theta * math.sin(self.margin))
+        return cos_theta
+
+    def compute_theta(self, p, g, label):
+        i, B = self.index, p.shape[0]
+        queue = torch.cat([self.queue[:, :i], g.transpose(0, 1), self.queue[:, i + B:]], 1)
+        return self.add_margin(torch.mm(p, queue.detach()), label)
+
+    def forward(self, p1, g2, p2, g1, cur_ids):
+        B = p1.shape[0]
+        if self.index + B > self.queue_size:  # the reference raises at its slice assignment, after it has drawn nothing
+            raise RuntimeError("SST_Prototype: the window [%d, %d) runs past the queue's %d columns; queue_size must be a "
+                               "multiple of the batch size" % (self.index, self.index + B, self.queue_size))
+        if p1.is_cuda:
+            return self._forward_device(p1, g2, p2, g1, cur_ids)
+        queue = self.queue
+        p1, g2, p2, g1 = F.normalize(p1), F.normalize(g2).detach(), F.normalize(p2), F.normalize(g1).detach()
+        label = torch.arange(B, dtype=torch.int64) + self.index
+        output1 = self.compute_theta(p1, g2, label) * self.scale
+        output2 = self.compute_theta(p2, g1, label) * self.scale
+        g = g1 if random.random() > 0.5 else g2
+        ids = torch.as_tensor(cur_ids, dtype=torch.int64).reshape(-1)[:B]
+        with torch.no_grad():
+            self.queue = torch.cat([queue[:, :self.index], g.transpose(0, 1).to(queue.dtype), queue[:, self.index + B:]], 1)
+            self.labels[self.index:self.index + B] = ids.to(self.labels.device)
+        self.index = (self.index + B) % self.queue_size
+        self._generation += 1
+        return output1, output2, label, self.get_id_set()
+
+    def _forward_device(self, p1, g2, p2, g1, cur_ids):
+        if self.queue_size % 32:
+            raise NotImplementedError("SST_Prototype on the HIP path needs queue_size %% 32 == 0 (the GEMM's K step), got %d; "
+                                      "the host path serves any size" % self.queue_size)
+        dev = p1.device
+        _beside(self, self.queue, p1)
+        if self.queue.dtype != torch.float32:
+            raise NotImplementedError("SST_Prototype on the HIP path computes in fp32")
+        self._sync_queue_t()
+        B = p1.shape[0]
+        ids = torch.as_tensor(cur_ids, dtype=torch.int64).reshape(-1)[:B].to(dev).contiguous()
+        label = torch.arange(self.index, self.index + B, dtype=torch.int64, device=dev)
+        take_g1 = random.random() > 0.5
+        kind, p0, p1m = FRF.sst_margin(self.loss_type, self.margin)
+        self._generation += 1
+        output1, output2 = FRF.SSTHeadFn.apply(torch.cat([p1, p2]), torch.cat([g2, g1]).detach(), ids, self.queue,
+                                               self.queue_t, self.labels, self.index, take_g1, kind, p0, p1m, self.scale,
+                                               self)
+        self.index = (self.index + B) % self.queue_size
+        return output1, output2, label, _QueueIds(self.labels.clone())
