@@ -917,6 +917,19 @@ typedef struct FrSgdTensor {
 int fr_sgd_chunk_elems(void);
 int fr_sgd_step(const FrSgdTensor* table_dev, const int32_t* chunks_dev, int nchunks, float lr, float momentum,
                 void* stream);
+/* The same update on the rows idx[0 .. n_s) of ONE dense fp32 parameter p [n][D] and its momentum buffer buf [n][D], with
+ * the gradient given as the gathered rows g_rows [n_s][D] (contiguous) -- the lazy update of Partial-FC v1 for the sampled
+ * class-sharded head (frhip/sharded_head.py, sparse_update):
+ *   r = idx[j], j < n_s:   d = g_rows[j] + wd*p[r] ; buf[r] = momentum*buf[r] + d ; p[r] -= lr*buf[r]
+ * element for element the expression of fr_sgd_step with the same roundings (one device function serves both kernels).
+ * Rows not in idx are neither read nor written: no weight decay and no momentum step while a row is unselected.  idx is
+ * ascending and distinct with every entry in [0, n), as fr_class_sample leaves it (n does not cross the ABI and nothing
+ * checks the entries): one writer per element, plain stores, no atomics.  D >= 1 (D = 1: a bias); 16-byte accesses where
+ * D % 4 == 0 and p, buf and g_rows are 16-byte aligned, 4-byte accesses otherwise.  One launch whose grid follows n_s * D,
+ * 20 bytes of memory traffic per element of the selected rows.  n_s <= 0 launches nothing and returns 0; with n_s > 0 all
+ * four pointers are required. */
+int fr_sgd_rows(float* p, float* buf, const float* g_rows, const int32_t* idx, int n_s, int D, float lr, float momentum,
+                float wd, void* stream);
 
 /* ---- multi-tensor Adam (torch.optim.Adam defaults: no weight decay, no amsgrad; the reference's OPTIMIZER_NAME ==
  *      'Adam' branch, train.py:197-198), same table / chunk scheme as fr_sgd_step:

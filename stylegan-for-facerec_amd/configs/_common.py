@@ -26,7 +26,10 @@ def stage3(exp_name, **overrides):
         # optional, read by train.py when present: SHARDED_HEAD=True (the class-sharded head, frhip/sharded_head.py) and
         # with it SHARDED_HEAD_SAMPLE_RATE in (0, 1], default 1.0: below 1 a training step runs on that fraction of each
         # rank's classes, the classes of the batch among them, drawn from (SEED, batch counter); ArcFace, CosFace,
-        # SphereFace and Softmax only, and the rate must keep at least min(classes per rank, global batch) classes
+        # SphereFace and Softmax only, and the rate must keep at least min(classes per rank, global batch) classes.
+        # SHARDED_HEAD_SPARSE_UPDATE=True (default False; needs SHARDED_HEAD=True, a rate below 1 and OPTIMIZER_NAME 'SGD'):
+        # the optimizer updates only the sampled rows of the head and of its momentum; unselected rows see no weight decay
+        # and no momentum step (the lazy update of Partial-FC v1), and no gradient of the head's full shape is formed
         ENCODER_CHECKPOINT=None,
         ENCODER_AVG_IMAGE="<an arbitrary 112x112 image here>",
         ENCODER_INPUT_SIZE=112,

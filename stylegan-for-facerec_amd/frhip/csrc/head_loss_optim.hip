@@ -1182,6 +1182,16 @@ __global__ __launch_bounds__(256) void shard_rank_rows_kernel(const float* __res
 
 // ------------------------------------------------------------------------------------------ SGD
 constexpr int SGD_CHUNK = 4096;
+
+// One element of the update, shared by the dense and the row-sparse kernel so that both round alike: returns the new
+// parameter and leaves the new momentum in *bv.
+__device__ __forceinline__ float sgd_element(float pv, float g, float* bv, float wd, float momentum, float lr) {
+  const float d = fmaf(wd, pv, g);
+  const float b = fmaf(momentum, *bv, d);
+  *bv = b;
+  return pv - lr * b;
+}
+
 __global__ __launch_bounds__(256) void sgd_kernel(const FrSgdTensor* __restrict__ table,
                                                   const int2* __restrict__ chunks, float lr, float momentum) {
   const int2 ch = chunks[blockIdx.x];
@@ -1190,11 +1200,44 @@ __global__ __launch_bounds__(256) void sgd_kernel(const FrSgdTensor* __restrict_
   long long end = base + SGD_CHUNK;
   if (end > t.n) end = t.n;
   for (long long i = base + threadIdx.x; i < end; i += 256) {
-    const float pv = t.p[i];
-    const float d = fmaf(t.wd, pv, t.g[i]);
-    const float b = fmaf(momentum, t.buf[i], d);
+    const float pv = t.p[i], g = t.g[i];
+    float b = t.buf[i];
+    const float pn = sgd_element(pv, g, &b, t.wd, momentum, lr);
     t.buf[i] = b;
-    t.p[i] = pv - lr * b;
+    t.p[i] = pn;
+  }
+}
+
+// The lazy update of Partial-FC v1 on the rows idx[0 .. n_s) of a dense [n][D] parameter and its momentum buffer: element
+// (idx[j], d) takes sgd_element with the gradient g_rows[j][d]; no other row is read or written.  idx is ascending and
+// distinct, so every element has one writer: plain stores, no atomics.  Flat over the n_s * D / V elements of the selected
+// rows as cs_gather_kernel (class_sample.hip); V floats per thread and access (4: D % 4 == 0 and 16-byte aligned pointers).
+// 20 bytes of HBM traffic per element (p, buf, g read; p, buf written), whatever n is.
+template <int V>
+__global__ __launch_bounds__(256) void sgd_rows_kernel(float* __restrict__ p, float* __restrict__ buf,
+                                                       const float* __restrict__ g_rows, const int32_t* __restrict__ idx,
+                                                       long long total, int dv, float lr, float momentum, float wd) {
+  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+    const long long j = e / dv;
+    const int q = (int)(e - j * dv);
+    const long long at = ((long long)idx[j] * dv + q) * V;
+    if (V == 4) {
+      const float4 pv = *reinterpret_cast<const float4*>(p + at);
+      const float4 gv = *reinterpret_cast<const float4*>(g_rows + e * 4);
+      float4 bv = *reinterpret_cast<const float4*>(buf + at);
+      float4 o;
+      o.x = sgd_element(pv.x, gv.x, &bv.x, wd, momentum, lr);
+      o.y = sgd_element(pv.y, gv.y, &bv.y, wd, momentum, lr);
+      o.z = sgd_element(pv.z, gv.z, &bv.z, wd, momentum, lr);
+      o.w = sgd_element(pv.w, gv.w, &bv.w, wd, momentum, lr);
+      *reinterpret_cast<float4*>(buf + at) = bv;
+      *reinterpret_cast<float4*>(p + at) = o;
+    } else {
+      float b = buf[at];
+      const float o = sgd_element(p[at], g_rows[e], &b, wd, momentum, lr);
+      buf[at] = b;
+      p[at] = o;
+    }
   }
 }
 
@@ -1625,6 +1668,24 @@ extern "C" int fr_sgd_step(const FrSgdTensor* table_dev, const int32_t* chunks_d
   if (!table_dev || !chunks_dev) FR_UNSUPPORTED("fr_sgd_step: table_dev and chunks_dev are required when nchunks > 0");
   hipLaunchKernelGGL(sgd_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, table_dev,
                      (const int2*)chunks_dev, lr, momentum);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_sgd_rows(float* p, float* buf, const float* g_rows, const int32_t* idx, int n_s, int D, float lr,
+                           float momentum, float wd, void* stream) {
+  if (n_s <= 0) return 0;
+  if (!p || !buf || !g_rows || !idx) FR_UNSUPPORTED("fr_sgd_rows: p, buf, g_rows and idx are required when n_s > 0");
+  if (D < 1) FR_UNSUPPORTED("fr_sgd_rows: D >= 1");
+  hipStream_t st = (hipStream_t)stream;
+  const bool vec = D % 4 == 0 && (uintptr_t)p % 16 == 0 && (uintptr_t)buf % 16 == 0 && (uintptr_t)g_rows % 16 == 0;
+  const int dv = vec ? D / 4 : D;
+  const long long total = (long long)n_s * dv;  // the grid follows the selected rows, not the parameter
+  const long long want = (total + 255) / 256;
+  const dim3 grid((unsigned)(want > 4096 ? 4096 : want));  // 16 workgroups per CU, grid-stride beyond
+  if (vec)
+    hipLaunchKernelGGL(sgd_rows_kernel<4>, grid, dim3(256), 0, st, p, buf, g_rows, idx, total, dv, lr, momentum, wd);
+  else
+    hipLaunchKernelGGL(sgd_rows_kernel<1>, grid, dim3(256), 0, st, p, buf, g_rows, idx, total, dv, lr, momentum, wd);
   FR_LAUNCH_CHECK();
 }
 

@@ -5,6 +5,10 @@ Same constructor shape as ``torch.optim.SGD`` (param groups with per-group ``wei
 update:  d = g + wd*p ; buf = momentum*buf + d ; p -= lr*buf, with buf starting at zero so
 the first step yields buf = d.  Parameters whose ``.grad`` is None (frozen body, train.py:263-268) are
 skipped entirely.  ``param_groups`` stay plain dicts so warm_up_lr / schedule_lr work unchanged.
+
+A parameter that carries ``_frhip_row_grad = (idx, rows)`` (the sampled class-sharded head with ``sparse_update=True``,
+frhip/sharded_head.py) takes the same update on the rows ``idx`` alone, in one launch of its own (fr_sgd_rows): the lazy
+update of Partial-FC v1, where an unselected row sees no weight decay and no momentum step.  ``SGD`` only; ``Adam`` refuses.
 """
 import ctypes
 
@@ -38,6 +42,8 @@ class SGD(torch.optim.Optimizer):
         for group in self.param_groups:
             for p in group["params"]:
                 g = p.grad
+                if getattr(p, "_frhip_row_grad", None) is not None:  # a row gradient nobody consumed (sharded_head.py)
+                    p._frhip_row_grad = None
                 if g is None:
                     continue
                 if set_to_none:
@@ -108,6 +114,13 @@ class SGD(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
+        # parameters that carry a row gradient (sharded_head.py, sparse_update): their .grad is None, so the dense tables
+        # leave them out and the signature does not move with them
+        rows = _row_grad_params(self.param_groups)
+        for _group, p in rows:
+            if p.grad is not None:
+                raise _lib.FrhipError("frhip.optim.SGD: a parameter carries a row gradient (sparse_update) and a dense "
+                                      ".grad; the two cannot be combined -- set the dense one to None")
         sig = self._signature()
         if sig != self._sig:
             self._build()
@@ -120,7 +133,35 @@ class SGD(torch.optim.Optimizer):
             table = ctypes.cast(ctypes.c_void_p(raw.data_ptr()), ctypes.POINTER(_lib.FrSgdTensor))  # device array
             ops.Launch("fr_sgd_step", [table, ctypes.c_void_p(ch.data_ptr()), n, float(group["lr"]),
                                        float(group["momentum"]), st])()
+        for group, p in rows:
+            self._step_rows(group, p, st)
         return loss
+
+    def _step_rows(self, group, p, st):
+        """The lazy update of Partial-FC v1 on a parameter that carries ``_frhip_row_grad = (idx, rows)`` (a sampled
+        ``ShardedMarginLoss(sparse_update=True)``): d = rows[j] + wd p[r]; buf[r] = momentum buf[r] + d; p[r] -= lr buf[r]
+        on the rows r = idx[j] of the parameter and of its momentum buffer in one launch (fr_sgd_rows: the expression of the
+        dense step, the same roundings).  The other rows keep their bits: no weight decay, no momentum step.  The momentum
+        buffer is the dense tensor the dense path keeps, so state dicts do not change."""
+        if group.get("dampening", 0) != 0 or group.get("nesterov", False) or group.get("maximize", False):
+            raise NotImplementedError("frhip.optim.SGD: dampening / nesterov / maximize are not implemented")
+        idx, rows = p._frhip_row_grad
+        if not (p.is_cuda and p.is_contiguous() and p.dtype == torch.float32 and p.dim() in (1, 2)):
+            raise _lib.FrhipError("frhip.optim.SGD: a row gradient needs a contiguous float32 [n, D] or [n] ROCm parameter")
+        D = p.shape[1] if p.dim() == 2 else 1
+        if (idx.dtype != torch.int32 or idx.dim() != 1 or idx.shape[0] > p.shape[0] or rows.dtype != torch.float32
+                or tuple(rows.shape) != (idx.shape[0],) + tuple(p.shape[1:])):
+            raise _lib.FrhipError("frhip.optim.SGD: row gradient of shape %s with %s indices of %s for a parameter of shape %s"
+                                  % (tuple(rows.shape), tuple(idx.shape), idx.dtype, tuple(p.shape)))
+        state = self.state[p]
+        buf = state.get("momentum_buffer")
+        if buf is None:  # first use; torch.optim.SGD writes None before its first step
+            buf = state["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        if buf.shape != p.shape or not buf.is_contiguous():
+            raise _lib.FrhipError("frhip.optim.SGD: param / momentum buffer must share one dense layout")
+        ops.call("fr_sgd_rows", p, buf, rows.contiguous(), idx.contiguous(), idx.shape[0], D, float(group["lr"]),
+                 float(group["momentum"]), float(group["weight_decay"]), st)()
+        p._frhip_row_grad = None
 
 
 class Adam(torch.optim.Optimizer):
@@ -190,6 +231,10 @@ class Adam(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
+        for _group, _p in _row_grad_params(self.param_groups):
+            raise NotImplementedError("frhip.optim.Adam: a parameter carries a row gradient (ShardedMarginLoss with "
+                                      "sparse_update=True); the row-sparse update is built for frhip.optim.SGD only -- run "
+                                      "Adam with sparse_update=False")
         sig = self._signature()
         if sig != self._sig:
             self._build()
@@ -270,6 +315,11 @@ class ParamEMA(object):
         table = ctypes.cast(ctypes.c_void_p(raw.data_ptr()), ctypes.POINTER(_lib.FrEmaTensor))  # device array
         ops.Launch("fr_ema_step", [table, ctypes.c_void_p(ch.data_ptr()), n, float(a), float(b),
                                    ops.current_stream_ptr()])()
+
+
+def _row_grad_params(param_groups):
+    """[(group, parameter)] of the parameters that carry a pending ``_frhip_row_grad`` (frhip/sharded_head.py)."""
+    return [(g, p) for g in param_groups for p in g["params"] if getattr(p, "_frhip_row_grad", None) is not None]
 
 
 def _dense_same(a, b):

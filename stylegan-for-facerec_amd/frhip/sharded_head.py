@@ -49,6 +49,16 @@ gradient, so weight decay and momentum still act on it, as under torch.optim.SGD
 denominator, the loss and prec@1/@5 then run over the selected classes of all ranks; prec@k is an upper estimate (the label
 competes with fewer classes).  Row-sharded heads only (ArcFace, CosFace, SphereFace, Softmax); eval mode runs all classes.
 
+Row-sparse update (``sparse_update=True``, off by default; the lazy update of Partial-FC v1): in a sampled training step
+nothing of the shard's shape is formed after the logits either.  The backward pass skips the scatter, returns no gradient
+for the weight (and the bias) and leaves ``param._frhip_row_grad = (idx, rows)`` on the parameter: the [n_s, D] output of
+the weight-gradient GEMM (the [n_s] column sums for the bias) and the class indices.  ``frhip.optim.SGD.step`` applies
+d = rows[j] + wd p[r]; buf[r] = momentum buf[r] + d; p[r] -= lr buf[r] to the rows r = idx[j] in one launch (fr_sgd_rows, the
+expression and roundings of the dense step) and clears the attribute.  Rows that were not selected keep their weight and
+momentum bits: they see NO weight decay and NO momentum step while unselected, where the dense path above decays them and
+moves them along their momentum every step.  That difference is why this is an option; with weight decay 0 and momentum 0
+the two coincide bit for bit.  Eval mode, rate 1.0 and a rate whose n_s is the whole shard run the dense path unchanged.
+
 The device arithmetic sits behind ``HipKernels`` (the only implementation in the package: HIP through the C ABI; no
 CPU fallback).  tests/ substitutes an oracle-backed stand-in to run the collective choreography at world_size 2 on
 ``gloo``.
@@ -285,6 +295,19 @@ class HipKernels(object):
         return gx
 
 
+def _leave_row_grad(param, idx, rows):
+    """``param._frhip_row_grad = (idx, rows)``: the gradient of the rows ``idx`` of ``param`` and nothing else, for
+    ``frhip.optim.SGD.step`` to consume.  Row gradients of two backward passes belong to different index sets and cannot be
+    added, so a pending one is an error."""
+    if param is None or rows is None:
+        return
+    if getattr(param, "_frhip_row_grad", None) is not None:
+        raise RuntimeError("ShardedMarginLoss(sparse_update=True): a second backward pass before the optimizer consumed the "
+                           "row gradient of the first; row gradients of different class samples cannot be added -- call "
+                           "optimizer.step() (or zero_grad()) after every backward pass")
+    param._frhip_row_grad = (idx, rows)
+
+
 class ShardedHeadLossFn(torch.autograd.Function):
     """(loss, prec@1, prec@5) of the global batch from this rank's features, labels and weight shard."""
 
@@ -297,7 +320,7 @@ class ShardedHeadLossFn(torch.autograd.Function):
         lab_all = C.all_gather(label.contiguous().long())
         rows = x_all.shape[0]
         lab_loc = localize_labels(lab_all, head.lo, head.hi)
-        ctx.sample = None
+        ctx.sample = ctx.row_idx = None
         if head.step_salt is not None:  # class sampling: from here on the shard is its n_s selected classes
             n = head.hi - head.lo
             idx, inv, lab_loc = K.sample_classes(lab_loc, n, head.n_s, head.step_salt, head.lo)
@@ -305,6 +328,8 @@ class ShardedHeadLossFn(torch.autograd.Function):
             if bias is not None:
                 bias = K.gather_rows(bias.detach(), idx)
             ctx.sample = (inv, n)
+            if head.sparse_update:  # row-sparse update: ``backward`` hands the optimizer the gathered rows and idx
+                ctx.row_idx = idx
         if head.kind in (FRF.ARCFACE, FRF.COSFACE):
             logits, saved, cfg = K.logits(x_all, w.detach(), lab_loc, head.kind, head.s, head.m, head.easy_margin)
         elif head.kind == FRF.SPHEREFACE:
@@ -341,7 +366,11 @@ class ShardedHeadLossFn(torch.autograd.Function):
                                          ctx.needs_input_grad[1] or ctx.needs_input_grad[4])
         else:
             G_all, gw, r_part = K.ext_bwd(ctx.saved, ctx.cfg, grad, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
-        if ctx.sample is not None:  # back to the shard's shape: the selected rows, exact zeros elsewhere
+        if ctx.row_idx is not None:  # row-sparse update: the rows stay gathered, no [n, D] gradient is ever formed
+            _leave_row_grad(head.weight, ctx.row_idx, gw)
+            _leave_row_grad(getattr(head, "bias", None), ctx.row_idx, gb)
+            gw = gb = None
+        elif ctx.sample is not None:  # back to the shard's shape: the selected rows, exact zeros elsewhere
             inv, n = ctx.sample
             gw = None if gw is None else K.scatter_rows(gw, inv, n)
             gb = None if gb is None else K.scatter_rows(gb, inv, n)
@@ -398,11 +427,19 @@ class ShardedMarginLoss(nn.Module):
     and prec@1 / prec@5 run over the selected classes of all ranks, which makes prec@k an upper estimate.  ``sample_step``
     is a host int that counts the training forwards; set it to the step counter when a run is resumed.  In eval mode, and
     at rate 1.0, all classes run on the unsampled path.
+
+    ``sparse_update=True`` (row-sharded heads; acts in a sampled training step only): the lazy update of Partial-FC v1.
+    ``backward`` forms no gradient of the shard's shape: ``weight.grad`` (and ``bias.grad``) stay None and the parameter
+    carries ``_frhip_row_grad = (idx [n_s] int32, rows [n_s, in_features])`` (``rows`` [n_s] for the bias) until
+    ``frhip.optim.SGD.step()`` has applied it to exactly those rows of the parameter and of its momentum buffer, or
+    ``zero_grad()`` has dropped it.  Unselected rows keep their weight and momentum bits -- no weight decay and no momentum
+    step while unselected, unlike the default path.  A second ``backward`` before the optimizer consumed the first raises
+    RuntimeError; ``frhip.optim.Adam`` refuses a row gradient.
     """
 
     def __init__(self, in_features, out_features, head="ArcFace", s=None, m=None, easy_margin=False, gamma=2.0,
                  group=None, full_weight=None, average_over_ranks=True, kernels=None, loss="Focal", full_bias=None,
-                 sample_rate=1.0, sample_seed=0):
+                 sample_rate=1.0, sample_seed=0, sparse_update=False):
         super().__init__()
         if not 0.0 < sample_rate <= 1.0:
             raise ValueError("ShardedMarginLoss: sample_rate must lie in (0, 1], got %r" % (sample_rate,))
@@ -410,6 +447,11 @@ class ShardedMarginLoss(nn.Module):
             raise ValueError("ShardedMarginLoss: sample_rate < 1 with head %s: its kernel is [D, N], sharded by columns, and "
                              "the column gather is not built; class sampling serves ArcFace, CosFace, SphereFace and "
                              "Softmax" % head)
+        if sparse_update and CLASS_DIM.get(head) == 1:
+            raise ValueError("ShardedMarginLoss: sparse_update=True with head %s: its kernel is [D, N], sharded by columns, "
+                             "and class sampling does not serve it; the row-sparse update serves ArcFace, CosFace, "
+                             "SphereFace and Softmax" % head)
+        self.sparse_update = bool(sparse_update)
         if head not in KINDS and head not in LINEAR_KINDS:
             raise ValueError("ShardedMarginLoss: head must be one of %s, got %r"
                              % (", ".join(list(KINDS) + list(LINEAR_KINDS)), head))

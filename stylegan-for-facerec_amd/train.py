@@ -168,6 +168,17 @@ def check_head_config(cfg):
         if name in SAMPLED_NOT_SERVED:
             raise NotImplementedError("SHARDED_HEAD_SAMPLE_RATE=%r with HEAD_NAME '%s': %s; run it with "
                                       "SHARDED_HEAD_SAMPLE_RATE=1.0" % (rate, name, SAMPLED_NOT_SERVED[name]))
+    if cfg.get("SHARDED_HEAD_SPARSE_UPDATE", False):  # the row-sparse update of the sampled head (frhip/optim.py)
+        if not cfg.get("SHARDED_HEAD", False):
+            raise NotImplementedError("SHARDED_HEAD_SPARSE_UPDATE=True needs SHARDED_HEAD=True: the row-sparse update "
+                                      "belongs to the class-sharded head")
+        if rate == 1.0:
+            raise NotImplementedError("SHARDED_HEAD_SPARSE_UPDATE=True with SHARDED_HEAD_SAMPLE_RATE=1.0: every class "
+                                      "runs in every step, so there are no rows to leave out; set a rate below 1 or "
+                                      "SHARDED_HEAD_SPARSE_UPDATE=False")
+        if cfg.get("OPTIMIZER_NAME", "SGD") != "SGD":
+            raise NotImplementedError("SHARDED_HEAD_SPARSE_UPDATE=True with OPTIMIZER_NAME %r: the row-sparse update is "
+                                      "built for 'SGD' only" % (cfg.get("OPTIMIZER_NAME"),))
 
 
 def main():
@@ -290,7 +301,8 @@ def main():
         crit = ShardedMarginLoss.from_head(head, gamma=loss_fn.gamma if loss_fn is not None else 2.0,
                                            loss=cfg["LOSS_NAME"],  # takes the resumed weight and t along
                                            sample_rate=cfg.get("SHARDED_HEAD_SAMPLE_RATE", 1.0),
-                                           sample_seed=cfg["SEED"]).to(device)
+                                           sample_seed=cfg["SEED"],
+                                           sparse_update=cfg.get("SHARDED_HEAD_SPARSE_UPDATE", False)).to(device)
         optimizer = make_optimizer(list(crit.parameters()))  # the weight shard; the Softmax head's bias shard behind it
     # exposes .module like nn.DataParallel; all-reduce only when world > 1 (a weight shard is complete on its owner)
     BACKBONE = DataParallel(backbone, None if crit is not None else head)
