@@ -966,6 +966,57 @@ typedef struct FrEmaTensor {
 int fr_ema_chunk_elems(void);
 int fr_ema_step(const FrEmaTensor* table_dev, const int32_t* chunks_dev, int nchunks, float a, float b, void* stream);
 
+/* ---- device-side gradient guard: global L2 norm of a set of gradients, clip coefficient and non-finite step skip
+ *      (torch.nn.utils.clip_grad_norm_(parameters, max_norm), norm type 2, plus the skip GradScaler does on inf / NaN),
+ *      same table / chunk scheme as fr_sgd_step.  Two small launches before the optimizer step leave a control word on the
+ *      device; the *_ctl step entries read it.  Nothing crosses to the host and no gradient is written.
+ *
+ * fr_grad_sumsq: one workgroup of 256 threads per (tensor index, chunk index) pair; parts[c] is the sum of
+ * (double)g[i] * (double)g[i] over the L <= fr_sgd_chunk_elems() elements of chunk c, x[0 .. L), added in double in this
+ * order, which depends on L alone:
+ *   thread t (0 .. 255):  a[t] = ((x[t]^2 + x[t + 256]^2) + x[t + 512]^2) + ...   over t + 256 j < L, j ascending; no
+ *                         element: a[t] = +0.0   (a square of an fp32 value is exact in double, fused or not)
+ *   wave w (0 .. 3):      its 64 values v[0 .. 64) = a[64 w ..] fold in halves, v[l] += v[l + h] for l < h, h = 32, 16, 8,
+ *                         4, 2, 1 (the xor butterfly of wave_sum_d); the wave's sum is v[0]
+ *   parts[c] = ((s[0] + s[1]) + s[2]) + s[3]   over the four waves' sums.
+ * Every access to g is 4 bytes wide, so a tensor at any 4-byte offset is read inside [g, g + n) and in that order.  Plain
+ * stores, no atomics: bit-identical from run to run, whatever the grid and the order of the chunk list.  nchunks <= 0
+ * launches nothing and returns 0; with nchunks > 0 table_dev, chunks_dev and parts are required. */
+typedef struct FrGradTensor {
+  const float* g;
+  long long n;
+} FrGradTensor;
+int fr_grad_sumsq(const FrGradTensor* table_dev, const int32_t* chunks_dev, int nchunks, double* parts, void* stream);
+/* fr_grad_guard: ONE workgroup of 256 threads turns the partial sums into the control word ctl [4] (fp32, device):
+ *   total:   thread t adds parts[t], parts[t + 256], ... in ascending index order in double (no part: +0.0); the 256 values
+ *            are then summed by the tree of fr_grad_sumsq (halving folds per wave, the four waves in order).  The tree
+ *            depends on nparts alone.
+ *   ctl[0] = (float)sqrt(total)                           the global L2 norm (double square root, rounded once more to fp32)
+ *   ctl[1] = the clip coefficient, torch's expression with every operation rounded to fp32 on its own:
+ *            c = max_norm / (ctl[0] + 1e-6f);  ctl[1] = c > 1 ? 1 : c      -- a NaN passes through, an infinite norm gives 0;
+ *            max_norm <= 0 is "measure only": ctl[1] = 1 exactly
+ *   ctl[2] = the go flag: 0.0f when skip_nonfinite != 0 and total is not finite, else 1.0f
+ *   ctl[3] = 0
+ * skipped (int32 [2], device) may be NULL; otherwise thread 0 does skipped[0] += 1 when the go flag is 0 and skipped[1] += 1
+ * always, with plain loads and stores (calls on one stream are ordered).  nparts == 0 is allowed, parts may then be NULL:
+ * norm 0, coefficient 1 (or max_norm / 1e-6f clamped, which is 1 for every max_norm >= 1e-6f), go 1.  nparts < 0, a NaN
+ * max_norm, a missing ctl and missing parts with nparts > 0 are refused. */
+int fr_grad_guard(const double* parts, int nparts, float max_norm, int skip_nonfinite, float* ctl, int32_t* skipped,
+                  void* stream);
+/* The step entries under the control word.  ctl[2] == 0: every workgroup returns before it touches p, buf, m or v (the
+ * gradients are not read either).  Otherwise the update of the entry without _ctl, by the same device functions, on
+ *   g' = g * ctl[1]  when use_coef != 0 (a multiply of its own, rounded to fp32, never contracted into the wd * p FMA),
+ *   g' = g           when use_coef == 0;
+ * g is never written.  Bit for bit "scale the gradients in place in fp32, then fr_sgd_step / fr_adam_step"; with ctl =
+ * {x, 1, 1, 0} bit for bit the entry without _ctl.  fr_sgd_rows_ctl honours the go flag alone (the head is not clipped:
+ * the norm is the backbone's, frhip/optim.py).  ctl is required whenever the entry would launch. */
+int fr_sgd_step_ctl(const FrSgdTensor* table_dev, const int32_t* chunks_dev, int nchunks, float lr, float momentum,
+                    const float* ctl, int use_coef, void* stream);
+int fr_adam_step_ctl(const FrAdamTensor* table_dev, const int32_t* chunks_dev, int nchunks, float step_size, float w1,
+                     float beta2, float w2, float eps, float bc2_sqrt, const float* ctl, int use_coef, void* stream);
+int fr_sgd_rows_ctl(float* p, float* buf, const float* g_rows, const int32_t* idx, int n_s, int D, float lr, float momentum,
+                    float wd, const float* ctl, void* stream);
+
 /* out[r][c] = bias ? bias[c] : 0  (fp32 [rows][C]); seeds the split-K accumulation of Linear(25088,512) */
 int fr_fill_rows(float* out, const float* bias, long long rows, int C, void* stream);
 
@@ -996,7 +1047,7 @@ int fr_arm_stop_event(void* event);
 int fr_finish_stop_event(void* stream);
 /* sizeof() of the argument structs as compiled, for binding self-checks: 0 FrConvArgs, 1 FrWgradArgs,
  * 2 FrApplyArgs, 3 FrBnBwdArgs, 4 FrSgdTensor, 5 FrPackTensor, 6 FrAdamTensor, 7 FrBnEvalEntry, 8 FrBnFinArgs,
- * 9 FrEmaTensor */
+ * 9 FrEmaTensor, 10 FrGradTensor */
 int fr_struct_size(int which);
 const char* fr_last_error_string(void);
 

@@ -45,6 +45,9 @@ def stage3(exp_name, **overrides):
         NUM_EPOCH=100,
         WEIGHT_DECAY=2e-3,               # not applied to batch-norm parameters
         MOMENTUM=0.9,
+        GRAD_CLIP_NORM=None,             # a number > 0: clip the global L2 norm of the backbone's gradients to it every step
+        SKIP_NONFINITE_STEP=False,       # True: a step whose backbone gradients hold an inf or a NaN updates nothing
+                                         # (both on the device, frhip.optim.GradGuard; off: no launch is added)
         STAGES=np.arange(10, 125, 5) + 5,
         WARMUP=False,
         LAYER_DECAY=None,

@@ -87,6 +87,7 @@ FrAdamTensor = structs["FrAdamTensor"]
 FrBnEvalEntry = structs["FrBnEvalEntry"]
 FrBnFinArgs = structs["FrBnFinArgs"]
 FrEmaTensor = structs["FrEmaTensor"]
+FrGradTensor = structs["FrGradTensor"]
 
 # enums of the header
 FR_F32, FR_BF16 = 0, 1
@@ -118,7 +119,7 @@ lib = _load()
 def self_check():
     assert lib.fr_abi_version() == 7
     for i, s in enumerate((FrConvArgs, FrWgradArgs, FrApplyArgs, FrBnBwdArgs, FrSgdTensor, FrPackTensor, FrAdamTensor, FrBnEvalEntry,
-                           FrBnFinArgs, FrEmaTensor)):
+                           FrBnFinArgs, FrEmaTensor, FrGradTensor)):
         got = lib.fr_struct_size(i)
         if got != ctypes.sizeof(s):
             raise FrhipError("frhip: struct %s is %d bytes in libfrhip.so but %d in the ctypes binding"

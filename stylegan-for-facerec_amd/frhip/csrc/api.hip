@@ -27,6 +27,7 @@ extern "C" int fr_struct_size(int which) {
     case 7: return (int)sizeof(FrBnEvalEntry);
     case 8: return (int)sizeof(FrBnFinArgs);
     case 9: return (int)sizeof(FrEmaTensor);
+    case 10: return (int)sizeof(FrGradTensor);
   }
   return -1;
 }

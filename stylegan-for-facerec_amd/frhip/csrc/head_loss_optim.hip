@@ -1192,15 +1192,28 @@ __device__ __forceinline__ float sgd_element(float pv, float g, float* bv, float
   return pv - lr * b;
 }
 
-__global__ __launch_bounds__(256) void sgd_kernel(const FrSgdTensor* __restrict__ table,
-                                                  const int2* __restrict__ chunks, float lr, float momentum) {
+// The gradient an element's update takes under the guard's control word (fr_grad_guard): g * coef as a multiply of its own,
+// rounded to fp32 -- what scaling the gradient in place would have stored -- so that no compiler folds it into the FMA
+// that follows.
+__device__ __forceinline__ float guard_scaled(float g, float coef) {
+#pragma clang fp contract(off)
+  const float s = g * coef;
+  return s;
+}
+
+// One chunk of the dense step, shared by sgd_kernel and sgd_ctl_kernel so that both round alike.  SCALE is a compile-time
+// false in sgd_kernel, which therefore keeps the instructions it had.
+template <bool SCALE>
+__device__ __forceinline__ void sgd_chunk(const FrSgdTensor* __restrict__ table, const int2* __restrict__ chunks, float lr,
+                                          float momentum, float coef) {
   const int2 ch = chunks[blockIdx.x];
   const FrSgdTensor t = table[ch.x];
   const long long base = (long long)ch.y * SGD_CHUNK;
   long long end = base + SGD_CHUNK;
   if (end > t.n) end = t.n;
   for (long long i = base + threadIdx.x; i < end; i += 256) {
-    const float pv = t.p[i], g = t.g[i];
+    const float pv = t.p[i];
+    const float g = SCALE ? guard_scaled(t.g[i], coef) : t.g[i];
     float b = t.buf[i];
     const float pn = sgd_element(pv, g, &b, t.wd, momentum, lr);
     t.buf[i] = b;
@@ -1208,15 +1221,35 @@ __global__ __launch_bounds__(256) void sgd_kernel(const FrSgdTensor* __restrict_
   }
 }
 
+__global__ __launch_bounds__(256) void sgd_kernel(const FrSgdTensor* __restrict__ table,
+                                                  const int2* __restrict__ chunks, float lr, float momentum) {
+  sgd_chunk<false>(table, chunks, lr, momentum, 1.0f);
+}
+
+// fr_sgd_step_ctl: the go flag and the coefficient come from the control word; both are uniform over the grid.
+__global__ __launch_bounds__(256) void sgd_ctl_kernel(const FrSgdTensor* __restrict__ table,
+                                                      const int2* __restrict__ chunks, float lr, float momentum,
+                                                      const float* __restrict__ ctl, int use_coef) {
+  if (ctl[2] == 0.0f) return;
+  if (use_coef)
+    sgd_chunk<true>(table, chunks, lr, momentum, ctl[1]);
+  else
+    sgd_chunk<false>(table, chunks, lr, momentum, 1.0f);
+}
+
 // The lazy update of Partial-FC v1 on the rows idx[0 .. n_s) of a dense [n][D] parameter and its momentum buffer: element
 // (idx[j], d) takes sgd_element with the gradient g_rows[j][d]; no other row is read or written.  idx is ascending and
 // distinct, so every element has one writer: plain stores, no atomics.  Flat over the n_s * D / V elements of the selected
 // rows as cs_gather_kernel (class_sample.hip); V floats per thread and access (4: D % 4 == 0 and 16-byte aligned pointers).
 // 20 bytes of HBM traffic per element (p, buf, g read; p, buf written), whatever n is.
-template <int V>
+// CTL (fr_sgd_rows_ctl): the same rows under the go flag of the gradient guard's control word -- every workgroup returns
+// before it touches p or buf when ctl[2] == 0; the head's rows are not clipped.  Without CTL the argument is not read.
+template <int V, bool CTL>
 __global__ __launch_bounds__(256) void sgd_rows_kernel(float* __restrict__ p, float* __restrict__ buf,
                                                        const float* __restrict__ g_rows, const int32_t* __restrict__ idx,
-                                                       long long total, int dv, float lr, float momentum, float wd) {
+                                                       long long total, int dv, float lr, float momentum, float wd,
+                                                       const float* __restrict__ ctl) {
+  if (CTL && ctl[2] == 0.0f) return;
   for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
     const long long j = e / dv;
     const int q = (int)(e - j * dv);
@@ -1247,9 +1280,11 @@ __global__ __launch_bounds__(256) void sgd_rows_kernel(float* __restrict__ p, fl
 // OCML_BASIC_ROUNDED_OPERATIONS the __fmul_rn / __fadd_rn of the HIP headers are plain operators that the compiler may
 // still contract into an FMA, and __fsqrt_rn is the native square root, which is not correctly rounded (it was 1 ulp off in
 // about 1 element of 100; tests/test_gpu_loss_optim.py holds the kernel to the np.float32 restatement bit for bit).
-__global__ __launch_bounds__(256) void adam_kernel(const FrAdamTensor* __restrict__ table,
-                                                   const int2* __restrict__ chunks, float step_size, float w1,
-                                                   float beta2, float w2, float eps, float bc2_sqrt) {
+// One chunk, shared by adam_kernel and adam_ctl_kernel (SCALE: the gradient times the guard's coefficient first).
+template <bool SCALE>
+__device__ __forceinline__ void adam_chunk(const FrAdamTensor* __restrict__ table, const int2* __restrict__ chunks,
+                                           float step_size, float w1, float beta2, float w2, float eps, float bc2_sqrt,
+                                           float coef) {
 #pragma clang fp contract(off)
   const int2 ch = chunks[blockIdx.x];
   const FrAdamTensor t = table[ch.x];
@@ -1258,13 +1293,95 @@ __global__ __launch_bounds__(256) void adam_kernel(const FrAdamTensor* __restric
   if (end > t.n) end = t.n;
   const float neg_step = -step_size;
   for (long long i = base + threadIdx.x; i < end; i += 256) {
-    const float g = t.g[i], m0 = t.m[i];
+    const float g = SCALE ? guard_scaled(t.g[i], coef) : t.g[i];
+    const float m0 = t.m[i];
     const float m = m0 + w1 * (g - m0);
     const float v = t.v[i] * beta2 + (w2 * g) * g;
     t.m[i] = m;
     t.v[i] = v;
     const float denom = sqrtf(v) / bc2_sqrt + eps;
     t.p[i] = t.p[i] + (neg_step * m) / denom;  // addcdiv: self + (value * t1) / t2
+  }
+}
+
+__global__ __launch_bounds__(256) void adam_kernel(const FrAdamTensor* __restrict__ table,
+                                                   const int2* __restrict__ chunks, float step_size, float w1,
+                                                   float beta2, float w2, float eps, float bc2_sqrt) {
+  adam_chunk<false>(table, chunks, step_size, w1, beta2, w2, eps, bc2_sqrt, 1.0f);
+}
+
+__global__ __launch_bounds__(256) void adam_ctl_kernel(const FrAdamTensor* __restrict__ table,
+                                                       const int2* __restrict__ chunks, float step_size, float w1,
+                                                       float beta2, float w2, float eps, float bc2_sqrt,
+                                                       const float* __restrict__ ctl, int use_coef) {
+  if (ctl[2] == 0.0f) return;
+  if (use_coef)
+    adam_chunk<true>(table, chunks, step_size, w1, beta2, w2, eps, bc2_sqrt, ctl[1]);
+  else
+    adam_chunk<false>(table, chunks, step_size, w1, beta2, w2, eps, bc2_sqrt, 1.0f);
+}
+
+// ------------------------------------------------------------------------------------------ gradient guard
+// The sum of 256 threads' doubles in the fixed tree both guard kernels document (include/frhip.h): wave_sum_d's xor
+// butterfly -- lane 0 holds the halving folds v[l] += v[l + h], h = 32 .. 1 -- then the four waves' sums in wave order.
+// Valid in thread 0.
+__device__ __forceinline__ double guard_block_sum(double a, double* dred) {
+  block_put(dred, wave_sum_d(a));
+  return waves_sum<4>(dred);
+}
+
+// parts[chunk] = sum of (double)g^2 over the chunk.  Thread t takes the elements t, t + 256, ... of the chunk in ascending
+// order; 4-byte loads only, so the order and the bounds hold at any alignment.  A full chunk issues its 16 loads together.
+// 4 bytes of HBM traffic per element.
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const FrGradTensor* __restrict__ table,
+                                                         const int2* __restrict__ chunks, double* __restrict__ parts) {
+  __shared__ double dred[4];
+  const int2 ch = chunks[blockIdx.x];
+  const FrGradTensor t = table[ch.x];
+  const long long base = (long long)ch.y * SGD_CHUNK;
+  long long end = base + SGD_CHUNK;
+  if (end > t.n) end = t.n;
+  const float* __restrict__ g = t.g + base;
+  const int len = end > base ? (int)(end - base) : 0;
+  double a = 0.0;
+  if (len == SGD_CHUNK) {
+    float x[SGD_CHUNK / 256];
+#pragma unroll
+    for (int j = 0; j < SGD_CHUNK / 256; ++j) x[j] = g[j * 256 + threadIdx.x];
+#pragma unroll
+    for (int j = 0; j < SGD_CHUNK / 256; ++j) a += (double)x[j] * (double)x[j];
+  } else {
+    for (int i = threadIdx.x; i < len; i += 256) a += (double)g[i] * (double)g[i];
+  }
+  const double s = guard_block_sum(a, dred);
+  if (threadIdx.x == 0) parts[blockIdx.x] = s;
+}
+
+// One workgroup: total of the parts (thread t: parts[t], parts[t + 256], ... ascending, then the tree above), and thread 0
+// writes the control word and the counters.
+__global__ __launch_bounds__(256) void grad_guard_kernel(const double* __restrict__ parts, int nparts, float max_norm,
+                                                         int skip_nonfinite, float* __restrict__ ctl,
+                                                         int32_t* __restrict__ skipped) {
+#pragma clang fp contract(off)
+  __shared__ double dred[4];
+  double a = 0.0;
+  for (int i = threadIdx.x; i < nparts; i += 256) a += parts[i];
+  const double total = guard_block_sum(a, dred);
+  if (threadIdx.x != 0) return;
+  const float norm = (float)sqrt(total);
+  float coef = 1.0f;
+  if (max_norm > 0.0f) {
+    const float c = max_norm / (norm + 1e-6f);
+    coef = c > 1.0f ? 1.0f : c;
+  }
+  const bool go = !(skip_nonfinite && !isfinite(total));
+  ctl[0] = norm;
+  ctl[1] = coef;
+  ctl[2] = go ? 1.0f : 0.0f;
+  ctl[3] = 0.0f;
+  if (skipped) {
+    if (!go) skipped[0] = skipped[0] + 1;
+    skipped[1] = skipped[1] + 1;
   }
 }
 
@@ -1671,11 +1788,10 @@ extern "C" int fr_sgd_step(const FrSgdTensor* table_dev, const int32_t* chunks_d
   FR_LAUNCH_CHECK();
 }
 
-extern "C" int fr_sgd_rows(float* p, float* buf, const float* g_rows, const int32_t* idx, int n_s, int D, float lr,
-                           float momentum, float wd, void* stream) {
-  if (n_s <= 0) return 0;
-  if (!p || !buf || !g_rows || !idx) FR_UNSUPPORTED("fr_sgd_rows: p, buf, g_rows and idx are required when n_s > 0");
-  if (D < 1) FR_UNSUPPORTED("fr_sgd_rows: D >= 1");
+// The row-sparse step with or without the guard's control word: vector width and grid follow the selected rows.
+template <bool CTL>
+static int launch_sgd_rows(float* p, float* buf, const float* g_rows, const int32_t* idx, int n_s, int D, float lr,
+                           float momentum, float wd, const float* ctl, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const bool vec = D % 4 == 0 && (uintptr_t)p % 16 == 0 && (uintptr_t)buf % 16 == 0 && (uintptr_t)g_rows % 16 == 0;
   const int dv = vec ? D / 4 : D;
@@ -1683,10 +1799,71 @@ extern "C" int fr_sgd_rows(float* p, float* buf, const float* g_rows, const int3
   const long long want = (total + 255) / 256;
   const dim3 grid((unsigned)(want > 4096 ? 4096 : want));  // 16 workgroups per CU, grid-stride beyond
   if (vec)
-    hipLaunchKernelGGL(sgd_rows_kernel<4>, grid, dim3(256), 0, st, p, buf, g_rows, idx, total, dv, lr, momentum, wd);
+    hipLaunchKernelGGL((sgd_rows_kernel<4, CTL>), grid, dim3(256), 0, st, p, buf, g_rows, idx, total, dv, lr, momentum, wd,
+                       ctl);
   else
-    hipLaunchKernelGGL(sgd_rows_kernel<1>, grid, dim3(256), 0, st, p, buf, g_rows, idx, total, dv, lr, momentum, wd);
+    hipLaunchKernelGGL((sgd_rows_kernel<1, CTL>), grid, dim3(256), 0, st, p, buf, g_rows, idx, total, dv, lr, momentum, wd,
+                       ctl);
   FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_sgd_rows(float* p, float* buf, const float* g_rows, const int32_t* idx, int n_s, int D, float lr,
+                           float momentum, float wd, void* stream) {
+  if (n_s <= 0) return 0;
+  if (!p || !buf || !g_rows || !idx) FR_UNSUPPORTED("fr_sgd_rows: p, buf, g_rows and idx are required when n_s > 0");
+  if (D < 1) FR_UNSUPPORTED("fr_sgd_rows: D >= 1");
+  return launch_sgd_rows<false>(p, buf, g_rows, idx, n_s, D, lr, momentum, wd, nullptr, stream);
+}
+
+extern "C" int fr_grad_sumsq(const FrGradTensor* table_dev, const int32_t* chunks_dev, int nchunks, double* parts,
+                             void* stream) {
+  if (nchunks <= 0) return 0;
+  if (!table_dev || !chunks_dev || !parts)
+    FR_UNSUPPORTED("fr_grad_sumsq: table_dev, chunks_dev and parts are required when nchunks > 0");
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, table_dev,
+                     (const int2*)chunks_dev, parts);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_grad_guard(const double* parts, int nparts, float max_norm, int skip_nonfinite, float* ctl,
+                             int32_t* skipped, void* stream) {
+  if (nparts < 0) FR_UNSUPPORTED("fr_grad_guard: nparts >= 0");
+  if (nparts > 0 && !parts) FR_UNSUPPORTED("fr_grad_guard: parts is required when nparts > 0");
+  if (!ctl) FR_UNSUPPORTED("fr_grad_guard: ctl is required");
+  if (max_norm != max_norm) FR_UNSUPPORTED("fr_grad_guard: max_norm is NaN (max_norm <= 0 measures without clipping)");
+  hipLaunchKernelGGL(grad_guard_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, parts, nparts, max_norm,
+                     skip_nonfinite, ctl, skipped);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_sgd_step_ctl(const FrSgdTensor* table_dev, const int32_t* chunks_dev, int nchunks, float lr,
+                               float momentum, const float* ctl, int use_coef, void* stream) {
+  if (nchunks <= 0) return 0;
+  if (!table_dev || !chunks_dev || !ctl)
+    FR_UNSUPPORTED("fr_sgd_step_ctl: table_dev, chunks_dev and ctl are required when nchunks > 0");
+  hipLaunchKernelGGL(sgd_ctl_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, table_dev,
+                     (const int2*)chunks_dev, lr, momentum, ctl, use_coef);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_adam_step_ctl(const FrAdamTensor* table_dev, const int32_t* chunks_dev, int nchunks, float step_size,
+                                float w1, float beta2, float w2, float eps, float bc2_sqrt, const float* ctl,
+                                int use_coef, void* stream) {
+  if (nchunks <= 0) return 0;
+  if (!table_dev || !chunks_dev || !ctl)
+    FR_UNSUPPORTED("fr_adam_step_ctl: table_dev, chunks_dev and ctl are required when nchunks > 0");
+  hipLaunchKernelGGL(adam_ctl_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, table_dev,
+                     (const int2*)chunks_dev, step_size, w1, beta2, w2, eps, bc2_sqrt, ctl, use_coef);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_sgd_rows_ctl(float* p, float* buf, const float* g_rows, const int32_t* idx, int n_s, int D, float lr,
+                               float momentum, float wd, const float* ctl, void* stream) {
+  if (n_s <= 0) return 0;
+  if (!p || !buf || !g_rows || !idx || !ctl)
+    FR_UNSUPPORTED("fr_sgd_rows_ctl: p, buf, g_rows, idx and ctl are required when n_s > 0");
+  if (D < 1) FR_UNSUPPORTED("fr_sgd_rows_ctl: D >= 1");
+  return launch_sgd_rows<true>(p, buf, g_rows, idx, n_s, D, lr, momentum, wd, ctl, stream);
 }
 
 extern "C" int fr_ema_chunk_elems(void) { return SGD_CHUNK; }

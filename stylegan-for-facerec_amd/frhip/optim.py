@@ -9,8 +9,14 @@ skipped entirely.  ``param_groups`` stay plain dicts so warm_up_lr / schedule_lr
 A parameter that carries ``_frhip_row_grad = (idx, rows)`` (the sampled class-sharded head with ``sparse_update=True``,
 frhip/sharded_head.py) takes the same update on the rows ``idx`` alone, in one launch of its own (fr_sgd_rows): the lazy
 update of Partial-FC v1, where an unselected row sees no weight decay and no momentum step.  ``SGD`` only; ``Adam`` refuses.
+
+``GradGuard`` measures the global L2 norm of a parameter set's gradients on the device (two small launches) and leaves a
+control word there -- norm, clip coefficient, go flag -- that ``SGD.step(guard=...)`` / ``Adam.step(guard=...)`` consume:
+global-norm clipping and the skip of a step whose gradients are not finite, with no host read and no second pass over the
+gradients.  Without a guard the optimizers run exactly the launches they ran before it existed.
 """
 import ctypes
+import itertools
 
 import torch
 
@@ -29,7 +35,7 @@ class SGD(torch.optim.Optimizer):
                                       nesterov=nesterov, maximize=maximize, foreach=None, differentiable=False,
                                       fused=None))
         self._sig = None
-        self._tables = []  # per group: (table_dev, chunks_dev, nchunks)
+        self._tables = []  # per group: [(table_dev, chunks_dev, nchunks, use_coef)], one entry without a guard
 
     def zero_grad(self, set_to_none=False):
         """Keeps gradient buffers alive (the engine writes into them).  Gradients that are views of an engine
@@ -56,15 +62,16 @@ class SGD(torch.optim.Optimizer):
             a.zero_()
             a._frhip_zeroed = True  # the engine's next backward skips its own fill (engine.run_backward)
 
-    def _build(self):
+    def _build(self, guard=None):
+        """Per group the launch tables [(table_dev, chunks_dev, nchunks, use_coef)]: one table without a guard; with one,
+        the tensors of the guard's parameter set (use_coef 1: clipped) apart from the rest (use_coef 0: go flag only)."""
         for group in self.param_groups:  # a loaded state dict may carry settings this kernel does not implement
             if group.get("dampening", 0) != 0 or group.get("nesterov", False) or group.get("maximize", False):
                 raise NotImplementedError("frhip.optim.SGD: dampening / nesterov / maximize are not implemented")
         chunk = _lib.lib.fr_sgd_chunk_elems()
         self._tables = []
-        keep = []
         for group in self.param_groups:
-            recs, chunks = [], []
+            split = {}  # use_coef -> (records, chunks)
             for p in group["params"]:
                 if p.grad is None:
                     continue
@@ -86,20 +93,23 @@ class SGD(torch.optim.Optimizer):
                 if not (_dense_same(p, g) and _dense_same(p, buf)):
                     raise _lib.FrhipError("frhip.optim.SGD: param / grad / momentum buffer must share one dense layout")
                 n = p.numel()
+                recs, chunks = split.setdefault(1 if guard is not None and guard.covers(p) else 0, ([], []))
                 t = len(recs)
                 recs.append((p.data_ptr(), g.data_ptr(), buf.data_ptr(), n, float(group["weight_decay"])))
                 chunks.extend((t, c) for c in range((n + chunk - 1) // chunk))
-            if not recs:
+            if not split:
                 self._tables.append(None)
                 continue
-            arr = (_lib.FrSgdTensor * len(recs))()
-            for i, (pp, gp, bp, n, wd) in enumerate(recs):
-                arr[i].p, arr[i].g, arr[i].buf, arr[i].n, arr[i].wd = pp, gp, bp, n, wd
-            dev = group["params"][0].device
-            raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
-            ch = torch.tensor(chunks, dtype=torch.int32).reshape(-1).to(dev)
-            self._tables.append((raw, ch, len(chunks)))
-            keep.append(arr)
+            tabs = []
+            for use_coef, (recs, chunks) in split.items():
+                arr = (_lib.FrSgdTensor * len(recs))()
+                for i, (pp, gp, bp, n, wd) in enumerate(recs):
+                    arr[i].p, arr[i].g, arr[i].buf, arr[i].n, arr[i].wd = pp, gp, bp, n, wd
+                dev = group["params"][0].device
+                raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+                ch = torch.tensor(chunks, dtype=torch.int32).reshape(-1).to(dev)
+                tabs.append((raw, ch, len(chunks), use_coef))
+            self._tables.append(tabs)
 
     def load_state_dict(self, state_dict):
         """As torch.optim.Optimizer.load_state_dict (works before the first step, like the reference's resume at
@@ -112,8 +122,15 @@ class SGD(torch.optim.Optimizer):
                      for g in self.param_groups for p in g["params"])
 
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None, guard=None):
+        """One update.  ``guard``: a ``GradGuard`` whose ``measure()`` ran for this step.  The update then goes through the
+        ``_ctl`` entry points: nothing moves when the guard's go flag is 0; the tensors of the guard's parameter set take
+        their gradient times the clip coefficient, the rest (the head) take it as it is and obey the go flag only -- at most
+        one launch more per parameter group; a row gradient goes through fr_sgd_rows_ctl.  ``.grad`` is never modified: the
+        coefficient is applied where the gradient is read (torch's ``clip_grad_norm_`` scales ``.grad`` in place; code that
+        reads ``.grad`` after the step sees the unclipped values here).  Without a guard: the launches of before."""
         loss = closure() if closure is not None else None
+        ctl = guard._take("frhip.optim.SGD") if guard is not None else None
         # parameters that carry a row gradient (sharded_head.py, sparse_update): their .grad is None, so the dense tables
         # leave them out and the signature does not move with them
         rows = _row_grad_params(self.param_groups)
@@ -121,23 +138,28 @@ class SGD(torch.optim.Optimizer):
             if p.grad is not None:
                 raise _lib.FrhipError("frhip.optim.SGD: a parameter carries a row gradient (sparse_update) and a dense "
                                       ".grad; the two cannot be combined -- set the dense one to None")
-        sig = self._signature()
+        sig = (self._signature(), None if guard is None else guard.key)
         if sig != self._sig:
-            self._build()
+            if guard is None:
+                self._build()
+            else:
+                self._build(guard)
             self._sig = sig
         st = ops.current_stream_ptr()
-        for group, tab in zip(self.param_groups, self._tables):
-            if tab is None:
-                continue
-            raw, ch, n = tab
-            table = ctypes.cast(ctypes.c_void_p(raw.data_ptr()), ctypes.POINTER(_lib.FrSgdTensor))  # device array
-            ops.Launch("fr_sgd_step", [table, ctypes.c_void_p(ch.data_ptr()), n, float(group["lr"]),
-                                       float(group["momentum"]), st])()
+        for group, tabs in zip(self.param_groups, self._tables):
+            for raw, ch, n, use_coef in tabs or ():
+                table = ctypes.cast(ctypes.c_void_p(raw.data_ptr()), ctypes.POINTER(_lib.FrSgdTensor))  # device array
+                if ctl is None:
+                    ops.Launch("fr_sgd_step", [table, ctypes.c_void_p(ch.data_ptr()), n, float(group["lr"]),
+                                               float(group["momentum"]), st])()
+                else:
+                    ops.Launch("fr_sgd_step_ctl", [table, ctypes.c_void_p(ch.data_ptr()), n, float(group["lr"]),
+                                                   float(group["momentum"]), ops.ptr(ctl), use_coef, st])()
         for group, p in rows:
-            self._step_rows(group, p, st)
+            self._step_rows(group, p, st, ctl)
         return loss
 
-    def _step_rows(self, group, p, st):
+    def _step_rows(self, group, p, st, ctl=None):
         """The lazy update of Partial-FC v1 on a parameter that carries ``_frhip_row_grad = (idx, rows)`` (a sampled
         ``ShardedMarginLoss(sparse_update=True)``): d = rows[j] + wd p[r]; buf[r] = momentum buf[r] + d; p[r] -= lr buf[r]
         on the rows r = idx[j] of the parameter and of its momentum buffer in one launch (fr_sgd_rows: the expression of the
@@ -159,8 +181,12 @@ class SGD(torch.optim.Optimizer):
             buf = state["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
         if buf.shape != p.shape or not buf.is_contiguous():
             raise _lib.FrhipError("frhip.optim.SGD: param / momentum buffer must share one dense layout")
-        ops.call("fr_sgd_rows", p, buf, rows.contiguous(), idx.contiguous(), idx.shape[0], D, float(group["lr"]),
-                 float(group["momentum"]), float(group["weight_decay"]), st)()
+        if ctl is None:
+            ops.call("fr_sgd_rows", p, buf, rows.contiguous(), idx.contiguous(), idx.shape[0], D, float(group["lr"]),
+                     float(group["momentum"]), float(group["weight_decay"]), st)()
+        else:  # under a GradGuard: the go flag only, the head is not clipped
+            ops.call("fr_sgd_rows_ctl", p, buf, rows.contiguous(), idx.contiguous(), idx.shape[0], D, float(group["lr"]),
+                     float(group["momentum"]), float(group["weight_decay"]), ctl, st)()
         p._frhip_row_grad = None
 
 
@@ -168,12 +194,16 @@ class Adam(torch.optim.Optimizer):
     """``torch.optim.Adam(params, lr)`` with its defaults (betas (0.9, 0.999), eps 1e-8, no weight decay, no amsgrad) as one
     multi-tensor HIP launch per parameter group -- the reference's ``OPTIMIZER_NAME == 'Adam'`` branch (train.py:197-198).
     State keys and layout follow torch (``step`` as a host float tensor, ``exp_avg``, ``exp_avg_sq``), so state dicts
-    are interchangeable with ``torch.optim.Adam``.  Parameters whose ``.grad`` is None are skipped and keep their step."""
+    are interchangeable with ``torch.optim.Adam``.  Parameters whose ``.grad`` is None are skipped and keep their step.
+
+    ``step(guard=...)`` as ``SGD.step``.  On a step the guard skips, ``exp_avg``, ``exp_avg_sq`` and the parameters keep their
+    bits, but the host ``step`` counter still advances -- the host does not know that the device skipped -- so the bias
+    correction of later steps is one step ahead of a run that never skipped."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
         self._sig = None
-        self._tables = []  # (group index, step value before this update, table_dev, chunks_dev, nchunks, params)
+        self._tables = []  # [group index, step value before this update, table_dev, chunks_dev, nchunks, params, use_coef]
 
     zero_grad = SGD.zero_grad
 
@@ -188,7 +218,7 @@ class Adam(torch.optim.Optimizer):
             return r
         return t
 
-    def _build(self):
+    def _build(self, guard=None):
         for group in self.param_groups:  # a loaded state dict may carry settings this kernel does not implement
             if group.get("dampening", 0) != 0 or group.get("nesterov", False) or group.get("maximize", False):
                 raise NotImplementedError("frhip.optim.Adam: dampening / nesterov / maximize are not implemented")
@@ -210,8 +240,9 @@ class Adam(torch.optim.Optimizer):
                 st["exp_avg"], st["exp_avg_sq"] = self._relaid(p, st["exp_avg"]), self._relaid(p, st["exp_avg_sq"])
                 if not (_dense_same(p, p.grad) and _dense_same(p, st["exp_avg"]) and _dense_same(p, st["exp_avg_sq"])):
                     raise _lib.FrhipError("frhip.optim.Adam: param / grad / moments must share one dense layout")
-                by_step.setdefault(float(st["step"]), []).append(p)
-            for step0, plist in by_step.items():
+                # with a guard: its parameter set (clipped) apart from the rest (go flag only)
+                by_step.setdefault((float(st["step"]), 1 if guard is not None and guard.covers(p) else 0), []).append(p)
+            for (step0, use_coef), plist in by_step.items():
                 arr = (_lib.FrAdamTensor * len(plist))()
                 chunks = []
                 for i, p in enumerate(plist):
@@ -222,26 +253,30 @@ class Adam(torch.optim.Optimizer):
                 dev = plist[0].device
                 raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
                 ch = torch.tensor(chunks, dtype=torch.int32).reshape(-1).to(dev)
-                self._tables.append([gi, step0, raw, ch, len(chunks), plist])
+                self._tables.append([gi, step0, raw, ch, len(chunks), plist, use_coef])
 
     def _signature(self):
         return tuple((p.data_ptr(), 0 if p.grad is None else p.grad.data_ptr())
                      for g in self.param_groups for p in g["params"])
 
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None, guard=None):
         loss = closure() if closure is not None else None
+        ctl = guard._take("frhip.optim.Adam") if guard is not None else None
         for _group, _p in _row_grad_params(self.param_groups):
             raise NotImplementedError("frhip.optim.Adam: a parameter carries a row gradient (ShardedMarginLoss with "
                                       "sparse_update=True); the row-sparse update is built for frhip.optim.SGD only -- run "
                                       "Adam with sparse_update=False")
-        sig = self._signature()
+        sig = (self._signature(), None if guard is None else guard.key)
         if sig != self._sig:
-            self._build()
+            if guard is None:
+                self._build()
+            else:
+                self._build(guard)
             self._sig = sig
         st = ops.current_stream_ptr()
         for rec in self._tables:
-            gi, step0, raw, ch, n, plist = rec
+            gi, step0, raw, ch, n, plist, use_coef = rec
             group = self.param_groups[gi]
             b1, b2 = group["betas"]
             step = step0 + 1.0
@@ -249,8 +284,12 @@ class Adam(torch.optim.Optimizer):
             step_size = group["lr"] / (1.0 - b1 ** step)
             bc2_sqrt = (1.0 - b2 ** step) ** 0.5
             table = ctypes.cast(ctypes.c_void_p(raw.data_ptr()), ctypes.POINTER(_lib.FrAdamTensor))
-            ops.Launch("fr_adam_step", [table, ctypes.c_void_p(ch.data_ptr()), n, float(step_size), float(1.0 - b1),
-                                        float(b2), float(1.0 - b2), float(group["eps"]), float(bc2_sqrt), st])()
+            scalars = [float(step_size), float(1.0 - b1), float(b2), float(1.0 - b2), float(group["eps"]), float(bc2_sqrt)]
+            if ctl is None:
+                ops.Launch("fr_adam_step", [table, ctypes.c_void_p(ch.data_ptr()), n] + scalars + [st])()
+            else:
+                ops.Launch("fr_adam_step_ctl", [table, ctypes.c_void_p(ch.data_ptr()), n] + scalars +
+                           [ops.ptr(ctl), use_coef, st])()
             for p in plist:
                 self.state[p]["step"] += 1.0
             rec[1] = step
@@ -315,6 +354,125 @@ class ParamEMA(object):
         table = ctypes.cast(ctypes.c_void_p(raw.data_ptr()), ctypes.POINTER(_lib.FrEmaTensor))  # device array
         ops.Launch("fr_ema_step", [table, ctypes.c_void_p(ch.data_ptr()), n, float(a), float(b),
                                    ops.current_stream_ptr()])()
+
+
+_GUARD_KEYS = itertools.count(1)
+
+
+class GradGuard(object):
+    """Global-norm gradient clipping and the non-finite step skip, decided on the device.
+
+        guard = GradGuard(backbone.parameters(), max_norm=5.0, skip_nonfinite=True)
+        loss.backward(); guard.measure(); optimizer.step(guard=guard)
+
+    ``measure()`` enqueues two launches on the current stream: fr_grad_sumsq (one workgroup per 4096-element chunk of every
+    dense ``.grad`` of ``params``, the sum of squares in double in a fixed order) and fr_grad_guard (one workgroup), which
+    leaves in ``self.ctl`` (device float32 [4]) the L2 norm, the clip coefficient of ``torch.nn.utils.clip_grad_norm_``
+    (``min(1, max_norm / (norm + 1e-6))`` in fp32; 1 when ``max_norm`` is None: measure only), the go flag (0 when
+    ``skip_nonfinite`` and the sum of squares is inf or NaN) and a zero, and counts in ``self.skipped`` (device int32 [2])
+    the skipped steps and all measured steps.  No host read, no synchronisation, no allocation after the first call; the
+    result is bit-identical from run to run.  ``optimizer.step(guard=guard)`` then runs under that control word; calling it
+    without a ``measure()`` since the last step raises.  ``state_dict()`` is the one place that reads the device.
+
+    Norm type 2 only.  Parameters whose ``.grad`` is None are left out (a frozen body; a parameter that carries a row
+    gradient), and the table is rebuilt when the gradients' addresses change.  ``.grad`` is never written: the optimizer
+    applies the coefficient as it reads the gradient (torch scales in place).
+
+    The norm is meant for the backbone alone, as in the Partial-FC recipe -- and under a class-sharded head it must be:
+    every rank holds another shard, so a norm that included it would differ between the ranks and the replicated backbone
+    would diverge.  After ``DataParallel.synchronize()`` the backbone's gradients are the same bits on every rank, hence so
+    are the coefficient and the skip decision, without a collective.  Parameters outside the set (the head) are not
+    clipped but obey the go flag.
+
+    Not protected: buffers that move in the forward pass move on a skipped step too -- BatchNorm running statistics,
+    CurricularFace's ``t``, AdaCos's scale, SphereFace's ``iter`` -- as under ``torch.cuda.amp.GradScaler``."""
+
+    def __init__(self, params, max_norm=None, skip_nonfinite=True, norm_type=2.0):
+        self.params = list(params)
+        if not self.params:
+            raise ValueError("frhip.optim.GradGuard: no parameters")
+        if float(norm_type) != 2.0:
+            raise NotImplementedError("frhip.optim.GradGuard: norm type 2 only, got %r" % (norm_type,))
+        if max_norm is not None:
+            if isinstance(max_norm, bool) or not isinstance(max_norm, (int, float)) or not max_norm > 0:
+                raise ValueError("frhip.optim.GradGuard: max_norm must be a number greater than 0, or None to measure "
+                                 "without clipping; got %r" % (max_norm,))
+        for p in self.params:
+            if not p.is_cuda:
+                raise _lib.FrhipError("frhip.optim.GradGuard: parameter on %s -- the HIP guard needs ROCm tensors" % p.device)
+        self.max_norm = None if max_norm is None else float(max_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        dev = self.params[0].device
+        self.ctl = torch.zeros(4, dtype=torch.float32, device=dev)
+        self.skipped = torch.zeros(2, dtype=torch.int32, device=dev)
+        self._ids = frozenset(id(p) for p in self.params)
+        self.key = next(_GUARD_KEYS)  # the optimizers key their launch tables on it: the parameter set never changes
+        self._sig = None
+        self._table = None  # (table_dev, chunks_dev, nchunks, parts)
+        self._measured = False
+
+    def covers(self, p):
+        return id(p) in self._ids
+
+    def _signature(self):
+        return tuple(0 if p.grad is None else p.grad.data_ptr() for p in self.params)
+
+    def _build(self):
+        chunk = _lib.lib.fr_sgd_chunk_elems()
+        recs, chunks = [], []
+        for p in self.params:
+            g = p.grad
+            if g is None:
+                continue
+            if not g.is_cuda or g.dtype != torch.float32 or g.is_sparse or not _is_dense(g):
+                raise _lib.FrhipError("frhip.optim.GradGuard: a gradient must be a dense float32 ROCm tensor")
+            t = len(recs)
+            recs.append((g.data_ptr(), g.numel()))
+            chunks.extend((t, c) for c in range((g.numel() + chunk - 1) // chunk))
+        dev = self.ctl.device
+        if not chunks:
+            self._table = (None, None, 0, None)
+            return
+        arr = (_lib.FrGradTensor * len(recs))()
+        for i, (gp, n) in enumerate(recs):
+            arr[i].g, arr[i].n = gp, n
+        raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+        ch = torch.tensor(chunks, dtype=torch.int32).reshape(-1).to(dev)
+        self._table = (raw, ch, len(chunks), torch.zeros(len(chunks), dtype=torch.float64, device=dev))
+
+    @torch.no_grad()
+    def measure(self):
+        """Enqueue the norm and the control word of the gradients as they are now; returns ``self.ctl`` (device)."""
+        sig = self._signature()
+        if sig != self._sig:
+            self._build()
+            self._sig = sig
+        raw, ch, n, parts = self._table
+        st = ops.current_stream_ptr()
+        if n:
+            table = ctypes.cast(ctypes.c_void_p(raw.data_ptr()), ctypes.POINTER(_lib.FrGradTensor))  # device array
+            ops.Launch("fr_grad_sumsq", [table, ctypes.c_void_p(ch.data_ptr()), n, ops.ptr(parts), st])()
+        ops.Launch("fr_grad_guard", [ops.ptr(parts), n, 0.0 if self.max_norm is None else self.max_norm,
+                                     int(self.skip_nonfinite), ops.ptr(self.ctl), ops.ptr(self.skipped), st])()
+        self._measured = True
+        return self.ctl
+
+    def _take(self, who):
+        """The control word for one optimizer step; a host flag, no device read."""
+        if not self._measured:
+            raise _lib.FrhipError("%s: step(guard=...) without a GradGuard.measure() for this step -- call guard.measure() "
+                                  "after backward (and after the gradient all-reduce) and before step" % who)
+        self._measured = False
+        return self.ctl
+
+    def state_dict(self):
+        """{"skipped": steps the guard skipped, "steps": steps it measured}.  Reads the device (a synchronisation): for
+        checkpoints and display lines."""
+        skipped, steps = (int(v) for v in self.skipped.tolist())
+        return {"skipped": skipped, "steps": steps}
+
+    def load_state_dict(self, state):
+        self.skipped.copy_(torch.tensor([int(state["skipped"]), int(state["steps"])], dtype=torch.int32))
 
 
 def _row_grad_params(param_groups):

@@ -33,7 +33,7 @@ from backbone.restyle_psp import pSp
 from dataset import FacesDataset, StageTransform, SyntheticFaces, TrainTransform
 from frhip import functional as FRF
 from frhip import set_compute_dtype
-from frhip.optim import SGD, Adam
+from frhip.optim import SGD, Adam, GradGuard
 from frhip.parallel import DataParallel
 from head.metrics import (AM_Softmax, AdaCos, Am_softmax, ArcFace, ArcNegFace, CircleLoss, CosFace, CurricularFace, MagFace,
                           MV_Softmax, NPCFace, Softmax, SphereFace)
@@ -181,6 +181,21 @@ def check_head_config(cfg):
                                       "built for 'SGD' only" % (cfg.get("OPTIMIZER_NAME"),))
 
 
+def check_guard_config(cfg):
+    """The gradient guard's keys (frhip.optim.GradGuard), validated before anything is built.  GRAD_CLIP_NORM: None (off, the
+    default) or a number greater than 0, the max_norm of global-norm clipping over the backbone's gradients;
+    SKIP_NONFINITE_STEP: False (the default) or True, skip the step whose backbone gradients hold an inf or a NaN.  Returns
+    None when both are off -- no guard is built and the loop is the one without it -- else (max_norm or None, skip)."""
+    clip, skip = cfg.get("GRAD_CLIP_NORM", None), cfg.get("SKIP_NONFINITE_STEP", False)
+    if clip is not None and (isinstance(clip, bool) or not isinstance(clip, (int, float)) or not clip > 0):
+        raise ValueError("GRAD_CLIP_NORM must be None or a number greater than 0, got %r" % (clip,))
+    if not isinstance(skip, bool):
+        raise ValueError("SKIP_NONFINITE_STEP must be True or False, got %r" % (skip,))
+    if clip is None and not skip:
+        return None
+    return (None if clip is None else float(clip)), skip
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=str, default="config.py")
@@ -189,6 +204,7 @@ def main():
     args = ap.parse_args()
     cfg = importlib.import_module(args.config.replace(".py", "").replace("/", ".")).configurations[1]
     check_head_config(cfg)
+    guard_cfg = check_guard_config(cfg)
 
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -306,6 +322,11 @@ def main():
         optimizer = make_optimizer(list(crit.parameters()))  # the weight shard; the Softmax head's bias shard behind it
     # exposes .module like nn.DataParallel; all-reduce only when world > 1 (a weight shard is complete on its owner)
     BACKBONE = DataParallel(backbone, None if crit is not None else head)
+    # GRAD_CLIP_NORM / SKIP_NONFINITE_STEP: the norm is the backbone's alone (the same bits on every rank once the gradients
+    # are all-reduced, whatever shard of the head a rank holds); the head is not clipped but skips with the backbone
+    guard = None
+    if guard_cfg is not None:
+        guard = GradGuard(backbone.parameters(), max_norm=guard_cfg[0], skip_nonfinite=guard_cfg[1])
     # LOSS_NAME 'Softmax' (reference train.py:237-238): the batch-mean cross entropy on the HIP row-softmax kernels
     ce = CrossEntropyLoss() if cfg["LOSS_NAME"] == "Softmax" else torch.nn.CrossEntropyLoss()
 
@@ -335,6 +356,8 @@ def main():
                 crit.iter = head.iter
         if "head_scale" in state and cfg["HEAD_NAME"] == "AdaCos":  # AdaCos's scale: not in the Head_* file (key W alone)
             head.scale.fill_(float(state["head_scale"]))
+        if guard is not None and "grad_guard" in state:  # the skipped / measured step counters
+            guard.load_state_dict(state["grad_guard"])
         if "torch_rng" in state:
             torch.set_rng_state(state["torch_rng"])
             n = state["numpy_rng"]
@@ -399,13 +422,22 @@ def main():
             optimizer.zero_grad()
             loss.backward()
             BACKBONE.synchronize()
-            optimizer.step()
+            if guard is None:
+                optimizer.step()
+            else:  # two small launches leave norm, clip coefficient and go flag on the device; the step reads them there
+                guard.measure()
+                optimizer.step(guard=guard)
             if (batch + 1) % disp_freq == 0 or (args.max_steps and batch + 1 >= args.max_steps):
                 flush()
                 if rank == 0:
-                    print("Epoch {}/{} Batch {}\tTraining Loss {:.4f} ({:.4f})\tPrec@1 {:.3f} ({:.3f})\tPrec@5 {:.3f} "
-                          "({:.3f})".format(epoch + 1, cfg["NUM_EPOCH"], batch + 1, losses.val, losses.avg, top1.val,
-                                            top1.avg, top5.val, top5.avg))
+                    line = ("Epoch {}/{} Batch {}\tTraining Loss {:.4f} ({:.4f})\tPrec@1 {:.3f} ({:.3f})\tPrec@5 {:.3f} "
+                            "({:.3f})".format(epoch + 1, cfg["NUM_EPOCH"], batch + 1, losses.val, losses.avg, top1.val,
+                                              top1.avg, top5.val, top5.avg))
+                    if guard is not None:  # the host has just synchronised in flush(): the last norm and the counters
+                        counts = guard.state_dict()
+                        line += "\tGrad Norm {:.4f}\tSkipped {}/{}".format(float(guard.ctl[0]), counts["skipped"],
+                                                                           counts["steps"])
+                    print(line)
                     if logger is not None:
                         logger.log({"train_loss": losses.val, "step": batch * cfg["BATCH_SIZE"] * world})
             batch += 1
@@ -478,6 +510,8 @@ def main():
                 run_state["head_iter"] = int(head.iter if finished else epoch_first_iter)
             if epoch_first_scale is not None:  # AdaCos's scale, at the same point as "batch" (the exact fp32 value)
                 run_state["head_scale"] = float(head.scale if finished else epoch_first_scale)
+            if guard is not None:
+                run_state["grad_guard"] = guard.state_dict()
             torch.save(run_state, os.path.join(root, "State_{}_{}".format(cfg["HEAD_NAME"], tag)))
         if args.max_steps and batch >= args.max_steps:
             break
