@@ -861,6 +861,17 @@ int fr_scatter_rows(const float* g, const int32_t* inv, float* out, int n, int D
 int fr_augment_u8(const uint8_t* src, const int32_t* xtab, const int32_t* ytab, const int32_t* crop, const uint8_t* flip,
                   const float* lut, float* out, int B, int Hin, int Win, int Hr, int Wr, int S, int kx, int ky,
                   void* stream);
+/* The same transform on a batch drawn from a device-resident store (frhip/resident.py): image b of the batch is
+ * store[idx[b]], transformed exactly as fr_augment_u8 transforms image b of a staged batch (same tables, crop, flip, lut),
+ * and label_out[b] = labels[idx[b]] is written by the same launch.  One launch, the grid of fr_augment_u8.
+ *   store uint8 [M][Hin][Win][3]    labels int64 [M]    idx int32 [B], 0 <= idx[b] < M (checked by the caller: the indices
+ *   live in device memory), may repeat, in any order    label_out int64 [B]    labels / label_out may both be null
+ * The slot offset idx[b] * Hin * Win * 3 is formed in 64 bits: stores beyond 4 GiB are the normal case.  B <= 0 returns 0;
+ * M <= 0, the size conditions of fr_augment_u8, B > 65535 and a null store / idx / out are refused before any launch. */
+int fr_augment_u8_gather(const uint8_t* store, const int64_t* labels, const int32_t* idx, const int32_t* xtab,
+                         const int32_t* ytab, const int32_t* crop, const uint8_t* flip, const float* lut, float* out,
+                         int64_t* label_out, int M, int B, int Hin, int Win, int Hr, int Wr, int S, int kx, int ky,
+                         void* stream);
 /* F.interpolate(x, size, mode='bilinear') of pSp.forward (backbone/restyle_psp.py:440-443: align_corners = False, no
  * antialias) on fp32 NCHW planes: in [planes][Hin][Win] -> out [planes][Hout][Wout]; planes = B * C <= 65535. */
 int fr_resize_bilinear(const float* in, float* out, int planes, int Hin, int Win, int Hout, int Wout, void* stream);

@@ -56,6 +56,10 @@ def stage3(exp_name, **overrides):
         GPU_ID=[0],
         PIN_MEMORY=True,
         NUM_WORKERS=8,
+        GPU_RESIDENT_DATASET=False,      # True (needs GPU_INPUT_PIPELINE=True): decode the training set once into device
+                                         # memory and draw every batch from there in one launch (frhip/resident.py); the
+                                         # samples, crops, flips and checkpoints of the GPU_INPUT_PIPELINE run, bit for bit
+        GPU_RESIDENT_MAX_GB=None,        # the most the resident set may take; None: half of the device's free memory
     )
     cfg.update(overrides)
     return cfg

@@ -23,25 +23,17 @@ __device__ __forceinline__ int clip8(int v) {
 }
 
 // xtab / ytab rows: [first input index, tap count, k_0 .. k_{K-1}]
-__global__ __launch_bounds__(256) void augment_u8_kernel(const unsigned char* __restrict__ src,
-                                                         const int* __restrict__ xtab, const int* __restrict__ ytab,
-                                                         const int* __restrict__ crop,
-                                                         const unsigned char* __restrict__ flip,
-                                                         const float* __restrict__ lut, float* __restrict__ out,
-                                                         int Hin, int Win, int S, int kx, int ky) {
-  __shared__ float slut[768];
-  for (int i = threadIdx.x; i < 768; i += 256) slut[i] = lut[i];
-  __syncthreads();
-  const int b = blockIdx.y;
-  const int pix = blockIdx.x * 256 + threadIdx.x;
-  if (pix >= S * S) return;
+// One output pixel `pix` of one image: `img` is that image's [Hin][Win][3] bytes, `o` its [3][S][S] floats.  Shared by the
+// staged-batch kernel and the resident-store gather, which differ in where `img` comes from and in nothing else.
+__device__ __forceinline__ void augment_pixel(const unsigned char* __restrict__ img, const int* __restrict__ xtab,
+                                              const int* __restrict__ ytab, int x0, int y0, bool flipped,
+                                              const float* slut, float* __restrict__ o, int pix, int Win, int S, int kx,
+                                              int ky) {
   const int y = pix / S, x = pix - y * S;
-  const int x0 = crop[2 * b], y0 = crop[2 * b + 1];
-  const int rx = x0 + (flip[b] ? S - 1 - x : x), ry = y0 + y;  // position in the resized image
+  const int rx = x0 + (flipped ? S - 1 - x : x), ry = y0 + y;  // position in the resized image
   const int* xr = xtab + (size_t)rx * (kx + 2);
   const int* yr = ytab + (size_t)ry * (ky + 2);
   const int xmin = xr[0], xn = xr[1], ymin = yr[0], yn = yr[1];
-  const unsigned char* img = src + (size_t)b * Hin * Win * 3;
   int acc[3] = {1 << (PRECISION_BITS - 1), 1 << (PRECISION_BITS - 1), 1 << (PRECISION_BITS - 1)};
   for (int t = 0; t < yn; ++t) {
     const unsigned char* row = img + ((size_t)(ymin + t) * Win + xmin) * 3;
@@ -58,10 +50,46 @@ __global__ __launch_bounds__(256) void augment_u8_kernel(const unsigned char* __
     acc[2] += clip8(h[2]) * kv;
   }
   const size_t plane = (size_t)S * S;
-  float* o = out + (size_t)b * 3 * plane + pix;
-  o[0] = slut[clip8(acc[0]) * 3];
-  o[plane] = slut[clip8(acc[1]) * 3 + 1];
-  o[2 * plane] = slut[clip8(acc[2]) * 3 + 2];
+  o[pix] = slut[clip8(acc[0]) * 3];
+  o[plane + pix] = slut[clip8(acc[1]) * 3 + 1];
+  o[2 * plane + pix] = slut[clip8(acc[2]) * 3 + 2];
+}
+
+__global__ __launch_bounds__(256) void augment_u8_kernel(const unsigned char* __restrict__ src,
+                                                         const int* __restrict__ xtab, const int* __restrict__ ytab,
+                                                         const int* __restrict__ crop,
+                                                         const unsigned char* __restrict__ flip,
+                                                         const float* __restrict__ lut, float* __restrict__ out,
+                                                         int Hin, int Win, int S, int kx, int ky) {
+  __shared__ float slut[768];
+  for (int i = threadIdx.x; i < 768; i += 256) slut[i] = lut[i];
+  __syncthreads();
+  const int b = blockIdx.y;
+  const int pix = blockIdx.x * 256 + threadIdx.x;
+  if (pix >= S * S) return;
+  augment_pixel(src + (size_t)b * Hin * Win * 3, xtab, ytab, crop[2 * b], crop[2 * b + 1], flip[b] != 0, slut,
+                out + (size_t)b * 3 * S * S, pix, Win, S, kx, ky);
+}
+
+// The same batch drawn from a resident store [M][Hin][Win][3]: image b is store[idx[b]] (idx may repeat, in any order;
+// 0 <= idx[b] < M is the caller's to guarantee, the indices live in device memory).  The slot offset is formed in size_t: a
+// store of 1.3 M 112x112 images is 49 GB.  The label of image b travels with it, written by one thread of its first
+// workgroup.
+__global__ __launch_bounds__(256) void augment_u8_gather_kernel(
+    const unsigned char* __restrict__ store, const long long* __restrict__ labels, const int* __restrict__ idx,
+    const int* __restrict__ xtab, const int* __restrict__ ytab, const int* __restrict__ crop,
+    const unsigned char* __restrict__ flip, const float* __restrict__ lut, float* __restrict__ out,
+    long long* __restrict__ label_out, int Hin, int Win, int S, int kx, int ky) {
+  __shared__ float slut[768];
+  for (int i = threadIdx.x; i < 768; i += 256) slut[i] = lut[i];
+  __syncthreads();
+  const int b = blockIdx.y;
+  const size_t slot = (size_t)idx[b];
+  if (label_out != nullptr && blockIdx.x == 0 && threadIdx.x == 0) label_out[b] = labels[slot];
+  const int pix = blockIdx.x * 256 + threadIdx.x;
+  if (pix >= S * S) return;
+  augment_pixel(store + slot * ((size_t)Hin * Win * 3), xtab, ytab, crop[2 * b], crop[2 * b + 1], flip[b] != 0, slut,
+                out + (size_t)b * 3 * S * S, pix, Win, S, kx, ky);
 }
 
 }  // namespace
@@ -76,6 +104,24 @@ extern "C" int fr_augment_u8(const uint8_t* src, const int32_t* xtab, const int3
   dim3 grid((S * S + 255) / 256, B);
   hipLaunchKernelGGL(augment_u8_kernel, grid, dim3(256), 0, (hipStream_t)stream, src, xtab, ytab, crop, flip, lut, out,
                      Hin, Win, S, kx, ky);
+  FR_LAUNCH_CHECK();
+}
+
+extern "C" int fr_augment_u8_gather(const uint8_t* store, const int64_t* labels, const int32_t* idx, const int32_t* xtab,
+                                    const int32_t* ytab, const int32_t* crop, const uint8_t* flip, const float* lut,
+                                    float* out, int64_t* label_out, int M, int B, int Hin, int Win, int Hr, int Wr, int S,
+                                    int kx, int ky, void* stream) {
+  if (B <= 0) return 0;
+  if (M <= 0) FR_UNSUPPORTED("fr_augment_u8_gather: the store holds no image (M <= 0)");
+  if (Hin <= 0 || Win <= 0 || S <= 0 || S > Hr || S > Wr || kx <= 0 || ky <= 0)
+    FR_UNSUPPORTED("fr_augment_u8_gather: sizes (need 0 < S <= resized size, at least one tap per axis)");
+  if (B > 65535) FR_UNSUPPORTED("fr_augment_u8_gather: more than 65535 images per launch");
+  if (!store || !idx || !out) FR_UNSUPPORTED("fr_augment_u8_gather: store, idx and out are required");
+  if (!labels) label_out = nullptr;  // the labels travel only when both ends exist
+  dim3 grid((S * S + 255) / 256, B);
+  hipLaunchKernelGGL(augment_u8_gather_kernel, grid, dim3(256), 0, (hipStream_t)stream, store,
+                     (const long long*)labels, idx, xtab, ytab, crop, flip, lut, out, (long long*)label_out, Hin, Win, S,
+                     kx, ky);
   FR_LAUNCH_CHECK();
 }
 

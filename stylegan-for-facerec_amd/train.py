@@ -196,6 +196,21 @@ def check_guard_config(cfg):
     return (None if clip is None else float(clip)), skip
 
 
+def check_input_config(cfg):
+    """The resident training set's keys (frhip/resident.py), validated before anything is built.  GPU_RESIDENT_DATASET:
+    False (the default) or True, decode the training set once into device memory and draw every batch from there;
+    GPU_RESIDENT_MAX_GB: None (the default: half of the device's free memory) or a number greater than 0, the most the set
+    may take."""
+    resident, max_gb = cfg.get("GPU_RESIDENT_DATASET", False), cfg.get("GPU_RESIDENT_MAX_GB", None)
+    if not isinstance(resident, bool):
+        raise ValueError("GPU_RESIDENT_DATASET must be True or False, got %r" % (resident,))
+    if max_gb is not None and (isinstance(max_gb, bool) or not isinstance(max_gb, (int, float)) or not max_gb > 0):
+        raise ValueError("GPU_RESIDENT_MAX_GB must be None or a number greater than 0, got %r" % (max_gb,))
+    if resident and not cfg.get("GPU_INPUT_PIPELINE", False):
+        raise NotImplementedError("GPU_RESIDENT_DATASET=True needs GPU_INPUT_PIPELINE=True: the resident set feeds the GPU "
+                                  "transform (staged uint8 images), not the host transform")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=str, default="config.py")
@@ -204,6 +219,7 @@ def main():
     args = ap.parse_args()
     cfg = importlib.import_module(args.config.replace(".py", "").replace("/", ".")).configurations[1]
     check_head_config(cfg)
+    check_input_config(cfg)
     guard_cfg = check_guard_config(cfg)
 
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
@@ -252,6 +268,14 @@ def main():
                                          shuffle=False, pin_memory=cfg["PIN_MEMORY"],
                                          num_workers=cfg["NUM_WORKERS"], drop_last=cfg["DROP_LAST"],
                                          collate_fn=collate_fn_ignore_none)
+    resident = cfg.get("GPU_RESIDENT_DATASET", False)
+    if resident:
+        # the set is decoded once into device memory (every rank holds all of it) and each batch is one gather + transform
+        # launch: bit for bit the samples, crops and flips of the loader above (frhip/resident.py)
+        from frhip.resident import ResidentLoader, ResidentStore
+        store = ResidentStore.build(dataset, device, cfg["NUM_WORKERS"], cfg.get("GPU_RESIDENT_MAX_GB", None))
+        loader = ResidentLoader(store, gpu_tf, cfg["BATCH_SIZE"], cfg["DROP_LAST"], world, rank, cfg["SEED"],
+                                generator=aug_rng)
     print("Number of Training Classes: {}".format(num_class))
     val = get_val_data(cfg["DATA_ROOT"]) if not args.synthetic else None
 
@@ -387,7 +411,7 @@ def main():
             enc.input_layer.requires_grad_(True)
             enc.body.requires_grad_(epoch > freeze)
             enc.output_layer.requires_grad_(True)
-        sampler.set_epoch(epoch)
+        (loader if resident else sampler).set_epoch(epoch)
         if gpu_tf is not None:  # crops / flips are a function of (SEED, epoch, rank): a resumed run redraws the same ones
             aug_rng.manual_seed(cfg["SEED"] + 7919 * rank + 104729 * (epoch + 1))
         losses, top1, top5 = AverageMeter(), AverageMeter(), AverageMeter()
@@ -403,10 +427,11 @@ def main():
         for inputs, labels in loader:
             if cfg.get("WARMUP", True) and epoch + 1 <= warm_epochs and batch + 1 <= warm_batches:
                 warm_up_lr(batch, warm_batches, cfg["LR"], optimizer)
-            inputs = inputs.to(device, non_blocking=True)
-            labels = labels.to(device, non_blocking=True).long()
-            if gpu_tf is not None:
-                inputs = gpu_tf(inputs, generator=aug_rng)
+            if not resident:
+                inputs = inputs.to(device, non_blocking=True)
+                labels = labels.to(device, non_blocking=True).long()
+                if gpu_tf is not None:
+                    inputs = gpu_tf(inputs, generator=aug_rng)
             if crit is not None:
                 loss, prec1, prec5 = crit(BACKBONE(inputs), labels)
             else:
