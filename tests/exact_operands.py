@@ -15,12 +15,17 @@ references below; the recipes assert their own preconditions before anything is 
 The GEMMs of the output layer (Linear forward in K slices, data and weight gradient on the fp32 master weight, the split-K
 slab epilogue) and the Flatten-order hand-over in front of them are the third group (last section; test_gpu_exact_output.py).
 
+The ArcFace / CosFace head and the cosine backward every head shares are the fourth group (the section behind that;
+test_gpu_exact_head.py): operands whose norms are powers of two, so that the normalised rows, the cosines the GEMM forms from
+them and the whole CosFace chain are dyadic fractions, exact in fp32 in any order.
+
 A plain helper module (like shard_ref.py), used by test_exact_operands_host.py (no GPU), test_gpu_exact_conv.py,
-test_gpu_exact_elementwise.py and test_gpu_exact_output.py.
+test_gpu_exact_elementwise.py, test_gpu_exact_output.py and test_gpu_exact_head.py.
 Layout: activations NHWC ``[B, H, W, C]``, weights packed ``[O][kh*kw][I]`` -- what the C ABI takes.
 """
 import math
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -732,3 +737,321 @@ def flatten_case(B, C, HW, O, keep, p, seed=263):
     assert_exact_range(stored=[a, ga, gy], fp32=[(f, a.abs() @ c["Wq"].abs().t(), 1.0), (dW, c["g"].double().abs().t() @ a.abs(), 1.0)],
                        what=what)
     return dict(c, x=x, scale=scale, shift=shift), a, f, gy, dW
+
+
+# ------------------------------------------------------------------------------------------------------------ margin head
+# ArcFace / CosFace at the C ABI (FR_EPI_MARGIN of fr_conv_igemm, fr_margin_bwd) and the cosine backward every head shares
+# (frhip/functional.py::_cosine_backward: the head-shaped fr_conv_wgrad, FR_EPI_SLAB + fr_reduce_parts, fr_normalize_bwd,
+# fr_col_normalize_bwd): operand recipes, float64 references and comparators of test_gpu_exact_head.py.
+#
+# A weight row has nnz non-zeros of +-2^j (nnz a power of 4), so its norm is sqrt(nnz) 2^j, the reciprocal norm a power of two and
+# the normalised row +-1 / sqrt(nnz) on its support.  An embedding row is the sign pattern of its label's weight row with k signs
+# flipped -- target cosine (nnz - 2k) / nnz -- and, for the odd numerators, one non-zero moved off the support (where D > nnz),
+# times its own 2^j.  Every cosine is then a multiple of 1 / nnz that the GEMM forms without a rounding, in any order.
+HEAD_SHAPES = [(1, 4, 32),           # one row, one vector, Np = 32, split-K 1
+               (37, 203, 64),        # N % 4 = 3: ld = 204, ragged vector and column tile, Np = 224 < 256: per-row transposed copy
+               (129, 65, 32),        # one row in the second 128-row tile, one column in the second column tile
+               (5, 500, 32),         # Np = 512: split-K 2 in the data gradient, tiled transpose
+               (130, 1000, 512)]     # the product's D, split-K 4
+HEAD_COL_SHAPES = HEAD_SHAPES + [(37, 203, 96)]   # fr_col_normalize[_bwd]: a ragged 64-tile in D as well
+HEAD_NNZ = {32: 16, 64: 64, 96: 64, 512: 256}
+HEAD_CONFIGS = {"arcface": (0, 64.0, 0.5, 0), "arcface_easy": (0, 64.0, 0.5, 1), "cosface": (1, 30.0, 0.35, 0)}  # kind, s, m, easy
+HEAD_TH = math.cos(math.pi - 0.5)    # ArcFace's branch threshold at m = 0.5: the target cosines lie on both sides of it
+HEAD_TH_CLEARANCE = 2.0 ** -10       # see head_case
+PHI_ROUNDINGS = 8 * 2.0 ** -24       # the derived bound of the two ArcFace expressions, in units of their larger term
+EPS32 = float(np.float32(1e-10))     # the clamp of 1 - c^2 as the kernels hold it: [1e-10f, 1.0f - 1e-10f] = [1e-10f, 1.0f]
+
+
+def _f32(v):
+    return float(np.float32(v))
+
+
+def _ulp32(v):
+    return float(np.spacing(np.float32(abs(v))))
+
+
+def pad_to(n, m):
+    return (n + m - 1) // m * m
+
+
+def margin_constants(name):
+    """What frhip/functional.py::margin_forward hands to the kernels for a HEAD_CONFIGS entry, rounded to fp32 as the float
+    arguments of the C ABI are."""
+    kind, s, m, easy = HEAD_CONFIGS[name]
+    if kind == 0:
+        cos_m, sin_m, th, mm = math.cos(m), math.sin(m), math.cos(math.pi - m), math.sin(math.pi - m) * m
+    else:
+        cos_m, sin_m, th, mm = m, 0.0, 0.0, 0.0
+    return dict(name=name, kind=kind, easy=easy, s=_f32(s), cos_m=_f32(cos_m), sin_m=_f32(sin_m), th=_f32(th), mm=_f32(mm))
+
+
+def head_label_columns(N):
+    """The columns the labels must reach, in the order in which rows are spent on them: N - 1, the first column of the last
+    16-byte vector, the last and the first column of the last full 64-column tile, 63, 64, 0, and both sides of a vector boundary
+    inside a tile (3 | 4)."""
+    full = N // 64
+    cols = [N - 1, 4 * ((N - 1) // 4)] + ([64 * full - 1, 64 * (full - 1)] if full else []) + [63, 64, 0, 3, 4]
+    out = []
+    for c in cols:
+        if 0 <= c < N and c not in out:
+            out.append(c)
+    return out
+
+
+def head_labels(B, N):
+    """Placed, not drawn: (labels [B] int64, ordinal [B]).  Rows 1 and B - 2 carry -1 (the sharded head's "not my class") where
+    B >= 4.  The other rows take head_label_columns(N) in order -- the last row first: at B = 129 it is the one row of the second
+    row tile -- then (37 i + 11) mod N.  ordinal[b]: the position of row b in that order (-1: no label)."""
+    none = [1, B - 2] if B >= 4 else []
+    order = []
+    for b in [B - 1, 0] + list(range(2, B)):
+        if b not in none and b not in order:
+            order.append(b)
+    cols = head_label_columns(N)
+    labels, ordinal = torch.full((B,), -1, dtype=torch.int64), [-1] * B
+    for i, b in enumerate(order):
+        labels[b] = cols[i] if i < len(cols) else (37 * i + 11) % N
+        ordinal[b] = i
+    return labels, ordinal
+
+
+def head_targets(nnz, D):
+    """(k, move) by ordinal: k sign flips and `move` (0 | 1) non-zeros off the support give the cosine (nnz - move - 2k) / nnz.
+    First +1, -1, 0, the two cosines next to HEAD_TH, the two next to 0; then every other one, visited with a stride coprime to
+    their number."""
+    combos = [(k, 0) for k in range(nnz + 1)] + ([(k, 1) for k in range(nnz)] if D > nnz else [])
+    cosv = lambda c: (nnz - c[1] - 2 * c[0]) / nnz  # noqa: E731
+    first = [(0, 0), (nnz, 0), (nnz // 2, 0),
+             min((c for c in combos if cosv(c) > HEAD_TH), key=cosv), max((c for c in combos if cosv(c) < HEAD_TH), key=cosv),
+             min((c for c in combos if cosv(c) > 0), key=cosv), max((c for c in combos if cosv(c) < 0), key=cosv)]
+    rest = [c for c in sorted(combos, key=cosv) if c not in first]
+    stride = int(0.382 * len(rest)) | 1
+    while math.gcd(stride, len(rest)) != 1:
+        stride += 2
+    return lambda i: first[i] if i < len(first) else rest[((i - len(first)) * stride) % len(rest)]
+
+
+def _pow2_quantum(t):
+    """The largest power of two that divides every element."""
+    m = t.double().reshape(-1)
+    m = m[m != 0]
+    if m.numel() == 0:
+        return 1.0
+    for e in range(40, -80, -1):
+        q = 2.0 ** e
+        if bool((m / q == (m / q).round()).all()):
+            return q
+    raise AssertionError("no dyadic quantum above 2^-80")
+
+
+def assert_f32(t, what):
+    assert torch.equal(t.double().float().double(), t.double()), "%s does not survive a round trip through float32" % what
+
+
+def assert_gemm_exact(a, b, what):
+    """a [M][K] @ b [K][N]: the sum of the magnitudes of the terms of every element stays below 2^24 quanta of the smallest
+    term (the power of two that divides every product), so fp32 sums them exactly in any order."""
+    q = _pow2_quantum(a) * _pow2_quantum(b)
+    worst = float((a.double().abs() @ b.double().abs()).max()) / q
+    assert worst < 2.0 ** 24, "%s: the sums reach %.3g quanta (>= 2^24)" % (what, worst)
+    return worst
+
+
+def assert_rows_exact(a, b, what):
+    """The row-wise dot products a[r] . b[r] under the same condition."""
+    q = _pow2_quantum(a) * _pow2_quantum(b)
+    worst = float((a.double() * b.double()).abs().sum(1).max()) / q
+    assert worst < 2.0 ** 24, "%s: the sums reach %.3g quanta (>= 2^24)" % (what, worst)
+    return worst
+
+
+def cosine_backward(xn, inv_x, wn, inv_w, gcos):
+    """The float64 restatement of frhip/functional.py::_cosine_backward from gcos [B][N] on normalised operands xn [B][D], wn
+    [N][D]: G = gcos @ wn, GW = gcos^T @ xn, and the backward of the normalisation, g_in = (G - xhat (xhat . G)) * inv, for both.
+    The intermediates a kernel rounds (the dot product, its product with xhat, the difference) are returned too."""
+    G, GW = gcos @ wn, gcos.t() @ xn
+    dx, dw = (xn * G).sum(1, keepdim=True), (wn * GW).sum(1, keepdim=True)
+    gx, gw = (G - xn * dx) * inv_x[:, None], (GW - wn * dw) * inv_w[:, None]
+    return dict(G=G, GW=GW, gx=gx, gw=gw, dot_x=dx, dot_w=dw, proj_x=xn * dx, proj_w=wn * dw, diff_x=G - xn * dx,
+                diff_w=GW - wn * dw)
+
+
+def head_case(B, N, D, seed=281):
+    """Operands and float64 references of the margin head at (B, N, D); see the head of this section.  Keys: x [B][D], w [N][D],
+    labels, g [B][N] (upstream gradient from {-2 .. 2}, about half zeros; never zero on a label column, where d phi must show),
+    xn, inv_x, wn [Np][D] (rows N.. zero), wt = wn^T, inv_w, cos [B][N], and the CosFace chain at s = 30: gcos [B][Np], G, GW
+    [N4][D], gx, gw.  Asserted here, on the reference:
+      - every value of the chain (and every intermediate a kernel rounds) is an fp32 number;
+      - each GEMM keeps the sum of magnitudes of its terms below 2^24 quanta of its smallest term (assert_gemm_exact);
+      - no cosine is closer to ArcFace's threshold th than HEAD_TH_CLEARANCE = 2^-10.  The cosines are exact fp32 numbers and the
+        kernels compare them to the fp32 th without a rounding, so ANY non-zero distance decides the branch as float64 does;
+        2^-10 is 2^13 ulps of the cosines there.  (Half the spacing of the cosines, 1 / (2 nnz), cannot be kept by a set that
+        has a cosine on either side of th next to it: the spacing is 1 / nnz and th = -0.87758 lies 0.0026 below -14/16 = -56/64
+        and 0.0013 above -225/256.)"""
+    nnz, Np, N4 = HEAD_NNZ[D], pad_to(N, 32), pad_to(N, 4)
+    what = "head %s" % ((B, N, D),)
+    order = torch.argsort(synth.uniform(seed, "h.w.pos", (N, D), 0.0, 1.0), dim=1)[:, :nnz]
+    sign = torch.where(synth.uniform(seed, "h.w.sign", (N, D), 0.0, 1.0) < 0.5, -1.0, 1.0)
+    wj = pick(seed, "h.w.j", N, [2.0 ** j for j in range(-3, 4)])
+    w = torch.zeros(N, D).scatter_(1, order, torch.gather(sign, 1, order)) * wj[:, None]
+    labels, ordinal = head_labels(B, N)
+    target = head_targets(nnz, D)
+    x = torch.zeros(B, D)
+    for b in range(B):
+        lab = int(labels[b])
+        pattern = torch.sign(w[lab if lab >= 0 else b % N])
+        sup = pattern.nonzero().flatten()
+        k, move = target(ordinal[b]) if lab >= 0 else ((5 * b) % nnz, 0)
+        row = pattern.clone()
+        row[sup[[(b + t) % nnz for t in range(k)]]] *= -1.0
+        if move:
+            off = (pattern == 0).nonzero().flatten()
+            row[sup[(b + nnz - 1) % nnz]] = 0.0
+            row[off[b % off.numel()]] = 1.0
+        x[b] = row * 2.0 ** (b % 7 - 3)
+    g = pick(seed, "h.g", B * N, [-2.0, -1.0, 0.0, 1.0, 2.0], [0.125, 0.125, 0.5, 0.125, 0.125]).view(B, N)
+    for b in range(B):
+        if labels[b] >= 0:
+            g[b, labels[b]] = (1.0 + b % 2) * (-1.0 if (b // 2) % 2 else 1.0)
+    xd, wd = x.double(), w.double()
+    inv_x, inv_w = 1.0 / (xd * xd).sum(1).sqrt(), 1.0 / (wd * wd).sum(1).sqrt()
+    xn = xd * inv_x[:, None]
+    wn = torch.zeros(Np, D, dtype=torch.float64)
+    wn[:N] = wd * inv_w[:, None]
+    cos = xn @ wn[:N].t()
+    s = margin_constants("cosface")["s"]
+    gcos = torch.zeros(B, Np, dtype=torch.float64)
+    gcos[:, :N] = s * g.double()
+    r = cosine_backward(xn, inv_x, wn[:N], inv_w, gcos[:, :N])
+    GW = torch.zeros(N4, D, dtype=torch.float64)
+    GW[:N] = r["GW"]
+    c = dict(B=B, N=N, D=D, nnz=nnz, Np=Np, N4=N4, ld=N4, x=x, w=w, labels=labels, g=g, xn=xn, inv_x=inv_x, wn=wn,
+             wt=wn.t().contiguous(), inv_w=inv_w, cos=cos, gcos=gcos, G=r["G"], GW=GW, gx=r["gx"], gw=r["gw"], chain=r)
+    # the preconditions
+    for name in ("inv_x", "inv_w"):
+        lg = torch.log2(c[name] * math.sqrt(nnz))
+        assert torch.equal(lg, lg.round()), "%s: %s is not a power of two over sqrt(nnz)" % (what, name)
+    assert bool(((xn * math.sqrt(nnz)).abs() == (xn != 0)).all()) and bool(((wn * math.sqrt(nnz)).abs() == (wn != 0)).all()), what
+    assert torch.equal(cos * nnz, (cos * nnz).round()) and float(cos.abs().max()) <= 1.0, what + ": cosines off the 1 / nnz grid"
+    for name, t in [("xn", xn), ("wn", wn), ("cos", cos), ("s * cos", s * cos), ("gcos", gcos)] + sorted(r.items()):
+        assert_f32(t, "%s: %s" % (what, name))
+    c["quanta"] = dict(cos=assert_gemm_exact(xn, wn[:N].t(), what + " cosine GEMM"),
+                       G=assert_gemm_exact(gcos[:, :N], wn[:N], what + " data-gradient GEMM"),
+                       GW=assert_gemm_exact(gcos[:, :N].t(), xn, what + " weight-gradient GEMM"),
+                       dot_x=assert_rows_exact(xn, r["G"], what + " xhat . G"),
+                       dot_w=assert_rows_exact(wn[:N], r["GW"], what + " what . GW"))
+    near = float((cos - HEAD_TH).abs().min())
+    assert near >= HEAD_TH_CLEARANCE, "%s: a cosine lies %.3g from th" % (what, near)
+    return c
+
+
+def head_target_cosines(c):
+    """[B] float64: cos[b][label[b]], NaN where the row has no label."""
+    lab = c["labels"]
+    t = torch.full((c["B"],), float("nan"), dtype=torch.float64)
+    has = lab >= 0
+    t[has] = c["cos"][has, lab[has]]
+    return t
+
+
+def margin_logits_ref(c, k):
+    """What FR_EPI_MARGIN must store for the constants k (margin_constants): (ref [B][N] float64, bound [B][N], moved [B][N]
+    bool).  bound = 0 demands equality: s * c off the label column (one exact product) and in rows without a label; on the label
+    column (c - m) * s for CosFace, (c - mm) * s for ArcFace at c <= th -- two fp32 operations, evaluated in numpy float32 --
+    and s * c under the easy margin at c <= 0.  On ArcFace's phi branch, phi = c cos_m - sqrt(clamp(1 - c^2)) sin_m in float64
+    from the fp32 constants, within PHI_ROUNDINGS * max(|c cos_m|, |sine sin_m|), carried through * s, plus one ulp of the
+    result.  moved: where ref differs from s * c -- the label columns, except where the margin is the identity."""
+    s32, f = np.float32(k["s"]), np.float32
+    plain = k["s"] * c["cos"]
+    ref, bound = plain.clone(), torch.zeros_like(plain)
+    for b in range(c["B"]):
+        lab = int(c["labels"][b])
+        if lab < 0:
+            continue
+        cc = float(c["cos"][b, lab])
+        if k["kind"] == 1:
+            ref[b, lab] = float((f(cc) - f(k["cos_m"])) * s32)
+        elif not (cc > 0.0 if k["easy"] else cc > k["th"]):
+            ref[b, lab] = k["s"] * cc if k["easy"] else float((f(cc) - f(k["mm"])) * s32)
+        else:
+            sine = math.sqrt(min(max(1.0 - cc * cc, EPS32), 1.0))
+            ref[b, lab] = k["s"] * (cc * k["cos_m"] - sine * k["sin_m"])
+            bound[b, lab] = k["s"] * PHI_ROUNDINGS * max(abs(cc * k["cos_m"]), abs(sine * k["sin_m"])) + _ulp32(ref[b, lab])
+    return ref, bound, ref != plain
+
+
+def dphi_ref(cc, k):
+    """(d phi / d cos, bound) of fr_margin_bwd at the fp32 target cosine cc: 1 off the phi branch and for CosFace, cos_m where the
+    clamp of t = 1 - c^2 does not pass (t as fp32 at or outside [1e-10f, 1.0f]) -- both exact -- else cos_m + sin_m c / sqrt(t)
+    within PHI_ROUNDINGS * max(cos_m, |sin_m c / sine|)."""
+    if k["kind"] == 1 or not (cc > 0.0 if k["easy"] else cc > k["th"]):
+        return 1.0, 0.0
+    t = 1.0 - cc * cc
+    if not (_f32(t) > EPS32 and _f32(t) < 1.0):
+        return k["cos_m"], 0.0
+    slope = k["sin_m"] * cc / math.sqrt(t)
+    return k["cos_m"] + slope, PHI_ROUNDINGS * max(k["cos_m"], abs(slope))
+
+
+def margin_gcos_ref(g, labels, cos_t, k, Np):
+    """What fr_margin_bwd must store: (ref [B][Np] float64, bound).  s * g off the label column and in rows without a label (one
+    exact product), +0 in the columns N..Np; on the label column (s g) * dphi: one more fp32 rounding where dphi is exact
+    (equality with that rounding), else within |s g| times dphi's bound plus one ulp of the result.  cos_t: the fp32 target
+    cosines the kernel reads, as float64 (unread for rows without a label)."""
+    B, N = g.shape
+    ref = torch.zeros(B, Np, dtype=torch.float64)
+    ref[:, :N] = k["s"] * g.double()
+    bound = torch.zeros_like(ref)
+    for b in range(B):
+        lab = int(labels[b])
+        if lab < 0:
+            continue
+        d, db = dphi_ref(float(cos_t[b]), k)
+        sg = float(ref[b, lab])
+        ref[b, lab] = sg * d if db else _f32(sg * d)
+        if db:
+            bound[b, lab] = abs(sg) * db + _ulp32(sg * d)
+    return ref, bound
+
+
+def assert_within(got, ref, bound, what="", names=None):
+    """|got - ref| <= bound element for element, bound = 0 meaning equality (a NaN never passes); reports the count, the first
+    index, both values and the bound there."""
+    g, r, bd = got.double().cpu(), ref.double().cpu(), bound.double().cpu()
+    assert g.shape == r.shape == bd.shape, "%s: shape %s vs %s" % (what, tuple(g.shape), tuple(r.shape))
+    bad = ~((g - r).abs() <= bd)
+    if not bool(bad.any()):
+        return
+    idx = bad.nonzero()
+    f = tuple(idx[0].tolist())
+    per = ""
+    if names:
+        per = "; " + ", ".join("%s %s" % (n, sorted(set(idx[:, i].tolist()))[:8]) for i, n in enumerate(names))
+    raise AssertionError("%s: %d of %d elements differ; first at %s: got %r, want %r within %r%s" % (
+        what, idx.shape[0], bad.numel(), f, float(g[f]), float(r[f]), float(bd[f]), per))
+
+
+def check_margin_forward(logits, cos_t, c, k, sentinel, what=""):
+    """Everything FR_EPI_MARGIN owes: the logits [B][N] (margin_logits_ref), cos_t[m] = the label cosine for labelled rows and the
+    untouched `sentinel` for rows with label -1, and the set of elements that differ from s * c is exactly the set of label
+    columns on which the margin is not the identity."""
+    ref, bound, moved = margin_logits_ref(c, k)
+    assert_within(logits, ref, bound, what + " logits", ("row", "column"))
+    want_t = head_target_cosines(c)
+    want_t[torch.isnan(want_t)] = sentinel
+    assert_equal_tensor(cos_t.reshape(-1).cpu(), want_t, what + " cos_t", ("row",))
+    plain = k["s"] * c["cos"]
+    diff = logits.double().cpu() != plain
+    if not torch.equal(diff, moved):
+        f = tuple((diff != moved).nonzero()[0].tolist())
+        raise AssertionError("%s: the elements that differ from s * cos are not the label set; first at %s (label %d): got %r, "
+                             "s * cos %r" % (what, f, int(c["labels"][f[0]]), float(logits[f]), float(plain[f])))
+
+
+def check_margin_backward(gcos, g, labels, cos_t, k, what=""):
+    """Everything fr_margin_bwd owes (margin_gcos_ref), the padding columns N..Np as +0 bit for bit."""
+    N = g.shape[1]
+    ref, bound = margin_gcos_ref(g, labels, cos_t, k, gcos.shape[1])
+    assert_within(gcos, ref, bound, what + " gcos", ("row", "column"))
+    pad = gcos[:, N:].contiguous().cpu()
+    assert bool((pad.view(torch.int32) == 0).all()), "%s: a padding column of gcos is not +0" % what

@@ -625,3 +625,218 @@ def test_linear_comparators_catch_planted_differences():
     trunc = (c["W"].view(torch.int32) & -65536).view(torch.float32).double()
     with pytest.raises(AssertionError):
         X.assert_equal_tensor((c["a"].double() @ trunc.t() + c["bias"].double()).float(), ref.sum(0), "control")
+
+
+# ------------------------------------------------------------------------------------------------------------ margin head
+# The recipe of test_gpu_exact_head.py (exact_operands.head_case) meets its conditions at every shape, its references are the
+# oracle's ArcFace / CosFace and autograd's gradients, and the comparators catch five planted defects.
+head_case = functools.lru_cache(maxsize=None)(X.head_case)
+HEAD_IDS = ["%d_%d_%d" % s for s in X.HEAD_COL_SHAPES]
+
+
+@pytest.mark.parametrize("B,N,D", X.HEAD_COL_SHAPES, ids=HEAD_IDS)
+def test_head_operands_meet_their_conditions(B, N, D):
+    """head_case asserts the exactness conditions itself (fp32 round trip of the whole CosFace chain, every GEMM below 2^24
+    quanta, powers of two as reciprocal norms, the clearance to th).  Here: what the recipe must REACH.  Labels: the columns of
+    head_label_columns where the batch has rows for them, two rows with -1 from B = 4 on.  Target cosines: -1, +1, 0, both
+    neighbours of th and of 0 where the batch has the seven rows for them, every numerator at (129, 65, 32).  Density: 80 % of the
+    off-label cosines are non-zero (a column permutation shows), 80 % of gx where N >= 32 and of gw where B >= 32 (with fewer rows
+    than that, half the columns of a half-zero g have no term at all: (1, 4, 32) has 18 % and is there for its geometry); the
+    upstream gradient is about half zeros and never zero on a label column."""
+    c = head_case(B, N, D)
+    lab, nnz = c["labels"], c["nnz"]
+    has = lab >= 0
+    cols = X.head_label_columns(N)
+    assert {N - 1, 4 * ((N - 1) // 4), 0} <= set(cols) and (N <= 64 or {63, 64, 64 * (N // 64) - 1, 64 * (N // 64 - 1)} <= set(cols))
+    assert N <= 4 or {3, 4} <= set(cols)
+    assert int((~has).sum()) == (2 if B >= 4 else 0)
+    reach = min(len(cols), int(has.sum()))
+    assert set(cols[:reach]) <= set(lab[has].tolist()) and int(lab[B - 1]) == N - 1
+    if B >= 32:
+        assert set(cols) <= set(lab.tolist())
+    tc = X.head_target_cosines(c)[has]
+    num = set((tc * nnz).round().int().tolist())
+    assert torch.equal(tc * nnz, (tc * nnz).round())
+    if int(has.sum()) >= 3:
+        assert {nnz, -nnz, 0} <= num
+    if int(has.sum()) >= 7:
+        assert bool(((tc > X.HEAD_TH) & (tc < -0.8)).any()) and bool((tc < X.HEAD_TH).any() and (tc[tc < X.HEAD_TH] > -1).any())
+        assert bool((tc > 0).any()) and bool((tc < 0).any())
+        step = 1 if D > nnz else 2   # the smallest non-zero numerator: odd ones need a place off the support
+        assert {step, -step} <= num
+    if (B, N, D) == (129, 65, 32):
+        assert num == set(range(-16, 17))
+        assert {-14, -15} <= num and -14 / 16 > X.HEAD_TH > -15 / 16
+    off = torch.ones(B, N, dtype=torch.bool)
+    off[has.nonzero().flatten(), lab[has]] = False
+    if off.any():
+        assert float((c["cos"][off] != 0).double().mean()) >= 0.8
+    if N >= 32:
+        assert float((c["gx"] != 0).double().mean()) >= 0.8
+    if B >= 32:
+        assert float((c["gw"] != 0).double().mean()) >= 0.8
+    assert float((c["gw"] != 0).double().mean()) > 0.15 and float((c["gx"] != 0).double().mean()) > 0.5
+    g = c["g"]
+    assert bool((g[has.nonzero().flatten(), lab[has]] != 0).all())
+    assert N < 32 or 0.4 < float((g == 0).double().mean()) < 0.6
+    assert set(g.unique().tolist()) <= {-2.0, -1.0, 0.0, 1.0, 2.0}
+    # the geometry each shape is there for (frhip/functional.py: Np = pad32, ld = pad4, splitk = max(1, min(nk, 64, nk // 8)))
+    nk = c["Np"] // 32
+    want = {(1, 4, 32): (32, 4, 1), (37, 203, 64): (224, 204, 1), (129, 65, 32): (96, 68, 1), (5, 500, 32): (512, 500, 2),
+            (130, 1000, 512): (1024, 1000, 4), (37, 203, 96): (224, 204, 1)}[(B, N, D)]
+    assert (c["Np"], c["ld"], max(1, min(nk, 64, nk // 8))) == want
+
+
+@pytest.mark.parametrize("B,N,D", [(37, 203, 64), (129, 65, 32)], ids=["37_203_64", "129_65_32"])
+def test_head_references_equal_the_oracle_and_autograd(B, N, D):
+    """The float64 references against code that was not written for them, on the labelled rows: the oracle's CosFace / ArcFace
+    (oracle/irse_ref.py, float64) for the logits -- the two-operation fp32 values within an fp32 rounding of the float64 ones,
+    the phi branch within the fp32 rounding of the constants -- and torch autograd for d phi / d cos (dphi_ref) and for the shared
+    cosine backward (cosine_backward)."""
+    from oracle import irse_ref as O
+    c = head_case(B, N, D)
+    rows = (c["labels"] >= 0).nonzero().flatten()
+    lab = c["labels"][rows]
+    x = c["x"][rows].double().requires_grad_(True)
+    w = c["w"].double().requires_grad_(True)
+    assert float((O.cosine_logits(x, w).detach() - c["cos"][rows]).abs().max()) < 1e-15
+    for name, (kind, s, m, easy) in X.HEAD_CONFIGS.items():
+        k = X.margin_constants(name)
+        ref, bound, moved = X.margin_logits_ref(c, k)
+        y = O.cosface_forward(x, w, lab, s, m) if kind == 1 else O.arcface_forward(x, w, lab, s, m, bool(easy))
+        assert float((y.detach() - ref[rows]).abs().max()) < 64 * 2.0 ** -22, name
+        assert float(bound.max()) < 64 * 2.0 ** -20 and bool((bound[~moved] == 0).all())
+        # d logits / d cos on the label column = s * dphi
+        cos = c["cos"][rows].clone().requires_grad_(True)
+        tl = cos[torch.arange(len(rows)), lab]
+        if kind == 1:
+            phi = tl - k["cos_m"]
+        else:
+            full = tl * k["cos_m"] - torch.sqrt((1.0 - tl * tl).clamp(X.EPS32, 1.0)) * k["sin_m"]
+            phi = torch.where(tl > 0, full, tl) if easy else torch.where(tl > k["th"], full, tl - k["mm"])
+        (d_auto,) = torch.autograd.grad(phi.sum(), [cos])
+        d_auto = d_auto[torch.arange(len(rows)), lab]
+        for i, r in enumerate(rows.tolist()):
+            d, db = X.dphi_ref(float(c["cos"][r, lab[i]]), k)
+            cc = float(c["cos"][r, lab[i]])
+            if abs(cc) == 1.0 or cc == 0.0:   # at the clamp autograd's subgradient is torch's choice; the kernel's mask is strict
+                assert d in (1.0, k["cos_m"]) and db == 0.0
+            else:
+                assert abs(float(d_auto[i]) - d) < 1e-12, (name, r, cc)
+    # the shared backward from CosFace's gcos: autograd through F.normalize and F.linear
+    gcos = c["gcos"][rows][:, :N]
+    gx, gw = torch.autograd.grad(O.cosine_logits(x, w), [x, w], gcos)
+    r = X.cosine_backward(c["xn"][rows], c["inv_x"][rows], c["wn"][:N], c["inv_w"], gcos)
+    assert float((gx - r["gx"]).abs().max()) <= 1e-12 * float(r["gx"].abs().max())
+    assert float((gw - r["gw"]).abs().max()) <= 1e-12 * float(r["gw"].abs().max())
+
+
+def test_head_clearance_check_refuses_a_cosine_on_the_threshold(monkeypatch):
+    monkeypatch.setattr(X, "HEAD_TH", -14.0 / 16 + 2.0 ** -12)
+    with pytest.raises(AssertionError) as e:
+        X.head_case(129, 65, 32)
+    assert "from th" in str(e.value), str(e.value)
+
+
+SENT = 24576.0
+
+
+def _forward_ok(c, k):
+    ref, bound, _ = X.margin_logits_ref(c, k)
+    cos_t = X.head_target_cosines(c)
+    cos_t[torch.isnan(cos_t)] = SENT
+    return ref.float(), cos_t.float()
+
+
+def _row_with(c, pred, neighbour=True):
+    """The first labelled row that `pred` accepts (neighbour: and whose label column has one to its right)."""
+    for b in range(c["B"]):
+        lab = int(c["labels"][b])
+        if lab >= 0 and (lab + 1 < c["N"] or not neighbour) and pred(b, lab):
+            return b, lab
+    raise AssertionError("the recipe has no such row: test data")
+
+
+@pytest.mark.parametrize("name", sorted(X.HEAD_CONFIGS))
+def test_margin_comparators_catch_planted_defects(name):
+    """The comparators of test_gpu_exact_head.py on the float64 reference (rounded to fp32, as a kernel's output is) with one
+    defect planted at a time: the margin on column label + 1, cos_t from the neighbouring column, one non-zero in a padding column
+    of gcos, dphi with the clamp mask passing at c = 1, a label -1 row with the margin applied to column 0.  Each control first
+    shows that the unplanted reference passes and that the defect changes it; the failure names the element."""
+    c = head_case(37, 203, 64)
+    k = X.margin_constants(name)
+    ref, bound, moved = X.margin_logits_ref(c, k)
+    logits, cos_t = _forward_ok(c, k)
+    X.check_margin_forward(logits, cos_t, c, k, SENT, "control")
+    plain = (k["s"] * c["cos"]).float()
+
+    # the margin one column off
+    b, lab = _row_with(c, lambda b, lab: bool(moved[b, lab]))
+    bad = logits.clone()
+    bad[b, lab + 1] = plain[b, lab + 1] + (logits[b, lab] - plain[b, lab])
+    bad[b, lab] = plain[b, lab]
+    assert not torch.equal(bad, logits)
+    with pytest.raises(AssertionError) as e:
+        X.check_margin_forward(bad, cos_t, c, k, SENT, "control")
+    assert "2 of" in str(e.value) and "first at (%d, %d)" % (b, lab) in str(e.value), str(e.value)
+
+    # cos_t from the neighbouring column
+    b, lab = _row_with(c, lambda b, lab: float(c["cos"][b, lab + 1]) != float(c["cos"][b, lab]))
+    bad_t = cos_t.clone()
+    bad_t[b] = c["cos"][b, lab + 1]
+    with pytest.raises(AssertionError) as e:
+        X.check_margin_forward(logits, bad_t, c, k, SENT, "control")
+    assert "cos_t" in str(e.value) and "first at (%d,)" % b in str(e.value), str(e.value)
+
+    # a row without a label: cos_t written, and the margin applied to column 0
+    b = int((c["labels"] < 0).nonzero()[0])
+    bad_t = cos_t.clone()
+    bad_t[b] = c["cos"][b, 0]
+    with pytest.raises(AssertionError) as e:
+        X.check_margin_forward(logits, bad_t, c, k, SENT, "control")
+    assert "cos_t" in str(e.value) and "first at (%d,)" % b in str(e.value), str(e.value)
+    bad = logits.clone()
+    bad[b, 0] = (c["cos"][b, 0] - 0.35) * k["s"]
+    assert bad[b, 0] != logits[b, 0]
+    with pytest.raises(AssertionError) as e:
+        X.check_margin_forward(bad, cos_t, c, k, SENT, "control")
+    assert "1 of" in str(e.value) and "first at (%d, 0)" % b in str(e.value), str(e.value)
+
+    # the backward pass
+    g, labels, Np = c["g"], c["labels"], c["Np"]
+    gref, gbound = X.margin_gcos_ref(g, labels, cos_t.double(), k, Np)
+    gcos = gref.float()
+    X.check_margin_backward(gcos, g, labels, cos_t.double(), k, "control")
+    bad = gcos.clone()
+    bad[36, Np - 1] = 2.0 ** -20                                      # one non-zero in a padding column
+    with pytest.raises(AssertionError) as e:
+        X.check_margin_backward(bad, g, labels, cos_t.double(), k, "control")
+    assert "1 of" in str(e.value) and "first at (36, %d)" % (Np - 1) in str(e.value), str(e.value)
+    bad = gcos.clone()
+    bad[0, Np - 3] = -0.0                                             # ... and a -0 there
+    with pytest.raises(AssertionError) as e:
+        X.check_margin_backward(bad, g, labels, cos_t.double(), k, "control")
+    assert "not +0" in str(e.value), str(e.value)
+    if k["kind"] == 0:                                                # the clamp mask passing at c = 1
+        b, lab = _row_with(c, lambda b, lab: float(c["cos"][b, lab]) == 1.0, neighbour=False)
+        bad = gcos.clone()
+        bad[b, lab] = k["s"] * g[b, lab] * (k["cos_m"] + k["sin_m"] * 1.0 / (X.EPS32 ** 0.5))
+        assert bad[b, lab] != gcos[b, lab] and float(gbound[b, lab]) == 0.0
+        with pytest.raises(AssertionError) as e:
+            X.check_margin_backward(bad, g, labels, cos_t.double(), k, "control")
+        assert "1 of" in str(e.value) and "first at (%d, %d)" % (b, lab) in str(e.value), str(e.value)
+        # one ulp beside an exact value fails, the bounded branch takes a rounding and refuses 1e-4 of the value
+        b2, lab2 = _row_with(c, lambda b, lab: float(gbound[b, lab]) > 0)
+        near = gcos.clone()
+        near[b2, lab2] = torch.nextafter(gcos[b2, lab2], torch.tensor(1e9))
+        X.check_margin_backward(near, g, labels, cos_t.double(), k, "control")
+        near[b2, lab2] = gcos[b2, lab2] * (1.0 + 1e-4)
+        with pytest.raises(AssertionError):
+            X.check_margin_backward(near, g, labels, cos_t.double(), k, "control")
+    else:                                                             # CosFace: s * g on the label column too
+        b, lab = _row_with(c, lambda b, lab: True)
+        bad = gcos.clone()
+        bad[b, lab] = torch.nextafter(gcos[b, lab], torch.tensor(1e9))
+        with pytest.raises(AssertionError) as e:
+            X.check_margin_backward(bad, g, labels, cos_t.double(), k, "control")
+        assert "first at (%d, %d)" % (b, lab) in str(e.value), str(e.value)
