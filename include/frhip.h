@@ -872,6 +872,23 @@ int fr_augment_u8_gather(const uint8_t* store, const int64_t* labels, const int3
                          const int32_t* ytab, const int32_t* crop, const uint8_t* flip, const float* lut, float* out,
                          int64_t* label_out, int M, int B, int Hin, int Win, int Hr, int Wr, int S, int kx, int ky,
                          void* stream);
+/* RandAugment on the decoded images (data_processing/randaugment.py, the served set): image b of the batch is
+ * src[idx ? idx[b] : b], taken through the K operations (op[b][k], par[b][k]), k = 0 .. K-1 in order, every step rounded
+ * to uint8 as Pillow rounds between operations; the bytes are Pillow's (tests/randaug_ref.py).  One workgroup per image:
+ * one read from HBM, the whole chain in LDS, one write.  Integer statistics only: the same bytes from run to run.
+ *   src uint8 [idx ? M : B][H][W][3]    dst uint8 [B][H][W][3]    op uint8 [B][K]    par float32 [B][K]
+ *   idx int32 [B] or null, 0 <= idx[b] < M (checked by the caller: device memory), may repeat, in any order; the slot
+ *   offset is formed in 64 bits    labels int64 [M] / label_out int64 [B]: label_out[b] = labels[slot] when both are given
+ *   op  0 identity (equalize, which the reference leaves undone; padding; any code above 9)
+ *       1 autocontrast                          6 brightness, par = factor
+ *       2 solarize, par = threshold             7 translateX, par = integer shift sx: out[y][x] = in[y][x + sx], else black
+ *       3 color, par = factor                   8 translateY, par = integer shift sy: out[y][x] = in[y + sy][x], else black
+ *       4 posterize, par = bits kept (0..8)     9 invert
+ *       5 contrast, par = factor (the mean is that of the image as the step finds it)
+ * B <= 0 returns 0.  Refused before any launch: B > 65535, K outside 1..16, a null src / op / par / dst, M <= 0 with idx,
+ * H or W <= 0, and an image beyond the LDS budget H * W * 3 + 3 * 256 * 4 <= 65536 (128x128 fits, 148x148 does not). */
+int fr_randaug_u8(const uint8_t* src, const int64_t* labels, const int32_t* idx, const uint8_t* op, const float* par,
+                  uint8_t* dst, int64_t* label_out, int M, int B, int K, int H, int W, void* stream);
 /* F.interpolate(x, size, mode='bilinear') of pSp.forward (backbone/restyle_psp.py:440-443: align_corners = False, no
  * antialias) on fp32 NCHW planes: in [planes][Hin][Win] -> out [planes][Hout][Wout]; planes = B * C <= 65535. */
 int fr_resize_bilinear(const float* in, float* out, int planes, int Hin, int Win, int Hout, int Wout, void* stream);

@@ -60,6 +60,12 @@ def stage3(exp_name, **overrides):
                                          # memory and draw every batch from there in one launch (frhip/resident.py); the
                                          # samples, crops, flips and checkpoints of the GPU_INPUT_PIPELINE run, bit for bit
         GPU_RESIDENT_MAX_GB=None,        # the most the resident set may take; None: half of the device's free memory
+        GPU_RANDAUGMENT=False,           # True (needs GPU_INPUT_PIPELINE=True): the reference's Rand_Augment policy on the
+                                         # decoded images, one more launch per batch (fr_randaug_u8); rotate, shearX, shearY
+                                         # and sharpness are not served on the device
+        GPU_RANDAUGMENT_NUM=None,        # operations per image, 1..16; None: half the number of operations (5 of 10)
+        GPU_RANDAUGMENT_MAX_MAGNITUDE=10,  # magnitude indices are drawn below it, 1..10
+        GPU_RANDAUGMENT_OPS=None,        # None: the served set (frhip.input_pipeline.SERVED), or a list of its names
     )
     cfg.update(overrides)
     return cfg

@@ -12,6 +12,10 @@ order (``epoch_batches`` instantiates the same ``DistributedSampler`` and ``Batc
 (``GpuTrainTransform.draw``), the same transform (the kernel shares its per-pixel body with ``fr_augment_u8``), and the same
 use of the global torch generator (one draw per epoch, the ``DataLoader``'s worker base seed), so the ``State_*`` files
 agree too.  Every rank holds the whole set.
+
+With RandAugment on (``gpu_tf.randaug``) the gather moves into ``fr_randaug_u8``, which reads ``store[idx[b]]``, writes the
+augmented uint8 batch and the labels, and the unchanged ``fr_augment_u8`` runs on that batch: the loader path's two launches,
+with the chain of every image drawn after the batch's crop / flip draws, as there.
 """
 import time
 
@@ -187,6 +191,30 @@ class ResidentLoader(object):
             if idx.min() < 0 or idx.max() >= m:
                 raise ValueError("resident: batch index outside [0, %d): %d .. %d" % (m, idx.min(), idx.max()))
             crop, flip = tf.draw(b, generator)
+            if getattr(tf, "randaug", None) is not None:
+                # RandAugment on: the gather moves into fr_randaug_u8 (idx, labels), and the unchanged fr_augment_u8 runs on
+                # the staged result -- the loader path's two launches, draws in the loader path's order.  Still one pinned
+                # block and one asynchronous copy, 13 + 5 K bytes per image:
+                # [idx int32 b | crop int32 2b | par float32 bK | flip uint8 b | op uint8 bK]
+                op, par = tf.randaug.draw(b, generator, (h, w))
+                k = int(op.shape[1])
+                host = torch.empty((BYTES_PER_IMAGE + 5 * k) * b, dtype=torch.uint8, pin_memory=True)
+                host[:4 * b].view(torch.int32).copy_(torch.from_numpy(idx))
+                host[4 * b:12 * b].view(torch.int32).copy_(crop.reshape(-1))
+                host[12 * b:(12 + 4 * k) * b].view(torch.float32).copy_(par.reshape(-1))
+                host[(12 + 4 * k) * b:(13 + 4 * k) * b].copy_(flip)
+                host[(13 + 4 * k) * b:].copy_(op.reshape(-1))
+                pack = host.to(dev, non_blocking=True)
+                labels = torch.empty(b, device=dev, dtype=torch.int64)
+                staged = tf.randaug.launch(store.data, pack[(13 + 4 * k) * b:].view(b, k),
+                                           pack[12 * b:(12 + 4 * k) * b].view(torch.float32).view(b, k), b, h, w,
+                                           pack[:4 * b].view(torch.int32), store.labels, labels)
+                out = torch.empty(b, 3, tf.size, tf.size, device=dev, dtype=torch.float32)
+                ops.call("fr_augment_u8", staged, xtab, ytab, pack[4 * b:12 * b].view(torch.int32),
+                         pack[(12 + 4 * k) * b:(13 + 4 * k) * b], lut, out, b, h, w, tf.big, tf.big, tf.size, kx, ky,
+                         ops.current_stream_ptr())()
+                yield out, labels
+                continue
             # one pinned block, one asynchronous copy: [idx int32 b | crop int32 2b | flip uint8 b]
             host = torch.empty(BYTES_PER_IMAGE * b, dtype=torch.uint8, pin_memory=True)
             host[:4 * b].view(torch.int32).copy_(torch.from_numpy(idx))

@@ -211,6 +211,35 @@ def check_input_config(cfg):
                                   "transform (staged uint8 images), not the host transform")
 
 
+def check_randaug_config(cfg):
+    """RandAugment on the GPU input pipeline (frhip.input_pipeline.GpuRandAugment), validated before anything is built.
+    GPU_RANDAUGMENT: False (the default) or True; GPU_RANDAUGMENT_NUM: None (half the number of operations, the reference's
+    rule) or 1..16 operations per image; GPU_RANDAUGMENT_MAX_MAGNITUDE: 1..10 (default 10), magnitude indices are drawn
+    below it; GPU_RANDAUGMENT_OPS: None (the served set) or a list of served names.  Returns None when it is off -- nothing
+    is built and the loop is the one without it -- else (num, max_magnitude, ops)."""
+    from frhip.input_pipeline import RANDAUG_MAX_STEPS, check_randaug_ops
+    on = cfg.get("GPU_RANDAUGMENT", False)
+    if not isinstance(on, bool):
+        raise ValueError("GPU_RANDAUGMENT must be True or False, got %r" % (on,))
+    if not on:
+        return None
+    if not cfg.get("GPU_INPUT_PIPELINE", False):
+        raise NotImplementedError("GPU_RANDAUGMENT=True needs GPU_INPUT_PIPELINE=True: RandAugment runs on the GPU input "
+                                  "pipeline (fr_randaug_u8 on the staged uint8 images); the host workers do not run it")
+    num, mag = cfg.get("GPU_RANDAUGMENT_NUM", None), cfg.get("GPU_RANDAUGMENT_MAX_MAGNITUDE", 10)
+    ops = cfg.get("GPU_RANDAUGMENT_OPS", None)
+    if ops is not None and (isinstance(ops, str) or not isinstance(ops, (list, tuple))):
+        raise ValueError("GPU_RANDAUGMENT_OPS must be None or a list of operation names, got %r" % (ops,))
+    ops = check_randaug_ops(ops, "GPU_RANDAUGMENT_OPS")  # an unserved name: NotImplementedError with the reason
+    if num is not None and (isinstance(num, bool) or not isinstance(num, int) or not 1 <= num <= RANDAUG_MAX_STEPS):
+        raise ValueError("GPU_RANDAUGMENT_NUM must be None or an integer in 1..%d, got %r" % (RANDAUG_MAX_STEPS, num))
+    if num is None and len(ops) // 2 < 1:
+        raise ValueError("GPU_RANDAUGMENT_NUM=None draws len(ops) // 2 operations per image, which is 0 for %r" % (ops,))
+    if isinstance(mag, bool) or not isinstance(mag, int) or not 1 <= mag <= 10:
+        raise ValueError("GPU_RANDAUGMENT_MAX_MAGNITUDE must be an integer in 1..10, got %r" % (mag,))
+    return num, mag, ops
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=str, default="config.py")
@@ -221,6 +250,7 @@ def main():
     check_head_config(cfg)
     check_input_config(cfg)
     guard_cfg = check_guard_config(cfg)
+    randaug_cfg = check_randaug_config(cfg)
 
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -253,6 +283,13 @@ def main():
         # workers decode only; resize / crop / flip / normalise run on the GPU per batch (frhip/input_pipeline.py)
         from frhip.input_pipeline import GpuTrainTransform
         gpu_tf = GpuTrainTransform(cfg["INPUT_SIZE"][0], cfg["RGB_MEAN"], cfg["RGB_STD"])
+        if randaug_cfg is not None:
+            # the reference's Rand_Augment policy on the decoded images, one more launch per batch; its draws follow the
+            # batch's crop / flip draws on aug_rng, so resumed runs and the resident path see the same chains
+            from frhip.input_pipeline import GpuRandAugment
+            gpu_tf.randaug = GpuRandAugment(*randaug_cfg)
+            print("GPU RandAugment: {} operations per image from {}, magnitude index below {}".format(
+                gpu_tf.randaug.num, list(gpu_tf.randaug.ops), gpu_tf.randaug.max_magnitude))
         aug_rng = torch.Generator().manual_seed(cfg["SEED"] + 7919 * rank)
     if args.synthetic:
         ids, per = (int(v) for v in args.synthetic.split("x"))
